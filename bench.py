@@ -18,9 +18,21 @@ point-in-polygon join.  The other configurations print one line each in the same
 A step = one full pass of the operator over one batch that is ALREADY RESIDENT IN HBM (C2 rotates through
 `--rotate` distinct input / output sets, > 256 MiB in total, so that no step finds its inputs in the Infinity
 Cache).  Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed on the launching
-stream), and at N=1 `cpu_baseline` (the CPU oracle on the host cores over a bounded sample of the same
-workload).  Every line is gated by parity: the GPU result of the last step is compared with the oracle on a
-RANDOM sample of rows (>= 200k, `--parity-rows`); a run that fails parity prints no number.
+stream).
+
+A plain run does only what the headline figure needs: set up, warm up, time exactly `--steps` steps, write the
+last step's outputs when `--dump-outputs DIR` is given, print the line.  `--full` adds everything else, as
+extra legs of the same run: at N=1 `cpu_baseline` (the CPU oracle on the host cores over a bounded sample of
+the same workload), the secondary measurements each configuration reports in `config` (C2: the PCIe leg, the
+weak-scaled form, the default call shape, the exact phase's counters; C3: the shuffled row map and the one-shot
+call; C4 / C5: repeated index builds, C5's index variant, full-column area and right-partitioned one-shot), and
+parity: the GPU result is compared with the oracle on a RANDOM sample of rows (>= 200k, `--parity-rows`);
+a full run that fails parity prints no number.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (rank 0's share) as DIR/<name>.npy,
+float32 where every value is exact in it, float64 otherwise: per-row outputs at a fixed, seeded sample of at
+most DUMP_ROWS rows (`sample_rows.npy` names them), the pairs whose left row is in that sample, and the total.
+The inputs depend on the arguments only, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -46,6 +58,9 @@ RANDOM_LINE_PEAK_GBS = 50e9 * 64 / 1e9  # tools/micro/random_lines.hip: independ
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (about 6.3 achievable)
 F64_VALU_PEAK = 39.3e12  # f64 vector instructions / s: 78.6 TFLOP/s FMA = 39.3 T instructions
 C5_CHUNKS = 8  # the C5 right side is the concatenation of 8 fixed chunks of 625k multipolygons (one per rank at 8 GPUs)
+DUMP_ROWS = 1 << 19  # --dump-outputs: per-row outputs are written at a fixed sample of this many rows (all of them when there are fewer)
+DUMP_SEED = 4245
+DUMP_MAX_BYTES = 64 << 20
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -377,6 +392,38 @@ def pairs_of_rows(pairs: np.ndarray, rows: np.ndarray) -> np.ndarray:
     return out
 
 
+def dump_arrays(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy, float32 when every value survives the cast exactly, float64 otherwise"""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        f32 = a.astype(np.float32)
+        exact = np.array_equal(f32.astype(a.dtype), a, equal_nan=a.dtype.kind == "f")
+        conv[name] = f32 if exact else a.astype(np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def dump_join(out_dir: str, counts, pairs, total: int, base: int = 0, per_row: dict | None = None) -> None:
+    """--dump-outputs of a join: hit counts (+ other per-row outputs) at the fixed row sample, the (l, r) pairs whose left row
+    (global numbering: `base` is the join's left_row_base) is in the sample, and the total number of pairs"""
+    idx = sample_rows(int(counts.shape[0]), DUMP_ROWS, seed=DUMP_SEED)
+    gc = counts.cpu().numpy()
+    h = min(int(total), int(pairs.shape[0]))
+    gp = pairs[:h].cpu().numpy().astype(np.int64)
+    got = pairs_of_rows(gp - np.array([base, 0]), idx)
+    got[:, 0] = idx[got[:, 0]] + base
+    arrays = {"sample_rows": idx + base, "counts": gc[idx], "pairs": got, "n_pairs": np.array([total], dtype=np.int64)}
+    for name, t in (per_row or {}).items():  # (a per-row output of another column: its own sample, named <name>_rows)
+        rows = sample_rows(int(t.shape[0]), DUMP_ROWS, seed=DUMP_SEED)
+        arrays[name], arrays[f"{name}_rows"] = t.cpu().numpy()[rows], rows
+    dump_arrays(out_dir, arrays)
+
+
 def base_line(ctx: Ctx, metric: str, value: float, unit: str, ms_per_step: float, scaling: str, config: dict, roofline: dict) -> dict:
     a = ctx.args
     return {
@@ -459,9 +506,9 @@ def run_c2(ctx: Ctx) -> None:
         torch.cuda.synchronize()
         return out, t_h2d
 
-    sets, t_h2d = build_sets(lo, hi, 0, True)  # (strong: every rank slices the SAME columns — seed independent of the rank)
+    sets, t_h2d = build_sets(lo, hi, 0, args.full)  # (strong: every rank slices the SAME columns — seed independent of the rank)
     sync_steps = args.sync_steps or args.index_per_step
-    last = {"set": 0}
+    last = {"set": 0, "h": 0}
     cur = {"sets": sets}
 
     def step(i: int) -> None:
@@ -472,7 +519,7 @@ def run_c2(ctx: Ctx) -> None:
         last["set"] = i % R
         if sync_steps:
             idx = SpatialIndex.from_device(polys, stream=stream, light=True) if args.index_per_step else index
-            join_pairs_device(s["pts"], polys, idx, "intersects", s["counts"], s["pairs"], left_row_base=s["base"], stream=stream)
+            last["h"] = join_pairs_device(s["pts"], polys, idx, "intersects", s["counts"], s["pairs"], left_row_base=s["base"], stream=stream)
             if args.index_per_step:
                 idx.free()
         else:
@@ -483,8 +530,12 @@ def run_c2(ctx: Ctx) -> None:
                                               one_launch_steps=lambda w: "gpk_pip_write" not in w and not sync_steps)
     fused = "gpk_pip_write" not in warm
     rank_seconds_main = list(getattr(ctx, "rank_seconds", []))
+    s_last = sets[last["set"]]  # what the last timed step wrote
+    h = last["h"] if sync_steps else int(s_last["total"].item())
+    if args.dump_outputs and ctx.rank == 0:
+        dump_join(args.dump_outputs, s_last["counts"], s_last["pairs"], h, base=s_last["base"])
     weak = None
-    if (W > 1 or args.force_weak) and not args.no_weak:  # the weak-scaled form beside the headline: 10M points PER GPU (rank-dependent seeds)
+    if args.full and (W > 1 or args.force_weak) and not args.no_weak:  # the weak-scaled form beside the headline: 10M points PER GPU (rank-dependent seeds)
         del sets
         torch.cuda.empty_cache()
         cur["sets"], _ = build_sets(0, n, ctx.rank + 1, False)
@@ -499,7 +550,7 @@ def run_c2(ctx: Ctx) -> None:
     # built inside every call — measured beside the prepared-index step on the N = 1 line (blocking entry point, index built and freed
     # per step; a second, shorter timed region)
     default_shape = None
-    if W == 1 and not args.index_per_step and not args.no_default_shape:
+    if args.full and W == 1 and not args.index_per_step and not args.no_default_shape:
         def step_default(i: int) -> None:
             s_ = sets[i % R]
             idx = SpatialIndex.from_device(polys, stream=stream, light=True)
@@ -530,15 +581,17 @@ def run_c2(ctx: Ctx) -> None:
                                                                     "what": "gpk_spatial_join(right_index = NULL) called again and again with the same right-side handle: the index built by the first call stays on the handle (blocking entry point: one host round trip per call)"}}
     # what the exact phase did, measured on one extra untimed step (a few atomics per tile: never inside the timed region)
     st = (C.c_int64 * 4)()
-    if not args.no_join_stats:
+    join_stats = args.full and not args.no_join_stats
+    if join_stats:
         lib.gpk_join_stats_enable(1)
         lib.gpk_join_stats(st, 1)
         step(args.warmup + args.steps)  # same set the next timed step would have used
         lib.gpk_join_stats(st, 1)
         lib.gpk_join_stats_enable(0)
     torch.cuda.synchronize()
-    s_last = sets[last["set"]]
-    h = join_pairs_device(s_last["pts"], polys, index, "intersects", s_last["counts"], s_last["pairs"], left_row_base=s_last["base"], stream=stream)
+    if args.full:  # (parity checks a blocking call over the set the last step used)
+        s_last = sets[last["set"]]
+        h = join_pairs_device(s_last["pts"], polys, index, "intersects", s_last["counts"], s_last["pairs"], left_row_base=s_last["base"], stream=stream)
     if ctx.rank != 0:
         ctx.finish()
         return
@@ -585,8 +638,8 @@ def run_c2(ctx: Ctx) -> None:
         "join_bytes_per_step": bytes_join,
         "join_GBps_end_to_end": bytes_join / step_s / 1e9,
         "kernel_ms": {"gpk_pip_tile": k_tile, "gpk_pip_write (warm-up steps)": k_write, "gpk_join_prep (warm-up steps)": warm.get("gpk_join_prep", 0.0)},
-        "exact_phase": {"test_points_per_step": queued, "edge_tests_per_step": edges, "rows_deferred_to_the_generic_walk_per_step": int(st[2])},
-        "edge_tests_per_s": edges / step_s if step_s > 0 else None,
+        "exact_phase": {"test_points_per_step": queued, "edge_tests_per_step": edges, "rows_deferred_to_the_generic_walk_per_step": int(st[2])} if join_stats else None,
+        "edge_tests_per_s": edges / step_s if join_stats and step_s > 0 else None,
         "valu_busy": valu_busy,
         "pcie_inclusive": None
         if t_h2d is None
@@ -611,8 +664,9 @@ def run_c2(ctx: Ctx) -> None:
         "source_hash": source_hash(),
     }
     out = base_line(ctx, "predicate evals/sec (10M pts x 1k polys point-in-polygon)", evals / elapsed, "evals/s", ms_per_step, "strong", config, roofline)
-    out["parity"] = parity_point_join(s_last["host"], polys_host, "intersects", s_last["counts"], s_last["pairs"], h, args.parity_rows, base=s_last["base"])
-    if ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["parity"] = parity_point_join(s_last["host"], polys_host, "intersects", s_last["counts"], s_last["pairs"], h, args.parity_rows, base=s_last["base"])
+    if args.full and ctx.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_join(s_last["host"], polys_host, "intersects", s_last["counts"], args.cpu_seconds)
     ctx.finish()  # (RCCL may print its banner while the group goes down: the JSON line stays the last line of stdout)
     emit_line(out)
@@ -716,14 +770,15 @@ def run_c3(ctx: Ctx) -> None:
 
     out = torch.empty(n, dtype=torch.float64, device=dev)
     results = {}
-    for label, rows in (("rows = i mod L", rows_mod), ("rows shuffled", rows_shuf)):
+    legs = (("rows = i mod L", rows_mod), ("rows shuffled", rows_shuf)) if args.full else (("rows = i mod L", rows_mod),)
+    for label, rows in legs:
         r_dev = torch.from_numpy(rows.view(np.int32)).to(dev)
         # the row map is an input that stays the same from step to step (a foreign-key column): ordered once, like a prebuilt
         # r_index (spatial_index.rs:558-624); the one-shot call that orders it inside is timed next to it
         torch.cuda.synchronize()
         build = []
         rmap = None
-        for _ in range(3):
+        for _ in range(3 if args.full else 1):
             if rmap is not None:
                 rmap.free()
             t0 = time.perf_counter()
@@ -737,7 +792,14 @@ def run_c3(ctx: Ctx) -> None:
         # (a step is one launch of gpk_distance_grouped: one event pair around the K launches — a pair per launch measured 0.565 ms
         # where the warm-up saw 0.493 and rocprofv3 0.515: the line now has ONE number for the kernel, gaps included)
         elapsed, k_ms, k_n, warm = ctx.timed(step, "gpk_distance_grouped", args.steps, args.warmup, one_launch_steps=lambda w: set(w) == {"gpk_distance_grouped"})
-        results[label] = {"elapsed": elapsed, "k_ms": k_ms, "launches": k_n, "warm": warm, "parity": None, "rowmap_build_ms": min(build)}
+        results[label] = {"elapsed": elapsed, "k_ms": k_ms, "launches": k_n, "warm": warm, "parity": None, "rowmap_build_ms": min(build), "one_shot_ms": None}
+        if args.dump_outputs and ctx.rank == 0 and label == "rows = i mod L":
+            torch.cuda.synchronize()
+            idx = sample_rows(n, DUMP_ROWS, seed=DUMP_SEED)
+            dump_arrays(args.dump_outputs, {"sample_rows": idx, "distance": out.cpu().numpy()[idx]})
+        if not args.full:
+            rmap.free()
+            break
         if ctx.rank == 0:
             results[label]["parity"] = parity_distance(pts_host, ls_host, rows, out, args.parity_rows)
         out.zero_()
@@ -782,7 +844,7 @@ def run_c3(ctx: Ctx) -> None:
             "rowmap_build_ms": results["rows shuffled"]["rowmap_build_ms"],
             "one_shot_ms": results["rows shuffled"]["one_shot_ms"],
             "parity": results["rows shuffled"]["parity"],
-        },
+        } if args.full else None,
     }
     roofline = {
         "bound": "hbm",
@@ -803,8 +865,9 @@ def run_c3(ctx: Ctx) -> None:
     if n == 10_000_000 and args.lines == 100_000:
         roofline_traffic(roofline, "c3")
     line = base_line(ctx, "row-wise point-linestring distances/sec (10M pts x 100k linestrings)", ctx.world * n * args.steps / main["elapsed"], "rows/s", ms_per_step, "weak", config, roofline)
-    line["parity"] = main["parity"]
-    if ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["parity"] = main["parity"]
+    if args.full and ctx.world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_distance(pts_host, ls_host, rows_mod, args.cpu_seconds)
     ctx.finish()  # (RCCL may print its banner while the group goes down: the JSON line stays the last line of stdout)
     emit_line(line)
@@ -906,7 +969,7 @@ def run_c4(ctx: Ctx) -> None:
     nl = hi - lo
     build_ms = []
     index = None
-    for _ in range(3):
+    for _ in range(3 if args.full else 1):
         if index is not None:
             index.free()
         torch.cuda.synchronize()
@@ -924,8 +987,10 @@ def run_c4(ctx: Ctx) -> None:
 
     elapsed, k_ms, k_n, warm = ctx.timed(step, "gpk_pair_refine", args.steps, args.warmup)
     h = hits["h"]
+    if args.dump_outputs and ctx.rank == 0:
+        dump_join(args.dump_outputs, counts, pairs, h, base=lo)
     total_pairs = ctx.sum_over_ranks(float(h))
-    parity = parity_poly_join(left_host, right_full, counts, pairs, h, lo, args.parity_rows) if ctx.rank == 0 else None
+    parity = parity_poly_join(left_host, right_full, counts, pairs, h, lo, args.parity_rows) if args.full and ctx.rank == 0 else None
     if ctx.rank != 0:
         ctx.finish()
         return
@@ -967,8 +1032,9 @@ def run_c4(ctx: Ctx) -> None:
     if args.polygons == 1_000_000 and W == 1:
         roofline_traffic(roofline, "c4")
     line = base_line(ctx, "polygon-pair intersects() join rows/sec (1M x 1M polygons)", n * args.steps / elapsed, "left rows/s", ms_per_step, "strong", config, roofline)
-    line["parity"] = parity
-    if W == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["parity"] = parity
+    if args.full and W == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_polyjoin(left_host, right_full, counts, args.cpu_seconds)
     ctx.finish()  # (RCCL may print its banner while the group goes down: the JSON line stays the last line of stdout)
     emit_line(line)
@@ -1058,11 +1124,13 @@ def run_c5(ctx: Ctx) -> None:
     torch.cuda.synchronize()
     build_ms = (time.perf_counter() - t0) * 1e3
     # the same build once more: the first one also grows the library's scratch arenas and size-classifies the column (one-off per process / column)
-    t0 = time.perf_counter()
-    again = SpatialIndex.from_device(right, stream=stream)
-    torch.cuda.synchronize()
-    build_again_ms = (time.perf_counter() - t0) * 1e3
-    again.free()
+    build_again_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        again = SpatialIndex.from_device(right, stream=stream)
+        torch.cuda.synchronize()
+        build_again_ms = (time.perf_counter() - t0) * 1e3
+        again.free()
     pts_host = synth.uniform_points(n, seed=52 + ctx.rank)
     if args.diag_sorted_points:  # diagnosis only (never the reported configuration): the same points in raster order
         xy = pts_host.xy
@@ -1083,8 +1151,11 @@ def run_c5(ctx: Ctx) -> None:
     h = int(total.item())
     if h > pairs.shape[0]:
         raise SystemExit(f"bench.py --config c5: {h} pairs exceed the pair buffer")
+    if args.dump_outputs and ctx.rank == 0:
+        dump_join(args.dump_outputs, counts, pairs, h, per_row={"area": area})
     st = (C.c_int64 * 4)()  # what the exact phase did, on one extra untimed join
-    if not args.no_join_stats:
+    join_stats = args.full and not args.no_join_stats
+    if join_stats:
         lib.gpk_join_stats_enable(1)
         lib.gpk_join_stats(st, 1)
         join_pairs_enqueue(pts, right, index, "within", counts, pairs, total, left_row_base=0, stream=stream)
@@ -1092,16 +1163,18 @@ def run_c5(ctx: Ctx) -> None:
         lib.gpk_join_stats_enable(0)
         torch.cuda.synchronize()
     # area over ALL multipolygons of the gathered right side, once (what one GPU would do alone)
-    area_all = torch.empty(right_buf.n_geoms, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(3):
-        _abi.check(lib.gpk_area(right.handle, area_all.data_ptr(), _abi.MEM_DEVICE, stream))
-    torch.cuda.synchronize()
-    area_all_ms = (time.perf_counter() - t0) * 1e3 / 3
+    area_all_ms = None
+    if args.full:
+        area_all = torch.empty(right_buf.n_geoms, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            _abi.check(lib.gpk_area(right.handle, area_all.data_ptr(), _abi.MEM_DEVICE, stream))
+        torch.cuda.synchronize()
+        area_all_ms = (time.perf_counter() - t0) * 1e3 / 3
     # the same join against an index WITH the per-entry records of its list cells (GPK_INDEX_PIP_FULL): reported, not the headline
     index_full = None
-    if W == 1 and not args.no_index_variants:
+    if args.full and W == 1 and not args.no_index_variants:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         full = SpatialIndex.from_device(right, stream=stream, full=True)
@@ -1122,7 +1195,7 @@ def run_c5(ctx: Ctx) -> None:
     # is measured on this GPU (its shard of the right side = the first 1 / K of the rows, all K x n points) — the collective that
     # replicates the points (16 bytes a row) is the one thing that cannot be timed on one GPU.
     one_shot = None
-    if not args.no_one_shot:
+    if args.full and not args.no_one_shot:
         try:
             from geopolars_amd.dist import join_partition_right
 
@@ -1184,7 +1257,7 @@ def run_c5(ctx: Ctx) -> None:
         "multipolygons": right_host.n_geoms,
         "coordinates": right_host.n_coords,
         "hits_per_step": h,
-        "exact_phase": {"queued_point_part_pairs_per_step": int(st[0]), "edge_tests_per_step": int(st[1])},
+        "exact_phase": {"queued_point_part_pairs_per_step": int(st[0]), "edge_tests_per_step": int(st[1])} if join_stats else None,
         "call": "gpk_spatial_join_async(within) + gpk_area, one stream",
         "index_build_ms": build_ms,
         "index_build_again_ms": build_again_ms,
@@ -1232,9 +1305,10 @@ def run_c5(ctx: Ctx) -> None:
                                            "frac": lines * 64.0 / k_s / 1e9 / RANDOM_LINE_PEAK_GBS,
                                            "note": "counted TCC_EA0_RDREQ lines x 64 B / launch time against 50 G independent random lines/s x 64 B"}
     line = base_line(ctx, "predicate evals/sec (points within power-law multipolygons, + area)", float(W) * n * right_host.n_geoms * args.steps / elapsed, "evals/s", ms_per_step, "weak", config, roofline)
-    line["parity"] = parity_point_join(pts_host, right_host, "within", counts, pairs, h, args.parity_rows)
-    line["parity"]["area"] = parity_area(shard_host, area)
-    if W == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["parity"] = parity_point_join(pts_host, right_host, "within", counts, pairs, h, args.parity_rows)
+        line["parity"]["area"] = parity_area(shard_host, area)
+    if args.full and W == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_join(pts_host, right_host, "within", counts, args.cpu_seconds)
     ctx.finish()  # (RCCL may print its banner while the group goes down: the JSON line stays the last line of stdout)
     emit_line(line)
@@ -1277,6 +1351,8 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: oracle parity, the CPU baseline and every secondary measurement the configuration reports (the --no-* options below trim a full run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (rank 0; per-row outputs at a fixed sample of rows) as DIR/<name>.npy")
     ap.add_argument("--points", type=int, default=None, help="left rows per GPU (c2/c3: 10M, c5: 6.25M)")
     ap.add_argument("--polys", type=int, default=1000, help="c2: right-side polygons")
     ap.add_argument("--verts", type=int, default=64, help="c2: vertices per polygon")

@@ -127,7 +127,7 @@ def test_row_sharded_hip_joins_equal_unsharded(gpk, k):
 def test_bench_n_rank_path_at_world_1(gpk, config, extra):
     """bench.py --force-dist: RCCL initialised, the right side exchanged, parity-gated line printed"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--parity-rows", "20000"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--force-dist", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--parity-rows", "20000"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -141,7 +141,7 @@ def test_bench_falls_back_to_the_torch_exchange_when_the_librarys_communicator_d
     """--comm abi is the default exchange of C4; if gpk_comm_init / the probe collective fail or do not return within --comm-timeout on ANY
     rank, every rank agrees (over the torch group) to run geopolars_amd.dist's exchange instead and the line says which one ran"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), GPK_BENCH_FAIL_COMM="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--parity-rows", "20000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--force-dist", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--parity-rows", "20000",
            "--polygons", "150000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -155,7 +155,7 @@ def test_bench_falls_back_to_the_torch_exchange_when_the_librarys_communicator_d
 def test_bench_c2_strong_scaled_shards(gpk, shard):
     """the headline at N > 1 is STRONG scaled — rank r owns rows [r n / W, (r + 1) n / W) of the fixed 10M points and its pairs carry
     that base; --as-shard r/W runs one rank's share in this process (one GPU here), parity-gated like any line"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--as-shard", shard, "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-default-shape", "--parity-rows", "50000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--as-shard", shard, "--full", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-default-shape", "--parity-rows", "50000"]
     if shard == "5/8":  # (one case also walks the weak-scaled leg that runs beside the headline at N > 1)
         cmd.append("--force-weak")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -174,7 +174,7 @@ def test_bench_launches_its_own_ranks(gpk):
     """`python bench.py --gpus N` with no launcher re-runs itself under torch.distributed.run (exercised here at N = 1 with
     --spawn: the same code path, RCCL initialised by the spawned rank); the line carries every rank's own step time"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--points", "2000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--full", "--points", "2000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
            "--parity-rows", "20000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -182,6 +182,27 @@ def test_bench_launches_its_own_ranks(gpk):
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
     assert line["n_gpus"] == 1 and line["ranks"]["world"] == 1 and line["ranks"]["backend"] == "nccl (RCCL)"
     assert len(line["ranks"]["ms_per_step_per_rank"]) == 1 and line["parity"]["bit_exact"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_outputs(gpk, oracle, tmp_path):
+    """a plain run times exactly --steps steps and prints the headline keys only (no parity, no CPU baseline); --dump-outputs writes
+    the last timed step's counts and pairs at the fixed row sample, which the oracle reproduces on exactly those rows"""
+    n, m, verts = 300_000, 200, 32
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--points", str(n), "--polys", str(m), "--verts", str(verts), "--rotate", "1",
+           "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "evals/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and "parity" not in line and "cpu_baseline" not in line
+    got = {k: np.load(str(tmp_path / f"{k}.npy")) for k in ("sample_rows", "counts", "pairs", "n_pairs")}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    idx = got["sample_rows"].astype(np.int64)
+    assert len(idx) == n and got["n_pairs"][0] == line["config"]["hits_per_step"]  # (fewer rows than the sample size: all of them)
+    pts, polys = synth.uniform_points(n, seed=synth.SEED + 1), synth.star_polygons(m, verts)
+    ep, ec, _ = oracle.spatial_join(pts.take(idx), polys, "intersects", mode=1, n_threads=0)
+    assert np.array_equal(got["counts"].astype(np.uint32), ec)
+    assert np.array_equal(got["pairs"].astype(np.int64), np.stack([idx[ep[:, 0].astype(np.int64)], ep[:, 1].astype(np.int64)], axis=1))
 
 
 def _roundtrip(comm, host):

@@ -380,6 +380,40 @@ def test_bench_helpers_sampling_and_traffic_records(tmp_path, monkeypatch):
     assert rec is not None and rec["traffic_bytes_raw"] == 5
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_of_the_join(tmp_path, monkeypatch):
+    """--dump-outputs: the hit counts at a fixed, seeded sample of rows, exactly the pairs of those rows (global row numbers), the
+    total, per-row outputs of another column at their own sample; float32 only where it is exact; never more than the byte budget"""
+    import importlib
+
+    import torch
+
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_ROWS", 40)
+    n, base = 100, 1000
+    counts = torch.from_numpy(np.arange(n, dtype=np.int32) % 3)
+    l = np.repeat(np.arange(n), counts.numpy()) + base
+    pairs = torch.from_numpy(np.stack([l, np.arange(len(l)) % 7], axis=1).astype(np.int32))
+    area = torch.from_numpy(np.linspace(0.1, 1.0, 60))
+    bench.dump_join(str(tmp_path / "a"), counts, pairs, len(l), base=base, per_row={"area": area})
+    bench.dump_join(str(tmp_path / "b"), counts, pairs, len(l), base=base, per_row={"area": area})
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"sample_rows", "counts", "pairs", "n_pairs", "area", "area_rows"}
+    for k, v in got.items():  # the same arguments: the same files
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / f"{k}.npy"))), k
+    rows = got["sample_rows"].astype(np.int64) - base
+    assert len(rows) == 40 and np.all(np.diff(rows) > 0) and got["counts"].dtype == np.float32
+    assert np.array_equal(got["counts"], counts.numpy()[rows])
+    want = pairs.numpy()[np.isin(pairs.numpy()[:, 0] - base, rows)]
+    assert got["pairs"].dtype == np.float32 and np.array_equal(got["pairs"], want)
+    assert got["n_pairs"].tolist() == [len(l)]
+    assert got["area"].dtype == np.float64 and np.array_equal(got["area"], area.numpy()[got["area_rows"].astype(np.int64)])
+    bench.dump_arrays(str(tmp_path / "c"), {"big": np.array([(1 << 25) + 1, 1], dtype=np.int64)})  # not exact in float32
+    assert np.load(str(tmp_path / "c" / "big.npy")).dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100)
+    with pytest.raises(SystemExit):
+        bench.dump_arrays(str(tmp_path / "d"), {"x": np.zeros(1000)})
+
+
 def test_bench_gpus_n_without_a_launcher_spawns_n_ranks():
     """`python bench.py --gpus 2` must not exit asking for a launcher: it re-runs itself as 2 ranks under torch.distributed.run.
     There is no GPU here, so each rank stops at "no GPU visible" — which shows that both were started."""

@@ -9,7 +9,7 @@ cd $R
 bash tools/profile_headline.sh $TAG
 bash tools/profile_configs.sh $TAG; cd $R   # traffic + instruction counts of the dominant kernels of C3 / C4 / C5 -> profiles/<tag>_pmc_traffic_configs.json
 for c in c2 c3 c4 c5; do
-  timeout 400 python bench.py --config $c > $O/${TAG}_bench_$c.log 2>&1; grep -h '"metric"' $O/${TAG}_bench_$c.log | cut -c1-300 || tail -5 $O/${TAG}_bench_$c.log
+  timeout 400 python bench.py --config $c --full > $O/${TAG}_bench_$c.log 2>&1; grep -h '"metric"' $O/${TAG}_bench_$c.log | cut -c1-300 || tail -5 $O/${TAG}_bench_$c.log
 done
 for c in c3 c4 c5; do
   bash tools/prof_stats.sh ${TAG}_$c python $R/bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline --parity-rows 20000
