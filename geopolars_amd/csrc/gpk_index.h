@@ -74,37 +74,19 @@ struct SubCell2 {
     uint32_t pad[4];
 };
 constexpr uint32_t SUB2_BIT = 1u << 29;         // in a CELL_TAG_SUB payload: the index refers to PipView::sub2
-// "test" sub-cells of a lean index (one part per cell), decided in the owning lane: for the padded sub-cell Q the LOCAL CHAIN is
-// the run of ring edges that covers every edge meeting Q, grown at both ends while the end vertex's y lies in Q's y-interval;
-// then winding(p) = base + sum of the chain edges' contributions for every p of Q (the rule is checked on
-// the CPU by tools/proto_local_chain.py / tests/test_local_chain_rule.py).  count == 0: no single short chain (several runs,
-// more than CHAIN_MAX edges, a part with holes): the row is decided by the generic walk, by the whole wave at the end of its tile.
-constexpr int CHAIN_MAX = 12;
-// chain entry i of an index = chain_head[i] (count, base, where vertices 4 .. are) + sub_aux[i] (the first four vertices, one cache
-// line): a `test` point reads both with independent requests and needs nothing else — 99.8 % of the chains of the C2 right side
-// have at most three edges.
-constexpr uint32_t CHAIN_COUNT_MASK = 0xFu;  // bits 0-3: edges in the chain, 1 .. CHAIN_MAX (0 = no chain entry: the generic walk decides)
-constexpr int CHAIN_BASE_SHIFT = 4;          // bits 4-11: summed winding contribution of every ring edge outside the chain (signed):
-                                             // constant over the padded sub-cell
-constexpr int CHAIN_EXT_SHIFT = 12;          // bits 12-31: count > 3: PipView::chain_ext[ext .. ext + count - 3) are vertices 4 .. count
-// GPK_HALF_CHAINS (round 4, the default): ONE chain per half-cell record instead of one per `test` sub-cell.  The chain is the arc of
-// the ring that covers every edge meeting the padded HALF CELL (grown at both ends while the end vertex's y lies in the half's
-// y-interval); the same argument gives winding(p) = base + sum over the chain for every p of the half cell, and an on-boundary
-// point lies on a chain edge.  The chain is named by a word IN the record (HalfCell::aux_base) — count, base, and where its
+// "test" sub-cells of a lean index (one part per cell), decided in the owning lane by a LOCAL CHAIN: ONE chain per half-cell
+// record, the arc of the ring that covers every edge meeting the padded HALF CELL (grown at both ends while the end vertex's y
+// lies in the half's y-interval); then winding(p) = base + sum of the chain edges' contributions for every p of the half cell, and
+// an on-boundary point lies on a chain edge (the rule is checked on the CPU by tools/proto_local_chain.py /
+// tests/test_local_chain_rule.py).  The chain is named by a word IN the record (HalfCell::aux_base) — count, base, and where its
 // vertices start in PipView::chain_xy, the right side's coordinates with CHAIN_MAX more per ring (a chain may run over the closing
 // vertex: vertex k of the extended ring is coordinate k % edges) — so a `test` point needs no head-word request and reads vertices of
-// a table as hot as the coordinates themselves (C2: 1.2 MB) instead of a cold 64-byte line of a per-sub-cell table (C2: 56 MB +
-// 3.5 MB of head words).  It walks about two edges where the per-sub-cell chain had 1.26.
-#ifndef GPK_HALF_CHAINS
-#define GPK_HALF_CHAINS 1
-#endif
+// a table as hot as the coordinates themselves (C2: 1.2 MB).  It walks about two edges.
+constexpr int CHAIN_MAX = 12;
 constexpr uint32_t HCHAIN_COUNT_MASK = 0xFu;  // bits 0-3: edges, 1 .. CHAIN_MAX (0: no chain — several runs, too long, a part with holes,
                                               // an unclosed ring: the generic walk decides the half's `test` points)
 constexpr int HCHAIN_BASE_SHIFT = 4;          // bits 4-7: the other edges' summed winding contribution, signed
 constexpr int HCHAIN_START_SHIFT = 8;         // bits 8-31: first vertex in PipView::chain_xy
-struct ChainAux {
-    double2 v[4];  // the chain's first four vertices, copied (a chain may run over the ring's closing vertex)
-};
 // An index with chains keeps its one-part level-2 records (PipView::sub, 32 bytes per raster cell) as TWO half-cell records: the
 // labels of four sub-cell rows, the part, and where the half's chain entries start — everything a point needs, in one 16-byte
 // request.  (The queue kernels read the SubCell form; an index has one or the other: pip_join_enqueue picks the kernel.)
@@ -114,8 +96,7 @@ struct HalfCell {
     uint32_t aux_base;    // chain entry of the half's first `test` label (label order)
 };
 static_assert(sizeof(HalfCell) * 2 == sizeof(SubCell), "two half-cell records overlay one SubCell");
-static_assert(sizeof(ChainAux) == 64, "one chain entry per cache line");
-static_assert(CHAIN_MAX <= (int)CHAIN_COUNT_MASK, "the edge count of a chain is a 4-bit field");
+static_assert(CHAIN_MAX <= (int)HCHAIN_COUNT_MASK, "the edge count of a chain is a 4-bit field");
 // Level-1 routing of a small raster (R <= PIP_ROUTE_RMAX) as an LDS image: one 16-byte word per 32 consecutive cells of a
 // raster row.  A persistent work-group keeps the whole image in LDS (128 KB at R = 512) and a point learns from ONE LDS
 // read whether its cell is empty (nothing to fetch), carries a one-part record (its index = rec0 + rank of the cell's bit:
@@ -134,10 +115,7 @@ struct PipView {
     const uint32_t* list;
     const SubCell* sub;              // level-2 records (cell tag 3)
     const SubCell2* sub2;            // two-part level-2 records (cell tag 3, payload & SUB2_BIT)
-    const ChainAux* sub_aux;         // lean indexes with chains (see ChainAux); else nullptr
-    const uint32_t* chain_head;      // count | base | ext per chain entry
-    const double2* chain_ext;        // vertices 4 .. of the chains longer than three edges
-    const double2* chain_xy;         // GPK_HALF_CHAINS: extended ring coordinates the half-cell chains index (then sub_aux / chain_head / chain_ext are null)
+    const double2* chain_xy;         // lean indexes with chains: extended ring coordinates the half-cell chains index; else nullptr
     const RouteWord* route;          // LDS image of the level-1 routing (chains + R <= PIP_ROUTE_RMAX); else nullptr
     const SubCell* lrec;             // level-2 records of the BOUNDARY entries of list cells: when set, such an entry is
                                      // `record index << 1 | 1` (the record names the part), else `part << 1 | 1`

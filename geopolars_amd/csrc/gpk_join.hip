@@ -150,40 +150,18 @@ __global__ void cell_sort_kernel(const int32_t* __restrict__ cell_off, int64_t n
 }
 
 // ================================= point-in-polygon join =========================================
-#ifndef GPK_PIP_PPT
-#define GPK_PIP_PPT 2  // points per lane of pip_tile_kernel on ordinary indexes; list-heavy ones (gpk_index::pip_list_heavy) run the
-                       // PPT = 1 instance: the flattened passes carry the memory-level parallelism there, and a 256-point tile keeps 84
-                       // registers and 19 KB of LDS per work-group (C5 1.41 -> 1.31 ms); a tessellation, which streams, loses 20 % with it
-#endif
-// GPK_ABLATE (tuning builds only, tools/pmc_ablate.sh, tools/ablate_time.py): 1 = no exact phase, 2 = every cell empty, 3 = level-1 interiors only,
-// 5 = level-2 labels without queue pushes, 6 = list cells skipped, 7 = list entries end after the box test, 8 = no hole rings.  0 in the shipped library.
-#ifndef GPK_ABLATE
-#define GPK_ABLATE 0
-#endif
-#ifndef GPK_PIP_GS
-#define GPK_PIP_GS 8
-#endif
-#ifndef GPK_PIP_BLOCK
-#define GPK_PIP_BLOCK 256
-#endif
-constexpr int PIP_BLOCK = GPK_PIP_BLOCK;       // threads per work-group of pip_tile
-#ifndef GPK_WR_BLOCK
-#define GPK_WR_BLOCK 256
-#endif
-constexpr int WR_BLOCK = GPK_WR_BLOCK;                  // threads per work-group of pip_write
-constexpr int PIP_PPT = GPK_PIP_PPT;           // points per thread, strided by PIP_BLOCK (coalesced 16-byte loads)
+constexpr int PIP_BLOCK = 256;                 // threads per work-group of pip_tile
+constexpr int WR_BLOCK = 256;                  // threads per work-group of pip_write
+// points per lane of pip_tile_kernel on ordinary indexes (strided by PIP_BLOCK: coalesced 16-byte loads); list-heavy ones
+// (gpk_index::pip_list_heavy) run the PPT = 1 instance: the flattened passes carry the memory-level parallelism there, and a
+// 256-point tile keeps 84 registers and 19 KB of LDS per work-group (C5 1.41 -> 1.31 ms); a tessellation, which streams, loses 20 % with it
+constexpr int PIP_PPT = 2;
 constexpr int PIP_TILE = PIP_BLOCK * PIP_PPT;  // points per work-group
-constexpr int PIP_GS = GPK_PIP_GS;             // lanes cooperating on one queued (point, part) pair
+constexpr int PIP_GS = 8;                      // lanes cooperating on one queued (point, part) pair
 constexpr int PIP_OVF = 256;                   // per-tile overflow list for points with more than PIP_KHIT hits
-#ifndef GPK_PIP_QCAP
-#define GPK_PIP_QCAP (GPK_PIP_BLOCK * GPK_PIP_PPT)
-#endif
-constexpr int PIP_QCAP = GPK_PIP_QCAP;             // LDS queue capacity (overflow is resolved inline, still exact)
+constexpr int PIP_QCAP = PIP_BLOCK * PIP_PPT;  // LDS queue capacity (overflow is resolved inline, still exact)
 constexpr int PIP_SUPER_SHIFT = 6;             // 64 tiles per super-tile (two-level prefix of the tile totals)
-#ifndef GPK_WR_WPT
-#define GPK_WR_WPT 8
-#endif
-constexpr int PIP_WPT = GPK_WR_WPT;            // writer: consecutive points per thread (a multiple of 4: 16-byte code loads)
+constexpr int PIP_WPT = 8;                     // writer: consecutive points per thread (a multiple of 4: 16-byte code loads)
 constexpr int PIP_WTILE = WR_BLOCK * PIP_WPT;  // writer: points per work-group (a multiple of PIP_TILE)
 constexpr int WR_CAP = PIP_WTILE;              // writer: pairs of one tile compacted in LDS (16 KB) before the coalesced copy-out
 static_assert(PIP_WTILE % PIP_TILE == 0, "a writer tile is a whole number of pip_tile tiles");
@@ -233,7 +211,7 @@ struct QEntry {  // 32 bytes: one queued (point, part) pair with its exterior sl
 //            offsets) and is pushed to an LDS queue with a wave-aggregated slot grab (ballot + one LDS atomic per wave).  Loads are
 //            issued in stages (all points, then all cells, then all records, ...) to keep PPT requests per lane in flight.
 //   entry lists (round 3): the lanes whose cell is a LIST register (point, list) jobs; the jobs' entries are then one flat work
-//            list — every lane takes a run of consecutive (point, entry) items, GPK_FLAT_B at a time with their gathers in flight
+//            list — every lane takes a run of consecutive (point, entry) items, FLAT_B at a time with their gathers in flight
 //            together (entry word + point, then the entry's record or its part's box), and pushes what survives.
 //   phase 2 (round 3: lane = slab EDGE): the queued pairs' slabs, flattened the same way; an edge's winding / on-boundary contribution
 //            goes to its pair's LDS accumulator (one atomicAdd of wn << 16 | on); a pair inside the exterior of a part with holes
@@ -242,15 +220,7 @@ struct QEntry {  // 32 bytes: one queued (point, part) pair with its exterior sl
 //   finalize: rows with exactly one part hit map part -> geometry; rows in several geometries (overlapping polygons / multipolygon
 //            parts) get a sorted segment of the multi-hit pool (its space reserved once per wave); only a tile that overflows its
 //            lists falls back to the generic walk.
-#ifndef GPK_PIP_MINWAVES
-#define GPK_PIP_MINWAVES 1
-#endif
-#ifndef GPK_PIP_NT
-#define GPK_PIP_NT 2  // bit 0: non-temporal point loads (measured slower), bit 1: non-temporal result stores
-#endif
-#ifndef GPK_FLAT_B
-#define GPK_FLAT_B 2  // entries / edges a lane of the flattened passes keeps in flight (4: 123 registers instead of 92, no faster)
-#endif
+constexpr int FLAT_B = 2;  // entries / edges a lane of the flattened passes keeps in flight (4: 123 registers instead of 92, no faster)
 #define PIP_SYNC() __syncthreads()
 // GPK_TILE_TRACE (diagnosis builds only; tools/c5_stage_clocks.py): thread 0 of every work-group adds the wall-clock ticks (100 MHz) it
 // spent in each stage of pip_tile_kernel — barrier waits included, so a stage's total is the work-groups' critical path through it — to
@@ -270,8 +240,8 @@ struct QEntry {  // 32 bytes: one queued (point, part) pair with its exterior sl
     } while (0)
 #endif
 // SUB2: the index holds two-part level-2 records (PipView::sub2); the variant without them stays as lean as it was
-template <bool RASTER, bool SUB2, int PPT = GPK_PIP_PPT>
-__global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(DevGeo pts, DevGeo polys, IndexView ix, PipView pv,
+template <bool RASTER, bool SUB2, int PPT = PIP_PPT>
+__global__ __launch_bounds__(PIP_BLOCK, 1) void pip_tile_kernel(DevGeo pts, DevGeo polys, IndexView ix, PipView pv,
                                                               uint32_t* __restrict__ counts,
                                                               uint32_t* __restrict__ code,
                                                               unsigned long long* __restrict__ block_tot,
@@ -325,7 +295,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
         for (int k = 0; k < PIP_PPT; ++k) {
             const uint32_t t = (uint32_t)(k * PIP_BLOCK + tid);  // scalar tile base + 32-bit lane offset
             const bool ok = t < rem && dev::valid_row(pts.validity, base + t);
-            p[k] = ok ? ((GPK_PIP_NT & 1) ? dev::load_stream(tile_xy + t) : tile_xy[t]) : make_double2(NAN, NAN);
+            p[k] = ok ? tile_xy[t] : make_double2(NAN, NAN);
         }
         // stage B: raster words (one 4-byte gather per point).  Columns/rows are computed at PIP_SUB x the
         // raster resolution (an exact power-of-two rescale of the same monotone function): `/ PIP_SUB` is the
@@ -350,8 +320,6 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
             fyf[k] = (uint32_t)dev::cell_of(p[k].y, pv.ry0, pv.inv_fh * FINE, pv.R * FINE);
             fy[k] = fyf[k] >> FY_SUB;
             word[k] = (p[k].x == p[k].x && p[k].y == p[k].y) ? pv.cell[(fy[k] / S) * (uint32_t)pv.R + (sx[k] / S)] : 0u;
-            if (GPK_ABLATE == 2) word[k] = 0u;  // tuning builds only
-            if (GPK_ABLATE == 3) word[k] = (word[k] >> 30) == CELL_TAG_SINGLE && !(word[k] & 1u) ? word[k] : 0u;
         }
         // stage C: decided cells; level-2 record gather (32 B) or PartInfo gather for inline boundary entries
         SubCell sc[PIP_PPT];
@@ -412,7 +380,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
                         const int li = k * PIP_BLOCK + tid;
                         s_cnt[li] = 1;
                         s_hit[li * PIP_KHIT] = qpart[k];
-                    } else if (lab == 2u && GPK_ABLATE != 5) {
+                    } else if (lab == 2u) {
                         slot_a();
                     }
                 } else {  // two parts share the cell (gpk_index.h: SubCell2)
@@ -495,7 +463,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
             // 151 us a work-group lived.  Now the lanes register (point, list) jobs, and every lane takes a run of consecutive entries
             // of the flattened job list, four at a time with their gathers in flight together.
             {
-                const bool has_list = (word[k] >> 30) == CELL_TAG_LIST && GPK_ABLATE != 6;
+                const bool has_list = (word[k] >> 30) == CELL_TAG_LIST;
                 const unsigned long long lm = __ballot(has_list);
                 if (lm) {  // (wave-uniform)
                     const uint32_t off = word[k] & 0x3FFFFFFFu;
@@ -533,7 +501,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
                         }
                         jb = lo;
                     }
-                    constexpr int B = GPK_FLAT_B;
+                    constexpr int B = FLAT_B;
                     for (uint32_t j = j0; j < j1; j += B) {
                         bool ok[B];
                         uint32_t jli[B], ew[B];
@@ -592,7 +560,6 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
                                 } else {
                                     // (closed box of the exterior, rounded outward: outside it = outside the part)
                                     if (pv.part_box && !(jx >= (double)bb[u].x && jx <= (double)bb[u].z && jy >= (double)bb[u].y && jy <= (double)bb[u].w)) continue;
-                                    if (GPK_ABLATE == 7) continue;  // tuning builds only
                                     const PartInfo pq = pv.part_info[part];
                                     if (!part_slab(pq, jfyf, a0, a1)) continue;
                                     holes = pq.n_rings > 1 ? 0x80000000u : 0u;
@@ -623,7 +590,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
             // such passes back to back, and that chain — not the arithmetic — was 1.1 ms of the 1.8 ms C5 join.  Here every lane takes a
             // run of consecutive edges of the flattened list, four at a time with all their gathers in flight together, and adds the
             // edge's winding / on-boundary contribution to its pair's LDS accumulator; one more pass decides the pairs.
-            const uint32_t nq = GPK_ABLATE == 1 ? 0u : (queued < (uint32_t)PIP_QCAP ? queued : (uint32_t)PIP_QCAP);
+            const uint32_t nq = queued < (uint32_t)PIP_QCAP ? queued : (uint32_t)PIP_QCAP;
             if (stats && tid == 0 && queued) atomicAdd(&stats[0], (unsigned long long)queued);  // measurement runs only
             if (nq) {  // (uniform)
                 uint32_t mine = 0, c_of[PIP_PPT];
@@ -663,7 +630,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
                         }
                         e = lo;
                     }
-                    constexpr int B = GPK_FLAT_B;
+                    constexpr int B = FLAT_B;
                     for (uint32_t j = j0; j < j1; j += B) {
                         uint32_t ee[B], at[B];
                         double2 pt[B];
@@ -716,7 +683,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
                     s_acc[e] = 0;
                     if ((packed & 0xFFFF) != 0 || (packed >> 16) == 0) continue;  // on the exterior ring, or outside it
                     const QEntry en = q[e];
-                    if ((en.li_flags >> 31) && GPK_ABLATE != 8) {  // the part has holes: inside one (or on it) = not inside the part
+                    if (en.li_flags >> 31) {  // the part has holes: inside one (or on it) = not inside the part
                         int r0, r1;
                         dev::part_rings(polys, (int)en.part, r0, r1);
                         const int row = pip::row_of(pv, en.py);
@@ -895,13 +862,8 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
             }
         }
         const uint32_t cd = cnt == 0 ? CODE_NONE : (cnt == 1 ? first : pool_code);
-        if (GPK_PIP_NT & 2) {
-            if (tile_counts) dev::store_stream(tile_counts + (uint32_t)li, cnt);
-            dev::store_stream(tile_code + (uint32_t)li, cd);
-        } else {
-            if (tile_counts) tile_counts[(uint32_t)li] = cnt;
-            tile_code[(uint32_t)li] = cd;
-        }
+        if (tile_counts) dev::store_stream(tile_counts + (uint32_t)li, cnt);  // non-temporal result stores
+        dev::store_stream(tile_code + (uint32_t)li, cd);
         wave_hits += (unsigned long long)__popcll(__ballot(cnt == 1));
         if (cnt >= 2) atomicAdd(&s_tot, (unsigned long long)cnt);
     }
@@ -922,17 +884,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_PIP_MINWAVES) void pip_tile_kernel(D
 // verdict comes back through its queue entry.  Versus pip_tile_kernel: no per-point LDS arrays (their initialisation, the
 // LDS atomics of phase 2, one of the three barriers per round), no list / overflow / multi-hit arms, PPT points per lane
 // in flight before the first dependent gather, one drain of the queue per tile.
-#ifndef GPK_LEAN_PPT
-#define GPK_LEAN_PPT 4
-#endif
-#ifndef GPK_LEAN_MINWAVES
-#define GPK_LEAN_MINWAVES 1
-#endif
-#ifndef GPK_LEAN_NT
-#define GPK_LEAN_NT 0  // 1: non-temporal point loads — a gain of 3 % while a queued pair carried its point in the entry; now the lane groups read the
-                       // point again from the tile, and that second read wants the line still in L2 (136.5 vs 138.7 us)
-#endif
-constexpr int LEAN_PPT = GPK_LEAN_PPT, LEAN_TILE = PIP_BLOCK * LEAN_PPT;  // (the queue holds a whole tile)
+constexpr int LEAN_PPT = 4, LEAN_TILE = PIP_BLOCK * LEAN_PPT;  // (the queue holds a whole tile)
 static_assert(PIP_WTILE % LEAN_TILE == 0, "a writer tile is a whole number of lean tiles");
 // GPK_TILE_TRACE (diagnosis builds only): lane 0 of every 64th tile stamps the wall clock at the stage boundaries of the lean
 // kernel (after forcing the stage's loads to land) into the statistics buffer; tools/tile_trace.py prints the stage times.
@@ -955,7 +907,7 @@ struct LeanEntry {
     uint32_t part;      // in: the part; out: the part when the point is inside it, CODE_NONE otherwise (slow path: the result code)
     uint32_t e0, cnt;   // in: the exterior slab's edge range; out (slow path): cnt = hits
 };
-__global__ __launch_bounds__(PIP_BLOCK, GPK_LEAN_MINWAVES) void pip_tile_lean_kernel(DevGeo pts, DevGeo polys, IndexView ix, PipView pv,
+__global__ __launch_bounds__(PIP_BLOCK, 1) void pip_tile_lean_kernel(DevGeo pts, DevGeo polys, IndexView ix, PipView pv,
                                                                                     uint32_t* __restrict__ counts, uint32_t* __restrict__ code,
                                                                                     unsigned long long* __restrict__ block_tot,
                                                                                     unsigned long long* __restrict__ super_tot,
@@ -978,7 +930,8 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_LEAN_MINWAVES) void pip_tile_lean_ke
     for (int k = 0; k < PPT; ++k) {
         const uint32_t t = (uint32_t)(k * PIP_BLOCK + tid);
         const bool ok = t < rem && dev::valid_row(pts.validity, base + t);
-        p[k] = ok ? (GPK_LEAN_NT ? dev::load_stream(tile_xy + t) : tile_xy[t]) : make_double2(NAN, NAN);
+        // (plain loads: the lane groups read the point again from the tile, and that second read wants the line still in L2)
+        p[k] = ok ? tile_xy[t] : make_double2(NAN, NAN);
     }
     if (tid == 0) {
         q_n = 0;
@@ -995,10 +948,6 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_LEAN_MINWAVES) void pip_tile_lean_ke
         fyf[k] = (uint32_t)dev::cell_of(p[k].y, pv.ry0, pv.inv_fh * FINE, pv.R * FINE);
         const uint32_t fy = fyf[k] >> FY_SUB;
         word[k] = (p[k].x == p[k].x && p[k].y == p[k].y) ? pv.cell[(fy / S) * (uint32_t)pv.R + (sx[k] / S)] : 0u;
-        // tuning builds only (tools/ablate_time.py; the answers are wrong on purpose)
-        if (GPK_ABLATE == 2) word[k] = 0u;                                                  // no gather at all: the streaming floor
-        if (GPK_ABLATE == 3) word[k] = (word[k] >> 30) == CELL_TAG_SINGLE ? word[k] : 0u;  // level-1 interiors only
-        if (GPK_ABLATE == 6) word[k] = (word[k] >> 30) == CELL_TAG_SUB ? ((CELL_TAG_SINGLE << 30) | (word[k] & 0x3FFFFFu)) : word[k];  // records never read
     }
     TILE_STAMP(2);
     // stage C: level-2 records of the cells an edge crosses (32 bytes: two 16-byte gathers off one line)
@@ -1039,7 +988,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_LEAN_MINWAVES) void pip_tile_lean_ke
                 const bool upper = ((fyf[k] >> PIP_FINE_LOG2) & 1u) != 0;
                 qe0[k] = upper ? ra[k].z : ra[k].y;
                 qcnt[k] = (upper ? ra[k].w : ra[k].z) - qe0[k];
-                todo[k] = qcnt[k] > 0 && GPK_ABLATE != 1;  // an empty slab: p.y is outside the exterior's y-range (ablation 1: no exact phase)
+                todo[k] = qcnt[k] > 0;  // an empty slab: p.y is outside the exterior's y-range
             }
         } else if (tag != CELL_TAG_EMPTY) {  // the few cells where parts meet (a lean index has next to none): generic walk
             qpart[k] = LEAN_SLOW;
@@ -1147,7 +1096,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_LEAN_MINWAVES) void pip_tile_lean_ke
 //   1. the point itself (coalesced 16-byte loads, non-temporal: read once);
 //   2. its raster cell's level-1 word: empty -> done; strictly inside a part -> the word names it; an edge crosses the cell -> the
 //      half-cell record of the point's sub-cell (ONE 16-byte request: 32 labels, the part, the half's chain word);
-//   3. the label: outside / inside -> done; `test` -> the half cell's chain (gpk_index.h: GPK_HALF_CHAINS);
+//   3. the label: outside / inside -> done; `test` -> the half cell's chain (gpk_index.h: HCHAIN_*);
 //   4. base + the contributions of the chain's edges; count + code + tile total (pip_write turns the codes into pairs).
 // Step 3 / 4 concern one point in twenty, scattered over the lanes: the wave packs those points into a list in its own slice of
 // LDS (no other wave sees it: wave-level ordering is enough) and lanes 0 .. T - 1 take one each — one round trip and one pass of
@@ -1161,16 +1110,7 @@ __global__ __launch_bounds__(PIP_BLOCK, GPK_LEAN_MINWAVES) void pip_tile_lean_ke
 // list cell, a `test` point whose half cell has no chain, a point whose orientation against a chain edge Shewchuk's stage-A bound
 // cannot certify: a handful per launch on real data — is settled at the end of the tile by the whole wave with the generic (always
 // exact) walk, its arguments read from device memory (ChainCold) at that point.
-#ifndef GPK_CHAIN_PPT
-#define GPK_CHAIN_PPT 4
-#endif
-#ifndef GPK_CHAIN_NT
-#define GPK_CHAIN_NT 1  // non-temporal point loads: a point is read exactly once by this kernel
-#endif
-#ifndef GPK_CHAIN_ABLATE
-#define GPK_CHAIN_ABLATE 0  // tuning builds only (answers wrong on purpose): 1 = `test` points count as outside
-#endif
-constexpr int CHAIN_PPT = GPK_CHAIN_PPT;
+constexpr int CHAIN_PPT = 4;
 static_assert(PIP_WTILE % (64 * CHAIN_PPT) == 0, "a writer tile is a whole number of chain tiles");
 
 // one small launch in place of the memset of a join's totals: zeroes them and writes the rare arm's arguments
@@ -1211,7 +1151,7 @@ __device__ __forceinline__ void chain_tile(const ChainHot& h, ChainItem* s_items
         constexpr int k = decltype(K)::value;
         double2 v = make_double2(NAN, NAN);
         if (FULL || ((uint32_t)(k * 64 + lane) < rem && dev::valid_row(h.pts_validity, base + k * 64 + lane)))
-            v = GPK_CHAIN_NT ? dev::load_stream(tile_xy + (k * 64 + lane)) : tile_xy[k * 64 + lane];
+            v = dev::load_stream(tile_xy + (k * 64 + lane));  // non-temporal: a point is read exactly once by this kernel
         px[k] = v.x;
         py[k] = v.y;
     });
@@ -1274,18 +1214,8 @@ __device__ __forceinline__ void chain_tile(const ChainHot& h, ChainItem* s_items
             const uint32_t lab = (lw >> sh) & 3u;
             if (lab >= 1u) res[k] = rec[k].z & 0x3FFFFFFFu;
             if (lab >= 2u) {
-#if GPK_HALF_CHAINS
                 aux_at = rec[k].w;  // the half's chain word
-#else
-                // rank of this `test` label among the half's: the lower label word (if the label sits in the upper one), then
-                // the fields below it in its own word
-                const uint32_t tl = (lw >> 1) & ~lw & 0x55555555u, tl0 = (rec[k].x >> 1) & ~rec[k].x & 0x55555555u;
-                aux_at = rec[k].w + (upper ? (uint32_t)__popc(tl0) : 0u) + (uint32_t)__popc(tl & ((1u << sh) - 1u));
-#endif
-                if (GPK_CHAIN_ABLATE == 1)
-                    res[k] = CODE_NONE;
-                else
-                    test = true;
+                test = true;
             }
         } else if (tag == CELL_TAG_SINGLE && !(payload & 1u)) {
             res[k] = payload >> 1;
@@ -1322,7 +1252,6 @@ __device__ __forceinline__ void chain_tile(const ChainHot& h, ChainItem* s_items
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if GPK_HALF_CHAINS
         const double2* __restrict__ const cxy = HOT_ARG(chain_xy);
         for (uint32_t i = (uint32_t)lane; i < n_items; i += 64u) {
             const uint32_t hd = s_items[i].aux_at;  // the half's chain word: count, base, first vertex
@@ -1357,40 +1286,6 @@ __device__ __forceinline__ void chain_tile(const ChainHot& h, ChainItem* s_items
                 inside = !on && wn != 0;
                 edges_walked += (unsigned long long)count;
             }
-#else
-        const ChainAux* __restrict__ const aux_all = HOT_ARG(sub_aux);
-        const uint32_t* __restrict__ const head_all = HOT_ARG(chain_head);
-        for (uint32_t i = (uint32_t)lane; i < n_items; i += 64u) {
-            const uint32_t at = GPK_CHAIN_ABLATE == 2 ? (s_items[i].aux_at & 0x3FFFu) : s_items[i].aux_at;  // (2, tuning builds only: chain entries from a 1 MB corner of the table)
-            const ChainAux* __restrict__ e = aux_all + at;
-            double2 q = make_double2(s_items[i].px, s_items[i].py);
-            uint32_t hd = head_all[at];
-            double2 a0 = e->v[0], a1 = e->v[1], a2 = e->v[2], a3 = e->v[3];
-            // (all five requests go out before the head is looked at: the compiler would otherwise sink the vertex requests
-            // under `count > 0` — a second round trip)
-            asm volatile("" : "+v"(hd), "+v"(a0.x), "+v"(a0.y), "+v"(a1.x), "+v"(a1.y), "+v"(a2.x), "+v"(a2.y), "+v"(a3.x), "+v"(a3.y));
-            const double qx = q.x, qy = q.y;
-            const int count = (int)(hd & CHAIN_COUNT_MASK);
-            bool inside = false, defer = count == 0;  // no chain entry for this sub-cell: the generic walk decides
-            if (count > 0) {
-                int wn = (int)(int8_t)((hd >> CHAIN_BASE_SHIFT) & 0xFFu);
-                bool on = dev::ring_edge_filtered(a0.x, a0.y, a1.x, a1.y, qx, qy, wn, defer);
-                if (count >= 2) on |= dev::ring_edge_filtered(a1.x, a1.y, a2.x, a2.y, qx, qy, wn, defer);
-                if (count >= 3) on |= dev::ring_edge_filtered(a2.x, a2.y, a3.x, a3.y, qx, qy, wn, defer);
-                if (count > 3) {  // 0.2 % of the chains: the further vertices follow in chain_ext
-                    const double2* __restrict__ ev = HOT_ARG(chain_ext) + (hd >> CHAIN_EXT_SHIFT);
-                    double ax = a3.x, ay = a3.y;
-                    for (int j = 3; j < count; ++j) {
-                        const double2 b = ev[j - 3];
-                        on |= dev::ring_edge_filtered(ax, ay, b.x, b.y, qx, qy, wn, defer);
-                        ax = b.x;
-                        ay = b.y;
-                    }
-                }
-                inside = !on && wn != 0;
-                edges_walked += (unsigned long long)count;
-            }
-#endif
             s_items[i].aux_at = (inside && !defer ? 1u : 0u) | (defer ? 2u : 0u);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1760,10 +1655,7 @@ __global__ __launch_bounds__(256) void cand_compact_kernel(DevGeo left, DevGeo r
 
 // Stage 2: exact refine, JOIN_GS lanes per candidate pair (pairs are independent: the unit of parallelism is the
 // pair, not the row, so ragged candidate lists do not unbalance waves).
-#ifndef GPK_JOIN_GS
-#define GPK_JOIN_GS 16
-#endif
-constexpr int JOIN_GS = GPK_JOIN_GS;
+constexpr int JOIN_GS = 16;
 __device__ __forceinline__ int64_t row_of_candidate(const int32_t* __restrict__ off, int64_t n_rows, int64_t c) {
     int64_t lo = 0, hi = n_rows;  // largest row with off[row] <= c
     while (hi - lo > 1) {
@@ -1775,15 +1667,9 @@ __device__ __forceinline__ int64_t row_of_candidate(const int32_t* __restrict__ 
     }
     return lo;
 }
-// (GPK_REFINE_MINWAVES=4 — 128 registers instead of 141, four waves per SIMD instead of three — was 4 % faster, 4.06 -> 3.90 ms, and wrote
-// 1.1 GB of spilled registers per launch to scratch memory, WRITE_SIZE 9.7 MB -> 1.14 GB: not taken)
-#ifndef GPK_REFINE_KEEP_A
-#define GPK_REFINE_KEEP_A 1
-#endif
-#ifndef GPK_REFINE_MINWAVES
-#define GPK_REFINE_MINWAVES 1
-#endif
-__global__ __launch_bounds__(256, GPK_REFINE_MINWAVES) void pair_refine_kernel(DevGeo left, DevGeo right, const uint32_t* __restrict__ cand_l,
+// (a minimum of four waves per SIMD — 128 registers instead of 141 — was 4 % faster, 4.06 -> 3.90 ms, and wrote 1.1 GB of spilled
+// registers per launch to scratch memory, WRITE_SIZE 9.7 MB -> 1.14 GB: not taken)
+__global__ __launch_bounds__(256, 1) void pair_refine_kernel(DevGeo left, DevGeo right, const uint32_t* __restrict__ cand_l,
                                                            const uint32_t* __restrict__ cand_r, int64_t n_cand,
                                                            const double4* __restrict__ lbbox, const double4* __restrict__ rbbox,
                                                            uint8_t* __restrict__ hit, bool l_one_ring, bool r_one_ring) {
@@ -1824,7 +1710,7 @@ __global__ __launch_bounds__(256, GPK_REFINE_MINWAVES) void pair_refine_kernel(D
             }
         }
         if (small) {
-            h = polygon_pair_small<JOIN_GS>(left.xy + ca, na, right.xy + cb, nb, lbbox[i], rbbox[j], lane, slice, GPK_REFINE_KEEP_A && staged_i == i);
+            h = polygon_pair_small<JOIN_GS>(left.xy + ca, na, right.xy + cb, nb, lbbox[i], rbbox[j], lane, slice, staged_i == i);
             staged_i = i;
         } else {
             h = polygonal_intersects_polygonal_group<JOIN_GS>(left, i, right, j, lane, reinterpret_cast<double4*>(slice), lbbox, rbbox);
@@ -1946,8 +1832,7 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
     if (host_out && want_pairs) need += align256(pairs_bytes);
     // (padded staging of the candidates: up to 512 MB — 8M left rows; beyond that the two-search path)
     const size_t stage_bytes = sizeof(uint32_t) * CAND_STAGE * (size_t)(n > 0 ? n : 1);
-    static const bool no_stage = getenv("GPK_NO_CAND_STAGE") != nullptr;  // A/B runs
-    const bool staged = !no_stage && stage_bytes <= (size_t(512) << 20);
+    const bool staged = stage_bytes <= (size_t(512) << 20);
     if (staged) need += align256(stage_bytes);
     rc = workspace().begin(need);
     if (rc != GPK_OK) return done(rc);
@@ -2173,11 +2058,7 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
                                 unsigned long long* total_out, hipStream_t s, uint32_t** counts_dev_out, uint32_t** pairs_dev_out,
                                 unsigned long long** grand_out) {
     const int64_t n = left->d.n_geoms;
-    static const bool no_lean = [] {  // GPK_NO_LEAN=1: A/B runs of the general tile kernel on a lean-eligible index
-        const char* e = getenv("GPK_NO_LEAN");
-        return e && *e && *e != '0';
-    }();
-    const bool lean = right_index->pip.R > 0 && right_index->pip_lean && !no_lean;
+    const bool lean = right_index->pip.R > 0 && right_index->pip_lean;
     // an index with chains (gpk_index.h) is served by the chain kernel or — with an LDS routing image — by the one-launch join of
     // gpk_pipflow.hip: its records carry chain words where the queue kernels expect slab ranges.
     // GPK_TILE_KERNEL=chain: A/B runs of the chain kernel + writer on an index that has the image
@@ -2189,11 +2070,11 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
     // same column — SpatialIndex(series) next to the series itself — stays valid after that upload is gone)
     PipView pvj = right_index->pip;
     pvj.slab_xy = right->d.xy;
-    const bool chain = right_index->pip.R > 0 && (GPK_HALF_CHAINS ? right_index->pip.chain_xy != nullptr : right_index->pip.sub_aux != nullptr);
+    const bool chain = right_index->pip.R > 0 && right_index->pip.chain_xy != nullptr;
     const bool one_per_lane = !chain && !lean && right_index->pip.R > 0 && right_index->pip_list_heavy;  // (pip_tile_kernel<., ., 1>)
     // `flow` (gpk_pipflow.hip, round 6): ONE launch — optimistic hits in a global pool, dense exact passes, dense emission, tiles of
     // 64 .. 512 rows by the column's length — for every chain index with a routing image, up to 4 M geometries and 201 M left rows
-    const int flow_p = GPK_HALF_CHAINS && chain && !no_flow && right_index->pip.route != nullptr && right_index->pip.R <= PIP_ROUTE_RMAX
+    const int flow_p = chain && !no_flow && right_index->pip.route != nullptr && right_index->pip.R <= PIP_ROUTE_RMAX
                            ? pip_flow_points_per_lane(n, right->d.n_geoms, right_index->pip.R, cu_count())
                            : 0;
     const bool flow = flow_p > 0;
@@ -2284,9 +2165,6 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
         hot.inv_fh = pv.inv_fh;
         hot.cell = pv.cell;
         hot.half = reinterpret_cast<const HalfCell*>(pv.sub);  // (an index with chains keeps its one-part records in half-cell form)
-        hot.sub_aux = pv.sub_aux;
-        hot.chain_head = pv.chain_head;
-        hot.chain_ext = pv.chain_ext;
         hot.chain_xy = pv.chain_xy;
         hot.part_geom = pv.part_geom;
         hot.route = pv.route;
@@ -2551,7 +2429,7 @@ int32_t gpk_index_describe(const gpk_index* idx, int64_t out[8]) {
     for (int i = 0; i < 8; ++i) out[i] = 0;
     out[0] = idx->pip.R;
     out[1] = idx->pip_lean;
-    out[2] = GPK_HALF_CHAINS ? idx->pip.chain_xy != nullptr : idx->pip.sub_aux != nullptr;
+    out[2] = idx->pip.chain_xy != nullptr;
     out[3] = idx->pip.route != nullptr;
     out[4] = idx->pip_list_heavy;
     return GPK_OK;

@@ -28,35 +28,9 @@ namespace gpk {
 // short ones — a shard of a column spread over several GPUs — so that every wave of the chip still gets a tile or two and a tile's
 // chain of dependent round trips is short (pip_flow_points_per_lane)
 constexpr int FLOW_P_MAX = 8;
-#ifndef GPK_FLOW_BLOCK
-#define GPK_FLOW_BLOCK 1024
-#endif
-constexpr int FLOW_BLOCK = GPK_FLOW_BLOCK, FLOW_W = FLOW_BLOCK / 64;
+constexpr int FLOW_BLOCK = 1024, FLOW_W = FLOW_BLOCK / 64;
 constexpr int FLOW_ITEMS = 128;                // list slots per wave
-#ifndef GPK_FLOW_PASS_AT
-#define GPK_FLOW_PASS_AT 40
-#endif
-#ifndef GPK_FLOW_PREFETCH
-#define GPK_FLOW_PREFETCH 0  // 1: a guard-free tile's points are requested by the tile before it, row by row as that tile's rows are done with
-                             // their registers.  Measured 10 us SLOWER on C2 (99.7 against 90.1 us): see DESIGN.md 4.1, round 6
-#endif
-#ifndef GPK_FLOW_POOL_NT
-#define GPK_FLOW_POOL_NT 0  // (1: measured 2 us slower)
-#endif
-#ifndef GPK_FLOW_VERTEX_MASK
-#define GPK_FLOW_VERTEX_MASK 0  // (1: vertices 3 .. 5 requested only by chains that have them — no change on C2: 91.3 against 90.6 us)
-#endif
-#ifndef GPK_FLOW_FLAT_EDGES
-#define GPK_FLOW_FLAT_EDGES 1
-#endif
-#ifndef GPK_FLOW_ABLATE
-#define GPK_FLOW_ABLATE 0  // tuning builds only (answers wrong on purpose): 1 no record / level-1 requests, 2 no exact passes, 3 no count stores,
-                           // 4 no pool stores / emission reads nothing, 5 = 1 + 2 + 3 + 4 (points in, nothing decided)
-#endif
-#ifndef GPK_FLOW_ROUTE_BATCH
-#define GPK_FLOW_ROUTE_BATCH 1
-#endif
-constexpr int FLOW_PASS_AT = GPK_FLOW_PASS_AT;  // a list this long is walked before the next tile is decided
+constexpr int FLOW_PASS_AT = 40;               // a list this long is walked before the next tile is decided
 constexpr int FLOW_MAX_TILES = 1536;           // tile records per work-group (201 M rows on 256 CUs at P = 8)
 constexpr int FLOW_ID_BITS = 22;               // geometry ids (and the hit count of a row in several geometries) in an entry
 constexpr uint32_t FLOW_DEAD = 0xFFFFFFFFu;    // entry of a `test` point that failed
@@ -147,8 +121,8 @@ __device__ __forceinline__ void ring_edge_flat(double sx, double sy, double ex, 
 __device__ __forceinline__ void flow_settle(const ChainHot& h, uint32_t* s_ttot, uint32_t t, uint32_t slot, uint32_t row, uint32_t li, uint32_t cnt,
                                             uint32_t first) {
     if (cnt == 0u) {
-        if (GPK_FLOW_ABLATE != 8 && GPK_FLOW_ABLATE != 9) h.pool[slot] = FLOW_DEAD;
-        if (h.counts && GPK_FLOW_ABLATE != 8 && GPK_FLOW_ABLATE != 10) h.counts[row] = 0u;
+        h.pool[slot] = FLOW_DEAD;
+        if (h.counts) h.counts[row] = 0u;
         atomicSub(&s_ttot[t], 1u);
     } else if (cnt == 1u) {
         h.pool[slot] = (first << 9) | li;
@@ -179,33 +153,15 @@ __device__ __forceinline__ void flow_exact_pass(const ChainHot& h, FlowItem* ite
     }
     const int count = (int)(hd & HCHAIN_COUNT_MASK);
     const double2* __restrict__ v = H_COLD(chain_xy) + (hd >> HCHAIN_START_SHIFT);
-#if GPK_FLOW_VERTEX_MASK
-    // (every lane-load is a request to the L2 whatever line it names — the L1 does not merge the five: a chain of one or two edges (76 % of the
-    // C2 half cells) asks for three vertices, not five)
-    double2 a0 = v[0], a1 = v[count < 1 ? count : 1], a2 = a1, a3, a4;
-    if (count >= 2) a2 = v[2];
-    a3 = a2;
-    if (count >= 3) a3 = v[3];
-    a4 = a3;
-    if (count >= 4) a4 = v[4];
-#else
     const int i1 = count < 1 ? count : 1, i2 = count < 2 ? count : 2, i3 = count < 3 ? count : 3, i4 = count < 4 ? count : 4;
     double2 a0 = v[0], a1 = v[i1], a2 = v[i2], a3 = v[i3], a4 = v[i4];
-#endif
     asm volatile("" : "+v"(a0.x), "+v"(a0.y), "+v"(a1.x), "+v"(a1.y), "+v"(a2.x), "+v"(a2.y), "+v"(a3.x), "+v"(a3.y), "+v"(a4.x), "+v"(a4.y));
     int wn = ((int)(hd << (28 - HCHAIN_BASE_SHIFT))) >> 28;  // the signed 4-bit base
     bool unsure = false, on = false;
-#if GPK_FLOW_FLAT_EDGES
     ring_edge_flat(a0.x, a0.y, a1.x, a1.y, qx, qy, wn, on, unsure);
     ring_edge_flat(a1.x, a1.y, a2.x, a2.y, qx, qy, wn, on, unsure);
     ring_edge_flat(a2.x, a2.y, a3.x, a3.y, qx, qy, wn, on, unsure);
     ring_edge_flat(a3.x, a3.y, a4.x, a4.y, qx, qy, wn, on, unsure);
-#else
-    on |= dev::ring_edge_filtered(a0.x, a0.y, a1.x, a1.y, qx, qy, wn, unsure);
-    on |= dev::ring_edge_filtered(a1.x, a1.y, a2.x, a2.y, qx, qy, wn, unsure);
-    on |= dev::ring_edge_filtered(a2.x, a2.y, a3.x, a3.y, qx, qy, wn, unsure);
-    on |= dev::ring_edge_filtered(a3.x, a3.y, a4.x, a4.y, qx, qy, wn, unsure);
-#endif
     if (count > 4) {
         double ax = a4.x, ay = a4.y;
         for (int j = 4; j < count; ++j) {
@@ -296,8 +252,7 @@ static __device__ __noinline__ void flow_settle_pending(const double2* pts_xy, c
 // should not hold: chain word 0, the whole wave walks it).  flow_exact_pass takes listed rows back.
 template <bool SIMPLE, bool FULL, int P>
 __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask, const uint32_t* s_rec0, FlowItem* items, uint32_t& n_list, uint32_t t,
-                                          uint32_t tile0, int lane, uint32_t* s_tcand, uint32_t* s_ttot, double (&px)[P], double (&py)[P],
-                                          const double2* next_xy FLOW_PHASE_ARGS) {
+                                          uint32_t tile0, int lane, uint32_t* s_tcand, uint32_t* s_ttot FLOW_PHASE_ARGS) {
     constexpr int S = PIP_SUB, FLOW_TILE = 64 * P, TS = P == 8 ? 9 : (P == 4 ? 8 : (P == 2 ? 7 : 6));
     static_assert(P == 1 || P == 2 || P == 4 || P == 8, "tile sizes");
     static_assert(S == 8, "the sub-cell arithmetic below is written for 8 x 8 sub-cells");
@@ -307,11 +262,9 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
     const int64_t base = (int64_t)tile * FLOW_TILE;
     const int64_t n_points = FULL ? 0 : H_COLD(n_points);
     const uint32_t rem = FULL ? (uint32_t)FLOW_TILE : (uint32_t)(n_points - base < (int64_t)FLOW_TILE ? n_points - base : (int64_t)FLOW_TILE);
-    // 1. the points.  FULL: px / py hold them already — the tile before requested them row by row as its own rows were done with their
-    // registers, so a wave's next 8 KB are on their way from HBM while it works (with one tile's loads per wave in flight only while
-    // that wave waits for them, a CU kept ~30 KB in flight where 6.3 TB/s x 2 us needs 49) — and receive the NEXT tile's below.
-    // Guarded tiles (the last of a column, columns with nulls): loaded here, NaN for rows past the end and null rows (they route to nothing)
-    if (!FULL || !GPK_FLOW_PREFETCH) {
+    // 1. the points; guarded tiles (the last of a column, columns with nulls): NaN for rows past the end and null rows (they route to nothing)
+    double px[P], py[P];
+    {
         const double2* __restrict__ tile_xy = h.pts_xy + base;
         static_for<P>([&](auto K) {
             constexpr int k = decltype(K)::value;
@@ -329,7 +282,6 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
     uint32_t sidx4[(P + 3) / 4], gw[P];
     u32x4 rec[P];
     static_for<(P + 3) / 4>([&](auto J) { sidx4[decltype(J)::value] = 0u; });
-#if GPK_FLOW_ROUTE_BATCH
     // (all sixteen image reads first, then all requests: one LDS round trip a tile instead of eight one after the other)
     uint32_t sxs[P], sys_[P], r0s[P];
     uint2 ms[P];
@@ -349,8 +301,8 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
         constexpr int k = decltype(K)::value;
         const uint32_t sx = sxs[k], sy = sys_[k], bit = (sx >> 3) & 31u;
         const bool real = !__builtin_isunordered(px[k], py[k]);
-        const bool has = real && ((ms[k].x >> bit) & 1u) != 0u && GPK_FLOW_ABLATE != 1 && (GPK_FLOW_ABLATE < 5 || GPK_FLOW_ABLATE > 7);
-        const bool want = real && !has && ((ms[k].y >> bit) & 1u) != 0u && GPK_FLOW_ABLATE != 1 && (GPK_FLOW_ABLATE < 5 || GPK_FLOW_ABLATE > 7);
+        const bool has = real && ((ms[k].x >> bit) & 1u) != 0u;
+        const bool want = real && !has && ((ms[k].y >> bit) & 1u) != 0u;
         sidx4[k / 4] |= (((sy & 3u) << 3) | (sx & 7u)) << (8 * (k % 4));
         rec[k] = u32x4{0u, 0u, 0u, 0u};
         gw[k] = 0u;
@@ -361,29 +313,6 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
         if (want) gw[k] = h.cell[((sy >> 3) << logR) + (sx >> 3)];
     });
     GPK_SCHED_FENCE();
-#else
-    static_for<P>([&](auto K) {
-        constexpr int k = decltype(K)::value;
-        uint32_t sx = cvt_u32_sat((px[k] - h.rx0) * h.inv_fw_s), sy = cvt_u32_sat((py[k] - h.ry0) * h.inv_fh_s);
-        sx = sx < sub_max ? sx : sub_max;
-        sy = sy < sub_max ? sy : sub_max;
-        const bool real = !__builtin_isunordered(px[k], py[k]);
-        const uint32_t cy = sy >> 3, at = (cy << (logR - 5)) + (sx >> 8), bit = (sx >> 3) & 31u;
-        const uint2 m = s_mask[at];
-        const uint32_t r0 = s_rec0[at];
-        const bool has = real && ((m.x >> bit) & 1u) != 0u;
-        const bool want = real && !has && ((m.y >> bit) & 1u) != 0u;
-        sidx4[k / 4] |= (((sy & 3u) << 3) | (sx & 7u)) << (8 * (k % 4));
-        rec[k] = u32x4{0u, 0u, 0u, 0u};
-        gw[k] = 0u;
-        if (has) {
-            const uint32_t w = r0 + (uint32_t)__popc(__builtin_amdgcn_ubfe(m.x, 0u, bit));
-            rec[k] = *reinterpret_cast<const u32x4*>(h.half + (2u * w + ((sy >> 2) & 1u)));
-        }
-        if (want) gw[k] = h.cell[(cy << logR) + (sx >> 3)];
-        GPK_SCHED_FENCE();
-    });
-#endif
     FLOW_PHASE(2);  // routed, records here
     // 3. labels -> hits, ranked row by row; entries, counts and the list's new points leave as they are known
     uint32_t run = 0u, n_new = 0u;  // (wave-uniform) entries so far; points pushed
@@ -408,10 +337,9 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
             }
         }
         if (walk) r = 0u;  // (any geometry: the walk names the real one)
-        if (GPK_FLOW_ABLATE == 6 || GPK_FLOW_ABLATE == 7) r = px[k] > 650.0 ? 7u : CODE_NONE;  // (6, 7: the skeleton — points in, 35 % "hits" out, nothing looked up)
         const bool mine = FULL || li < rem;
         const bool cand = mine && r != CODE_NONE;
-        bool listed = cand && (lab >= 2u || walk) && GPK_FLOW_ABLATE != 2 && GPK_FLOW_ABLATE != 5;
+        bool listed = cand && (lab >= 2u || walk);
         const unsigned long long mcand = __ballot(cand);
         const uint32_t rank = run + lanes_below(mcand);
         uint32_t e = (r << 9) | li;
@@ -434,21 +362,9 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
             }
             n_new += (uint32_t)__popcll(ml);
         }
-        if (tile_counts && mine && GPK_FLOW_ABLATE != 3 && GPK_FLOW_ABLATE != 5) dev::store_stream(tile_counts + li, cand ? 1u : 0u);
-        if (cand && GPK_FLOW_ABLATE != 4 && GPK_FLOW_ABLATE != 5 && GPK_FLOW_ABLATE != 7) {
-            if (GPK_FLOW_POOL_NT)
-                __builtin_nontemporal_store(e, tile_pool + rank);
-            else
-                tile_pool[rank] = e;
-        }
+        if (tile_counts && mine) dev::store_stream(tile_counts + li, cand ? 1u : 0u);
+        if (cand) tile_pool[rank] = e;
         run += (uint32_t)__popcll(mcand);
-        if (FULL && GPK_FLOW_PREFETCH) {
-            if (next_xy) {  // (wave-uniform) this row's registers are free: the next tile's row k
-                const double2 v = dev::load_stream(next_xy + (k * 64 + lane));
-                px[k] = v.x;
-                py[k] = v.y;
-            }
-        }
         GPK_SCHED_FENCE();
     });
     if (lane == 0) {
@@ -541,7 +457,6 @@ __global__ __launch_bounds__(FLOW_BLOCK) void pip_tile_flow_kernel(ChainHot h, F
     unsigned long long g_phase[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, g_last = wall_clock64();
 #endif
 #endif
-    double px[P], py[P];
     // (the draw: EVERY lane adds 1 — the counter runs in units of 64 — and the wave barrier keeps the iterations apart: see DESIGN.md 4.1,
     // "two things the compiler did")
     auto draw = [&](uint32_t* counter) -> uint32_t {
@@ -551,23 +466,13 @@ __global__ __launch_bounds__(FLOW_BLOCK) void pip_tile_flow_kernel(ChainHot h, F
     };
     {
         uint32_t t = draw(&s_next);
-        if (GPK_FLOW_PREFETCH && t < nf) {
-            const double2* __restrict__ xy = h.pts_xy + ((size_t)(T0 + t) << TS);
-            static_for<P>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                const double2 v = dev::load_stream(xy + (k * 64 + lane));
-                px[k] = v.x;
-                py[k] = v.y;
-            });
-        }
         while (t < nf) {
             const uint32_t tn = draw(&s_next);  // (the tile after this one)
             FLOW_PHASE(4);  // drawn
             // (a list long enough for a dense pass is walked first)
             if (n_list >= (uint32_t)FLOW_PASS_AT) flow_exact_pass<TS>(h, s_items[wave], n_list, lane, s_ttot, T0);
             FLOW_PHASE(0);  // list walked
-            flow_tile<SIMPLE, true, P>(h, s_mask, s_rec0, s_items[wave], n_list, t, T0, lane, s_tcand, s_ttot, px, py,
-                                       tn < nf ? h.pts_xy + ((size_t)(T0 + tn) << TS) : nullptr FLOW_PHASE_PASS);
+            flow_tile<SIMPLE, true, P>(h, s_mask, s_rec0, s_items[wave], n_list, t, T0, lane, s_tcand, s_ttot FLOW_PHASE_PASS);
             t = tn;
 #if defined(GPK_TILE_TRACE) && GPK_TILE_TRACE != 2
             if (n_mine < 6) FLOW_STAMP(3 + n_mine);
@@ -579,7 +484,7 @@ __global__ __launch_bounds__(FLOW_BLOCK) void pip_tile_flow_kernel(ChainHot h, F
         const uint32_t t = draw(&s_next2) + nf;
         if (t >= nt) break;
         if (n_list >= (uint32_t)FLOW_PASS_AT) flow_exact_pass<TS>(h, s_items[wave], n_list, lane, s_ttot, T0);
-        flow_tile<SIMPLE, false, P>(h, s_mask, s_rec0, s_items[wave], n_list, t, T0, lane, s_tcand, s_ttot, px, py, nullptr FLOW_PHASE_PASS);
+        flow_tile<SIMPLE, false, P>(h, s_mask, s_rec0, s_items[wave], n_list, t, T0, lane, s_tcand, s_ttot FLOW_PHASE_PASS);
     }
     while (n_list) flow_exact_pass<TS>(h, s_items[wave], n_list, lane, s_ttot, T0);  // what is left on the list
 #if defined(GPK_TILE_TRACE) && GPK_TILE_TRACE == 2
@@ -599,7 +504,7 @@ __global__ __launch_bounds__(FLOW_BLOCK) void pip_tile_flow_kernel(ChainHot h, F
         static_for<EM_T>([&](auto Rr) {
             constexpr int r = decltype(Rr)::value;
             const uint32_t et = first + (uint32_t)(r * W);
-            cand[r] = et < nt && want_pairs && GPK_FLOW_ABLATE != 4 && GPK_FLOW_ABLATE != 5 && GPK_FLOW_ABLATE != 7 ? s_tcand[et] : 0u;
+            cand[r] = et < nt && want_pairs ? s_tcand[et] : 0u;
             cand[r] = __builtin_amdgcn_readfirstlane(cand[r]);
             const uint32_t* seg = h.pool + ((size_t)(T0 + et) << TS);
             static_for<EM_C>([&](auto Cc) {

@@ -115,18 +115,6 @@ __global__ void ring_rows_kernel(const double4* __restrict__ ring_bbox, int64_t 
     nrows[r] = j1 - j0 + 1;
 }
 
-// ring that owns coordinate i: largest r with ring_off[r] <= i
-__device__ __forceinline__ int ring_of_coord(const int32_t* __restrict__ ring_off, int n_rings, int i) {
-    int lo = 0, hi = n_rings;  // invariant: ring_off[lo] <= i < ring_off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ring_off[mid] <= i)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 // edge starting at coordinate i (a single-coordinate ring contributes one degenerate edge so that the
 // "ring of one coordinate" arm of coord_pos_relative_to_ring is reproduced by the edge walk)
 // coord_ring: the ring of every coordinate, one load (ring_start_kernel + a scan, built once per index build) — the per-edge
@@ -149,7 +137,7 @@ __device__ __forceinline__ bool edge_at(const DevGeo& a, const int32_t* __restri
 }
 
 // flag[ring_off[r]] += 1 for every ring r >= 1 that starts below n_coords: the inclusive prefix sum at coordinate i is then the
-// largest r with ring_off[r] <= i (ring_of_coord's answer, empty rings included) — the build scans it in place
+// largest r with ring_off[r] <= i (empty rings included) — the build scans it in place
 __global__ void ring_start_kernel(const int32_t* __restrict__ ring_off, int64_t n_rings, int64_t n_coords, int32_t* __restrict__ flag) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < 1 || r >= n_rings) return;
@@ -161,7 +149,7 @@ template <bool FILL>
 __global__ void slab_register_kernel(DevGeo a, const int32_t* __restrict__ coord_ring, FineGrid f, const int32_t* __restrict__ row0,
                                      const int32_t* __restrict__ slab_base, int32_t* __restrict__ cnt_or_cursor,
                                      double4* __restrict__ edges, int32_t* __restrict__ vidx = nullptr) {
-    // vidx (optional, FILL only): the coordinate index every slab entry's edge starts at (chain_aux_kernel; PipView::slab_vidx when the
+    // vidx (optional, FILL only): the coordinate index every slab entry's edge starts at (half_chain_kernel; PipView::slab_vidx when the
     // index keeps no edge copies: `edges` is nullptr then)
     //
     // One atomic per RUN of lanes that register in the same slab, not one per edge: consecutive edges of a ring mostly lie in one
@@ -721,193 +709,8 @@ __global__ void lrec_count_kernel(const uint32_t* __restrict__ cell, const uint3
     }
     cnt[c] = n;
 }
-// ---- local chains of the `test` sub-cells of a lean index (gpk_index.h: ChainAux) ------------------------------------------
+// ---- half-cell chains of a lean index (gpk_index.h: HCHAIN_*) -------------------------------------------------------------
 __device__ __forceinline__ int test_labels_of(uint32_t w) { return __popc((w >> 1) & ~w & 0x55555555u); }  // 2-bit fields equal to 2
-__global__ void chain_count_kernel(const SubCell* __restrict__ sub, int64_t n_sub, int32_t* __restrict__ cnt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_sub) return;
-    const SubCell rc = sub[i];
-    cnt[i] = test_labels_of(rc.labels[0]) + test_labels_of(rc.labels[1]) + test_labels_of(rc.labels[2]) + test_labels_of(rc.labels[3]);
-}
-// One wave per record (work item = (cell, part) of sub_work_kernel), lane = sub-cell.  The wave lists the edges of the part's
-// slab rows in this raster row that meet the padded cell (with the coordinate index each starts at), every `test` lane then
-//   1. takes the listed edges that meet ITS padded sub-cell (exact: the test that labelled it) and the shortest arc of the
-//      ring — a ring is a cycle: the arc may run over the closing vertex — that covers them,
-//   2. grows the arc at both ends while the end vertex's y lies in the sub-cell's closed y-interval,
-//   3. sums the contributions, at the sub-cell centre, of the edges of the centre's slab row that are NOT in the arc: `base`,
-//   4. copies the arc's first four vertices into the entry (vertices 4 .. follow in chain_ext: chain_ext_kernel).
-// An arc of more than CHAIN_MAX edges, a part with holes, or a cell whose edge list overflowed gets count = 0 (such rows are
-// decided by the generic walk).
-__global__ __launch_bounds__(256) void chain_aux_kernel(DevGeo a, PipView pv, FineGrid g, const int32_t* __restrict__ work_cell,
-                                                        const uint32_t* __restrict__ work_part, int64_t n_work,
-                                                        const int32_t* __restrict__ slab_vidx, const SubCell* __restrict__ sub,
-                                                        const int32_t* __restrict__ aux_base, ChainAux* __restrict__ aux,
-                                                        uint32_t* __restrict__ head, uint32_t* __restrict__ first_at,
-                                                        int32_t* __restrict__ ext_need) {
-    constexpr int S = PIP_SUB, SS = PIP_SUB * PIP_SUB;
-    static_assert(SUB_EDGE_CAP <= 64, "the touched edges of a sub-cell are a 64-bit mask over the cell's list");
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t item = t / SS;
-    const int k = (int)(t % SS);
-    if (item >= n_work) return;  // (whole waves: SS == 64)
-    const int64_t c = work_cell[item];
-    const int part = (int)work_part[item];
-    const SubCell rc = sub[item];
-    const uint32_t lw = rc.labels[k >> 4];
-    const bool test = ((lw >> (2 * (k & 15))) & 3u) == 2u;
-    const unsigned long long tm = __ballot(test);
-    if (tm == 0ull) return;  // uniform
-    const int ci = (int)(c % g.R), cj = (int)(c / g.R);
-    const int si = S * ci + (k % S), sj = S * cj + (k / S);
-    const double fw2 = g.fw / S, fh2 = g.fh / S, px2 = g.pad_x / S, py2 = g.pad_y / S;
-    const double xl = g.rx0 + (double)si * fw2 - px2, xh = g.rx0 + (double)(si + 1) * fw2 + px2;
-    const double yl = g.ry0 + (double)sj * fh2 - py2, yh = g.ry0 + (double)(sj + 1) * fh2 + py2;
-    const double cxl = g.rx0 + (double)(S * ci) * fw2 - px2, cxh = g.rx0 + (double)(S * ci + S) * fw2 + px2;
-    const double cyl = g.ry0 + (double)(S * cj) * fh2 - py2, cyh = g.ry0 + (double)(S * cj + S) * fh2 + py2;
-    __shared__ double4 s_edges[256 / 64][SUB_EDGE_CAP];
-    __shared__ int32_t s_vidx[256 / 64][SUB_EDGE_CAP];
-    const int wave = threadIdx.x >> 6, lane64 = threadIdx.x & 63;
-    int r0, r1;
-    dev::part_rings(a, part, r0, r1);
-    bool list_ok = r1 - r0 == 1;  // a part with holes: no chains (uniform)
-    int n_list = 0;
-    if (list_ok) {
-        int e0, e1;
-        if (pip::slab_span_of_raster_row(pv, r0, cj, e0, e1)) {
-            for (int eb = e0; eb < e1 && list_ok; eb += 64) {
-                const int e = eb + lane64;
-                bool keep = false;
-                double4 ed = make_double4(0, 0, 0, 0);
-                if (e < e1) {
-                    ed = pip::slab_edge(pv, e);
-                    keep = !(fmax(ed.x, ed.z) < cxl || fmin(ed.x, ed.z) > cxh || fmax(ed.y, ed.w) < cyl || fmin(ed.y, ed.w) > cyh);
-                }
-                const unsigned long long m = __ballot(keep);
-                const int add = __popcll(m);
-                if (n_list + add > SUB_EDGE_CAP) {
-                    list_ok = false;
-                    break;
-                }
-                if (keep) {
-                    const int at = n_list + __popcll(m & ((1ull << lane64) - 1ull));
-                    s_edges[wave][at] = ed;
-                    s_vidx[wave][at] = pip::slab_vertex(slab_vidx[e]);
-                }
-                n_list += add;
-            }
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!test) return;
-    const int rank = __popcll(tm & ((1ull << lane64) - 1ull));
-    const int64_t slot = (int64_t)aux_base[item] + rank;
-    ChainAux out;
-    out.v[0] = out.v[1] = out.v[2] = out.v[3] = make_double2(0.0, 0.0);
-    uint32_t out_head = 0u, out_first = 0u;
-    int need = 0;
-    const int c0 = list_ok ? a.ring_off[r0] : 0, ne = list_ok ? a.ring_off[r0 + 1] - c0 - 1 : 0;  // the ring's edges: 0 .. ne - 1 (closed ring)
-    if (list_ok && ne >= 1) {
-        // 1. the listed edges that meet this padded sub-cell (an edge listed for both slab rows of the cell appears twice: harmless)
-        unsigned long long touched = 0ull;
-        for (int e = 0; e < n_list; ++e) {
-            const double4 ed = s_edges[wave][e];
-            if (fmax(ed.x, ed.z) < xl || fmin(ed.x, ed.z) > xh || fmax(ed.y, ed.w) < yl || fmin(ed.y, ed.w) > yh) continue;
-            if (line_clear_of_rect(ed.x, ed.y, ed.z, ed.w, xl, yl, xh, yh)) continue;
-            touched |= 1ull << e;
-        }
-        // the shortest arc [lo, lo + len) of the cycle 0 .. ne - 1 that covers the touched edges: the complement of the widest
-        // gap between one touched edge and the next one after it
-        int lo = 0, len = 0;
-        if (touched) {
-            int best_gap = -1, best_a = 0, best_next = 0;
-            for (unsigned long long ma = touched; ma; ma &= ma - 1ull) {
-                const int ea = s_vidx[wave][__ffsll((long long)ma) - 1] - c0;
-                int nd = ne, nb = ea;  // distance to / index of the next touched edge after ea, cyclically (ne: ea is the only one)
-                for (unsigned long long mb = touched; mb; mb &= mb - 1ull) {
-                    const int eb = s_vidx[wave][__ffsll((long long)mb) - 1] - c0;
-                    int d = eb - ea;
-                    if (d < 0) d += ne;
-                    if (d > 0 && d < nd) {
-                        nd = d;
-                        nb = eb;
-                    }
-                }
-                if (nd > best_gap) {
-                    best_gap = nd;
-                    best_a = ea;
-                    best_next = nb;
-                }
-            }
-            lo = best_next;                    // the arc starts right after the widest gap ...
-            len = ne - best_gap + 1;           // ... and ends at the edge before it (one touched edge: best_gap = ne, len = 1)
-        }
-        bool ok = len >= 1 && len <= CHAIN_MAX;
-        // 2. grow: the arc's last edge ends at vertex lo + len, its first edge starts at vertex lo (indices modulo ne)
-        while (ok && len < ne) {
-            int hv = lo + len;
-            if (hv >= ne) hv -= ne;
-            const double y = a.xy[c0 + hv].y;
-            if (!(y >= yl && y <= yh)) break;
-            ++len;
-            ok = len <= CHAIN_MAX;
-        }
-        while (ok && len < ne) {
-            const double y = a.xy[c0 + lo].y;
-            if (!(y >= yl && y <= yh)) break;
-            lo = lo == 0 ? ne - 1 : lo - 1;
-            ++len;
-            ok = len <= CHAIN_MAX;
-        }
-        if (ok) {
-            // 3. base: the other edges' winding at the centre — they all sit in the centre's slab row
-            const double cx = g.rx0 + ((double)si + 0.5) * fw2, cy = g.ry0 + ((double)sj + 0.5) * fh2;
-            int e0, e1, wn = 0;
-            bool on = false;
-            if (pip::slab_range(pv, r0, pip::row_of(pv, cy), e0, e1)) {
-                for (int e = e0; e < e1; ++e) {
-                    int d = pip::slab_vertex(slab_vidx[e]) - c0 - lo;
-                    if (d < 0) d += ne;
-                    if (d < len) continue;  // an edge of the arc
-                    const double4 ed = pip::slab_edge(pv, e);
-                    on |= dev::ring_edge(ed.x, ed.y, ed.z, ed.w, cx, cy, wn);
-                }
-            }
-            if (!on && wn >= -127 && wn <= 127) {  // (an edge outside the arc cannot pass through the centre; guard anyway)
-                out_head = (uint32_t)len | ((uint32_t)(uint8_t)(int8_t)wn << CHAIN_BASE_SHIFT);
-                out_first = (uint32_t)(c0 + lo);
-                for (int j = 0; j < 4; ++j) {  // 4. vertices 0 .. 3 (a shorter chain repeats its last vertex)
-                    const int v = (lo + (j <= len ? j : len)) % ne;
-                    out.v[j] = a.xy[c0 + v];
-                }
-                need = len > 3 ? len - 3 : 0;
-            }
-        }
-    }
-    aux[slot] = out;
-    head[slot] = out_head;
-    first_at[slot] = out_first;
-    ext_need[slot] = need;
-}
-// vertices 4 .. count of the chains longer than three edges (one thread per chain entry), and where they are in the entry's head
-__global__ void chain_ext_kernel(DevGeo a, uint32_t* __restrict__ head, const uint32_t* __restrict__ first_at, int64_t n_aux,
-                                 const int32_t* __restrict__ ext_off, double2* __restrict__ ext) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_aux) return;
-    const int len = (int)(head[i] & CHAIN_COUNT_MASK);
-    if (len <= 3) return;
-    if ((uint32_t)ext_off[i] >= (1u << (32 - CHAIN_EXT_SHIFT))) {  // the offset does not fit the head word: no chain entry (the generic walk decides)
-        head[i] = 0u;
-        return;
-    }
-    const int r = ring_of_coord(a.ring_off, (int)a.n_rings, (int)first_at[i]);
-    const int c0 = a.ring_off[r], ne = a.ring_off[r + 1] - c0 - 1;
-    const int lo = (int)first_at[i] - c0;
-    head[i] |= (uint32_t)ext_off[i] << CHAIN_EXT_SHIFT;
-    for (int j = 4; j <= len; ++j) ext[ext_off[i] + (j - 4)] = a.xy[c0 + (lo + j) % ne];
-}
-// ---- half-cell chains (gpk_index.h: GPK_HALF_CHAINS) -------------------------------------------------------------------------
 // extended ring coordinates: ring r's n coordinates followed by CHAIN_MAX more, entry k = coordinate k % (n - 1)
 __global__ void chain_xy_kernel(DevGeo a, double2* __restrict__ ext) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1060,17 +863,6 @@ __global__ void half_chain_commit_kernel(SubCell* __restrict__ sub, int64_t n_su
     h[0] = HalfCell{{rc.labels[0], rc.labels[1]}, rc.part_flags & ~SUB_INDIRECT, hword[2 * i]};
     h[1] = HalfCell{{rc.labels[2], rc.labels[3]}, rc.part_flags & ~SUB_INDIRECT, hword[2 * i + 1]};
 }
-// an index with chains: every one-part record is rewritten as two half-cell records (gpk_index.h: HalfCell) — after chain_aux_kernel,
-// which reads the SubCell form
-__global__ void chain_commit_kernel(SubCell* __restrict__ sub, int64_t n_sub, const int32_t* __restrict__ aux_base) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_sub) return;
-    const SubCell rc = sub[i];
-    const uint32_t lower_tests = (uint32_t)(test_labels_of(rc.labels[0]) + test_labels_of(rc.labels[1]));
-    HalfCell* h = reinterpret_cast<HalfCell*>(sub + i);
-    h[0] = HalfCell{{rc.labels[0], rc.labels[1]}, rc.part_flags & ~SUB_INDIRECT, (uint32_t)aux_base[i]};
-    h[1] = HalfCell{{rc.labels[2], rc.labels[3]}, rc.part_flags & ~SUB_INDIRECT, (uint32_t)aux_base[i] + lower_tests};
-}
 // LDS image of the level-1 routing (gpk_index.h: RouteWord): one thread per 32 cells of a raster row, after sub_commit_kernel
 __global__ void route_build_kernel(const uint32_t* __restrict__ cell, int64_t n_words, RouteWord* __restrict__ route) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1189,23 +981,18 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
     const double w = hg.inv_w > 0.0 ? (double)hg.gx / hg.inv_w : 0.0, h = hg.inv_h > 0.0 ? (double)hg.gy / hg.inv_h : 0.0;
     if (!(w > 0.0) || !(h > 0.0) || !std::isfinite(w) || !std::isfinite(h)) return GPK_OK;  // degenerate extent
 
-    int R = 64, r_max = 2048;
-    if (const char* e = getenv("GPK_PIP_RMAX")) {  // tuning knob: cap of the level-1 raster side (power of two, 64..4096)
-        const int v = atoi(e);
-        if (v >= 64 && v <= 4096 && (v & (v - 1)) == 0) r_max = v;
-    }
-    while (R < r_max && (double)R < 2.0 * sqrt((double)d.n_coords)) R <<= 1;
+    int R = 64;
+    while (R < 2048 && (double)R < 2.0 * sqrt((double)d.n_coords)) R <<= 1;
     // a column of MANY small parts (C5: 6.5M parts of 5M multipolygons) puts 1.5 parts into every cell of the 2048 raster and every
     // point walks an entry list; one more doubling: tile 1.91 -> 1.54 ms, level-1 words 16 -> 64 MB
     // At that resolution the per-entry records of the remaining list cells (29M of them for C5) cost 97 ms of a 215 ms build to
     // take 2.03 -> 1.57 ms per 6.25M-point join: they are built on request only (GPK_INDEX_PIP_FULL), the entry lists get part boxes
     bool many_parts = false;
-    if (!getenv("GPK_PIP_RMAX") && R == 2048 && d.n_parts > (int64_t)R * R / 2) {
+    if (R == 2048 && d.n_parts > (int64_t)R * R / 2) {
         R = 4096;
         many_parts = true;
     }
-    bool list_records = list_records_mode == 2 || (list_records_mode == 1 && !many_parts);
-    if (const char* e = getenv("GPK_LIST_RECORDS")) list_records = atoi(e) != 0;  // tuning knob
+    const bool list_records = list_records_mode == 2 || (list_records_mode == 1 && !many_parts);
     FineGrid g;
     g.R = R;
     g.fw = w / (double)(R - 3);
@@ -1327,12 +1114,10 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
     }
     stamp("slab rows + counts");
     // slab entries: 32-byte edge copies for small right sides (one load level in the exact walk), 4-byte coordinate indices beyond
-    // GPK_SLAB_COPY_MAX_MB (default 256) of copies — the copies of a 144M-coordinate column were 5 of its index's 6.4 GB
+    // 256 MB of copies — the copies of a 144M-coordinate column were 5 of its index's 6.4 GB
     double4* edges = nullptr;
     int32_t* slab_vidx = nullptr;  // also read by the chain build of lean indexes
-    size_t copy_max = size_t(256) << 20;
-    if (const char* e = getenv("GPK_SLAB_COPY_MAX_MB")) copy_max = (size_t)atoll(e) << 20;
-    const bool edge_copies = sizeof(double4) * (size_t)n_edges <= copy_max;
+    const bool edge_copies = sizeof(double4) * (size_t)n_edges <= (size_t(256) << 20);
     if (edge_copies) {
         GPK_HIP(cached_malloc((void**)&edges, sizeof(double4) * (size_t)(n_edges ? n_edges : 1)));
         keep(edges);
@@ -1490,8 +1275,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
             // no ring with refined rows: nearly every record takes the fast path — its own instance (twice the waves per SIMD), then one
             // for the stragglers (parts with holes); a column WITH refined rings (C5: 15 % of the records) keeps the single launch,
             // where a second pass over all records to find the others costs more than the occupancy gives (measured: +1 ms / -10 %)
-            static const bool force_split = getenv("GPK_SUB_SPLIT") != nullptr;  // A/B runs: the two instances also for columns with refined rings
-            if (n_refined == 0 || force_split) {
+            if (n_refined == 0) {
                 GPK_LAUNCH("gpk_pipidx_sub_build_fast", (sub_build_kernel<1, true, 1>), blocks_for((int64_t)n_sub * PIP_SUB * PIP_SUB), dim3(256), 0, s, d, pv, g,
                            (const int32_t*)nullptr, (const int32_t*)nullptr, n_cells, (const uint32_t*)cell, (const uint32_t*)list, sub, (SubCell2*)nullptr,
                            (const int32_t*)swork_cell, (const uint32_t*)swork_part, (int64_t)n_sub);
@@ -1523,7 +1307,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
     // records for the boundary entries of the cells that stayed lists (after the commit: two-part cells are gone)
     int32_t n_lrec = 0;
     SubCell* lrec = nullptr;
-    if (level2_ok && list_len > 0 && list_records && !getenv("GPK_NO_LIST_RECORDS")) {
+    if (level2_ok && list_len > 0 && list_records) {
         int32_t *lcnt, *lpos;
         GPK_TRY(t.alloc(&lcnt, (size_t)n_cells + 1));
         GPK_TRY(t.alloc(&lpos, (size_t)n_cells + 1));
@@ -1564,7 +1348,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
     }
     stamp("list-cell records");
     pv.lrec = lrec;
-    if (list_len > 0 && !lrec && !getenv("GPK_NO_PART_BOX")) {  // plain entry lists: a box per part rejects most (point, entry) pairs early
+    if (list_len > 0 && !lrec) {  // plain entry lists: a box per part rejects most (point, entry) pairs early
         float4* part_box = nullptr;
         GPK_HIP(cached_malloc((void**)&part_box, sizeof(float4) * (size_t)(n_parts ? n_parts : 1)));
         keep(part_box);
@@ -1580,11 +1364,10 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
     // their points through the generic walk: at most 1 list word per 8 one-part records)
     ix->pip_lean = (int64_t)list_len * 8 <= (int64_t)n_sub && n_refined == 0 && boundary_cells_have_records ? 1 : 0;
     if (getenv("GPK_DEBUG_INDEX")) fprintf(stderr, "[gpk] lean join kernel eligible: %d (list %d, refined rings: %s, one-part records %d)\n", ix->pip_lean, list_len, n_refined ? "some" : "none", n_sub);
-    // local chains for the `test` sub-cells of a lean index (gpk_index.h: ChainAux): the join then decides them in the owning lane
-    if (GPK_HALF_CHAINS && ix->pip_lean && slab_vidx && n_sub > 0 && swork_cell && !getenv("GPK_NO_CHAINS") &&
-        d.n_coords + d.n_rings * CHAIN_MAX < ((int64_t)1 << (32 - HCHAIN_START_SHIFT))) {
-        // half-cell chains (gpk_index.h: GPK_HALF_CHAINS): the extended coordinates, one chain word per half record, the records
-        // rewritten as half-cell records carrying their word — three launches, no table sized by a read-back
+    // local chains for the `test` sub-cells of a lean index (gpk_index.h: HCHAIN_*): the join then decides them in the owning lane.
+    // The extended coordinates, one chain word per half record, the records rewritten as half-cell records carrying their word —
+    // three launches, no table sized by a read-back
+    if (ix->pip_lean && slab_vidx && n_sub > 0 && swork_cell && d.n_coords + d.n_rings * CHAIN_MAX < ((int64_t)1 << (32 - HCHAIN_START_SHIFT))) {
         const int64_t n_ext = d.n_coords + d.n_rings * CHAIN_MAX;
         double2* cxy = nullptr;
         GPK_HIP(cached_malloc((void**)&cxy, sizeof(double2) * (size_t)n_ext));
@@ -1598,7 +1381,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
         GPK_LAUNCH("gpk_pipidx_chain_commit", half_chain_commit_kernel, blocks_for(n_sub), dim3(256), 0, s, sub, (int64_t)n_sub, (const uint32_t*)hword);
         pv.chain_xy = cxy;
         ix->nbytes += (int64_t)(sizeof(double2) * (size_t)n_ext);
-        if (R <= PIP_ROUTE_RMAX && !getenv("GPK_NO_ROUTE_IMAGE")) {
+        if (R <= PIP_ROUTE_RMAX) {
             RouteWord* route = nullptr;
             const int64_t n_words = n_cells / 32;
             GPK_HIP(cached_malloc((void**)&route, sizeof(RouteWord) * (size_t)n_words));
@@ -1610,64 +1393,6 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
         }
         GPK_HIP(hipStreamSynchronize(s));  // (the temporaries go back to the arena when this function returns)
         if (getenv("GPK_DEBUG_INDEX")) fprintf(stderr, "[gpk] half-cell chains: %d records, %lld extended coordinates%s\n", n_sub, (long long)n_ext, pv.route ? ", routing image" : "");
-        stamp("local chains");
-    } else if (!GPK_HALF_CHAINS && ix->pip_lean && slab_vidx && n_sub > 0 && swork_cell && !getenv("GPK_NO_CHAINS")) {
-        int32_t *ccnt, *cbase_tmp;
-        GPK_TRY(t.alloc(&ccnt, (size_t)n_sub + 1));
-        GPK_TRY(t.alloc(&cbase_tmp, (size_t)n_sub + 1));
-        pv.sub = sub;
-        GPK_LAUNCH("gpk_pipidx_chain_count", chain_count_kernel, blocks_for(n_sub), dim3(256), 0, s, (const SubCell*)sub, (int64_t)n_sub, ccnt);
-        GPK_TRY(exclusive_scan_i32(ccnt, n_sub, cbase_tmp, nullptr, btot, s));
-        int32_t n_aux = 0;
-        GPK_HIP(d2h_small(&n_aux, cbase_tmp + n_sub, sizeof n_aux, s));
-        GPK_HIP(sync_small(s));
-        if (n_aux > 0) {
-            ChainAux* aux = nullptr;
-            GPK_HIP(cached_malloc((void**)&aux, sizeof(ChainAux) * (size_t)n_aux));
-            keep(aux);
-            uint32_t* chead = nullptr;
-            GPK_HIP(cached_malloc((void**)&chead, sizeof(uint32_t) * (size_t)n_aux));
-            keep(chead);
-            int32_t *ext_need, *ext_off;
-            uint32_t* first_at;
-            GPK_TRY(t.alloc(&ext_need, (size_t)n_aux + 1));
-            GPK_TRY(t.alloc(&ext_off, (size_t)n_aux + 1));
-            GPK_TRY(t.alloc(&first_at, (size_t)n_aux + 1));
-            unsigned long long* btot3;
-            GPK_TRY(t.alloc(&btot3, (size_t)((n_aux + 255) / 256 + 4)));
-            GPK_LAUNCH("gpk_pipidx_chain_aux", chain_aux_kernel, blocks_for((int64_t)n_sub * PIP_SUB * PIP_SUB), dim3(256), 0, s, d, pv, g,
-                       (const int32_t*)swork_cell, (const uint32_t*)swork_part, (int64_t)n_sub, (const int32_t*)slab_vidx, (const SubCell*)sub,
-                       (const int32_t*)cbase_tmp, aux, chead, first_at, ext_need);
-            GPK_TRY(exclusive_scan_i32(ext_need, n_aux, ext_off, nullptr, btot3, s));
-            int32_t n_ext = 0;
-            GPK_HIP(d2h_small(&n_ext, ext_off + n_aux, sizeof n_ext, s));
-            GPK_HIP(sync_small(s));
-            double2* ext = nullptr;
-            GPK_HIP(cached_malloc((void**)&ext, sizeof(double2) * (size_t)(n_ext > 0 ? n_ext : 1)));
-            keep(ext);
-            if (n_ext > 0)
-                GPK_LAUNCH("gpk_pipidx_chain_ext", chain_ext_kernel, blocks_for(n_aux), dim3(256), 0, s, d, chead, (const uint32_t*)first_at, (int64_t)n_aux,
-                           (const int32_t*)ext_off, ext);
-            pv.chain_head = chead;
-            pv.chain_ext = ext;
-            ix->nbytes += (int64_t)(sizeof(double2) * (size_t)n_ext + sizeof(uint32_t) * (size_t)n_aux);
-            // (after chain_aux_kernel, which still reads the records' labels only: e0 now names the record's first chain entry)
-            GPK_LAUNCH("gpk_pipidx_chain_commit", chain_commit_kernel, blocks_for(n_sub), dim3(256), 0, s, sub, (int64_t)n_sub, (const int32_t*)cbase_tmp);
-            pv.sub_aux = aux;
-            ix->nbytes += (int64_t)(sizeof(ChainAux) * (size_t)n_aux);
-            if (R <= PIP_ROUTE_RMAX && !getenv("GPK_NO_ROUTE_IMAGE")) {
-                RouteWord* route = nullptr;
-                const int64_t n_words = n_cells / 32;
-                GPK_HIP(cached_malloc((void**)&route, sizeof(RouteWord) * (size_t)n_words));
-                keep(route);
-                GPK_LAUNCH("gpk_pipidx_route", route_build_kernel, blocks_for(n_words), dim3(256), 0, s, (const uint32_t*)cell, n_words, route);
-            if (R >= 32) GPK_LAUNCH("gpk_pipidx_route_rank", route_rank_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, s, route, R);
-                pv.route = route;
-                ix->nbytes += (int64_t)(sizeof(RouteWord) * (size_t)n_words);
-            }
-            GPK_HIP(hipStreamSynchronize(s));
-            if (getenv("GPK_DEBUG_INDEX")) fprintf(stderr, "[gpk] local chains: %d test sub-cells in %d records%s\n", n_aux, n_sub, pv.route ? ", routing image" : "");
-        }
         stamp("local chains");
     }
     ix->nbytes += (int64_t)(sizeof(SubCell) * (size_t)n_sub + sizeof(SubCell2) * (size_t)n_sub2 + sizeof(SubCell) * (size_t)n_lrec);

@@ -38,10 +38,7 @@ struct ChainHot {
     double rx0, ry0, inv_fw, inv_fh;
     const uint32_t* cell;
     const HalfCell* half;
-    const ChainAux* sub_aux;
-    const uint32_t* chain_head;
-    const double2* chain_ext;
-    const double2* chain_xy;  // GPK_HALF_CHAINS: the vertices the records' chain words index
+    const double2* chain_xy;  // the vertices the records' chain words index
     const uint32_t* part_geom;
     const RouteWord* route;
     uint32_t* counts;

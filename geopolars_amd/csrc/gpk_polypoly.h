@@ -5,9 +5,6 @@
 
 #include "gpk_device.h"
 
-#ifndef GPK_PP_BOX_SKIP
-#define GPK_PP_BOX_SKIP 1  // a vertex outside the other polygon's exterior box is outside it: the containment walk is skipped
-#endif
 namespace gpk {
 
 // Intersects<Line> for Line (geo 0.27 intersects/line.rs)
@@ -214,10 +211,7 @@ __device__ inline void polygon_bboxes_group(const DevGeo& a, int r0, int r1, int
 // Neighbouring polygons overlap in a small window, which takes the O(n*m) pruning loop down to the few segments
 // that can matter.  seg_list: 2 * PP_LIST double4 owned by this group (all lanes of a group sit in one wave).
 constexpr int PP_VOTE = 4;   // list entries between two group votes in the cross test
-#ifndef GPK_PP_LIST
-#define GPK_PP_LIST 32
-#endif
-constexpr int PP_LIST = GPK_PP_LIST;  // per list; a group owns two lists (2 * PP_LIST double4 = 2 KB)
+constexpr int PP_LIST = 32;  // per list; a group owns two lists (2 * PP_LIST double4 = 2 KB)
 template <int G>
 __device__ inline bool polygon_intersects_polygon_group(const DevGeo& a, int ar0, int ar1, const DevGeo& b, int br0, int br1, int lane,
                                                         double4* __restrict__ seg_list, bool have_a_box = false,
@@ -318,12 +312,13 @@ __device__ inline bool polygon_intersects_polygon_group(const DevGeo& a, int ar0
         const int c = b.ring_off[rb];
         if (b.ring_off[rb + 1] > c) {
             const double2 q = b.xy[c];
-            if (GPK_PP_BOX_SKIP && !(q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w)) continue;
+            // (a vertex outside the other polygon's exterior box is outside it: the containment walk is skipped)
+            if (!(q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w)) continue;
             if (polygon_pos_group<G>(a, ar0, ar1, q.x, q.y, lane) != dev::POS_OUTSIDE) return true;
         }
     }
     const double2 p = a.xy[a_c0];
-    if (GPK_PP_BOX_SKIP && !(p.x >= eb.x && p.x <= eb.z && p.y >= eb.y && p.y <= eb.w)) return false;
+    if (!(p.x >= eb.x && p.x <= eb.z && p.y >= eb.y && p.y <= eb.w)) return false;
     return polygon_pos_group<G>(b, br0, br1, p.x, p.y, lane) != dev::POS_OUTSIDE;
 }
 
@@ -414,10 +409,10 @@ __device__ inline bool polygon_pair_small(const double2* __restrict__ axy, int n
         // other ring's BOX is outside the ring: neighbours whose boxes merely overlap — most candidates that do not intersect — skip both
         // ring walks (round 6: the walks were a third of the refine)
         const double2 q = t->b[0];
-        if (!GPK_PP_BOX_SKIP || (q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w)) hit = coord_pos_ring_group<G>(t->a, na, q.x, q.y, lane) != dev::POS_OUTSIDE;
+        if (q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w) hit = coord_pos_ring_group<G>(t->a, na, q.x, q.y, lane) != dev::POS_OUTSIDE;
         if (!hit) {
             const double2 p = t->a[0];
-            if (!GPK_PP_BOX_SKIP || (p.x >= eb.x && p.x <= eb.z && p.y >= eb.y && p.y <= eb.w)) hit = coord_pos_ring_group<G>(t->b, nb, p.x, p.y, lane) != dev::POS_OUTSIDE;
+            if (p.x >= eb.x && p.x <= eb.z && p.y >= eb.y && p.y <= eb.w) hit = coord_pos_ring_group<G>(t->b, nb, p.x, p.y, lane) != dev::POS_OUTSIDE;
         }
     }
     __builtin_amdgcn_wave_barrier();  // the slice may be overwritten after this point

@@ -1,6 +1,6 @@
-// gpk_ringstream.hip — area / signed_area / euclidean_length / bounds of a POLYGON or MULTIPOLYGON column as ONE pass over the
-// coordinate buffer in storage order (geoseries.rs:14-16,28-41,188-190,200-202; geo 0.27 area.rs / bounding_rect.rs /
-// euclidean_length.rs semantics, the same arithmetic per edge and per geometry as gpk_unary.hip's two-stage form).
+// gpk_ringstream.hip — area / signed_area / euclidean_length of a POLYGON or MULTIPOLYGON column as ONE pass over the
+// coordinate buffer in storage order (geoseries.rs:14-16,28-41,188-190; geo 0.27 area.rs / euclidean_length.rs semantics, the same
+// arithmetic per edge and per geometry as gpk_unary.hip's two-stage form).
 //
 // Why a second form: gpk_unary.hip gives every RING a lane group sized by the ring's length (rings bucketed into classes once per
 // column) and folds the rings of a geometry in a second launch.  On a ragged column (ring lengths Pareto-distributed: most rings a
@@ -11,17 +11,16 @@
 //     1 KB a wave per instruction, the next block requested before this one is worked on, and turned through a padded LDS buffer);
 //   * where rings begin is a bit mask of the strip built from the ring offsets (the column's strip table — first ring / first geometry
 //     of every strip, built once per handle — says which offsets); a lane walks its coordinates with the mask's bits for them (+ the next lane's first) in a register:
-//     rings that begin and end inside the lane are finished there, the ring that crosses lanes is finished by a SEGMENTED SCAN over
-//     the lanes' open partial sums, the ring that crosses blocks rides in wave-uniform registers;
-//   * ring values land in an LDS table indexed by the ring's number within the strip; at the end of the strip a lane per GEOMETRY that
-//     began in the strip folds its rings from that table with the polygon / multipolygon rules and writes the result row: no table in
-//     global memory, no second launch;
+//     every run of coordinates of one ring in the lane adds its partial sum into that ring's slot of an LDS table indexed by the ring's
+//     number within the strip (rs_flush: one ds_add_f64, nothing returned) — a ring that crosses lanes or blocks gets one add per piece;
+//   * at the end of the strip a lane per GEOMETRY that began in the strip folds its rings from that table with the polygon /
+//     multipolygon rules and writes the result row: no table in global memory, no second launch;
 //   * what crosses a strip boundary — a ring (its partial sums before and after the boundary) or a geometry (the values of its rings
 //     that are complete in some strip) — is left in two small global arrays, and a second, tiny launch (one thread per strip boundary)
 //     finishes those geometries: one in ~30 on the power-law column.
 // Work is balanced by construction (every wave streams the same number of bytes), every load is coalesced, and the sums have a fixed
 // order given the column's layout (bit-reproducible run to run; the order differs from the two-stage form's pairing tree, both are
-// within the tests' tolerance of the oracle's sequential sums; min / max are exact).
+// within the tests' tolerance of the oracle's sequential sums).
 //
 // Eligible columns (checked once per handle, gpk_seq_classes::strips_ok): ring offsets start at 0 and end at n_coords, no zero-length
 // ring (a strip's ring numbers are then consecutive: ring = first ring of the strip + heads seen), at most RS_CAP rings beginning in
@@ -35,36 +34,20 @@ namespace gpk {
 namespace {
 
 template <int OP>
-constexpr int rs_k() { return OP == RS_BOUNDS ? 4 : 1; }
-template <int OP>
 struct RsVal {
-    double v[rs_k<OP>()];
+    double v;
 };
 template <int OP>
 __device__ __forceinline__ RsVal<OP> rs_identity() {
     RsVal<OP> r;
-    if constexpr (OP == RS_BOUNDS) {
-        r.v[0] = INFINITY;
-        r.v[1] = INFINITY;
-        r.v[2] = -INFINITY;
-        r.v[3] = -INFINITY;
-    } else {
-        r.v[0] = 0.0;
-    }
+    r.v = 0.0;
     return r;
 }
 // `left` covers coordinates before `right`'s
 template <int OP>
 __device__ __forceinline__ RsVal<OP> rs_combine(const RsVal<OP>& left, const RsVal<OP>& right) {
     RsVal<OP> r;
-    if constexpr (OP == RS_BOUNDS) {
-        r.v[0] = right.v[0] < left.v[0] ? right.v[0] : left.v[0];
-        r.v[1] = right.v[1] < left.v[1] ? right.v[1] : left.v[1];
-        r.v[2] = right.v[2] > left.v[2] ? right.v[2] : left.v[2];
-        r.v[3] = right.v[3] > left.v[3] ? right.v[3] : left.v[3];
-    } else {
-        r.v[0] = left.v[0] + right.v[0];
-    }
+    r.v = left.v + right.v;
     return r;
 }
 // coordinate p of a ring whose first coordinate is `first`; q = the coordinate stored after p; `tail`: p is the ring's last coordinate
@@ -72,19 +55,14 @@ __device__ __forceinline__ RsVal<OP> rs_combine(const RsVal<OP>& left, const RsV
 // of a ring that turns out open, which added nothing in the two-stage form either.
 template <int OP>
 __device__ __forceinline__ void rs_accumulate(RsVal<OP>& a, double2 p, double2 q, double2 first, bool tail) {
-    if constexpr (OP == RS_BOUNDS) {
-        a.v[0] = p.x < a.v[0] ? p.x : a.v[0];
-        a.v[1] = p.y < a.v[1] ? p.y : a.v[1];
-        a.v[2] = p.x > a.v[2] ? p.x : a.v[2];
-        a.v[3] = p.y > a.v[3] ? p.y : a.v[3];
-    } else if constexpr (OP == RS_LENGTH) {
+    if constexpr (OP == RS_LENGTH) {
         const double l = hypot(q.x - p.x, q.y - p.y);
-        a.v[0] += tail ? 0.0 : l;
+        a.v += tail ? 0.0 : l;
     } else {
         const double sx = p.x - first.x, sy = p.y - first.y;
         const double ex = q.x - first.x, ey = q.y - first.y;
         const double cr = sx * ey - sy * ex;
-        if (!tail) a.v[0] += cr;
+        if (!tail) a.v += cr;
     }
 }
 // a ring's value from the sum over its coordinates: twice_signed_ring_area is 0 for a ring that is not closed (area.rs); a ring of one
@@ -93,59 +71,41 @@ template <int OP>
 __device__ __forceinline__ RsVal<OP> rs_ring_value(const RsVal<OP>& sum, double2 first, double2 last) {
     if constexpr (OP == RS_AREA || OP == RS_SIGNED_AREA) {
         RsVal<OP> r;
-        r.v[0] = (first.x == last.x && first.y == last.y) ? sum.v[0] : 0.0;
+        r.v = (first.x == last.x && first.y == last.y) ? sum.v : 0.0;
         return r;
     } else {
         return sum;
     }
 }
 
-// ---- the per-geometry rules (area_combine_kernel / length_combine_kernel / bounds_combine_kernel of gpk_unary.hip, the ring values
+// ---- the per-geometry rules (area_combine_kernel / length_combine_kernel of gpk_unary.hip, the ring values
 // read through `val`) ----
 template <int OP, typename F>
 __device__ __forceinline__ void rs_geometry(const DevGeo& a, int64_t g, F val, double* __restrict__ out) {
     const bool valid = dev::valid_row(a.validity, g);
     int p0, p1;
     dev::geom_parts(a, g, p0, p1);
-    if constexpr (OP == RS_BOUNDS) {
-        RsVal<OP> b = rs_identity<OP>();
-        bool have = false;
-        if (valid)
-            for (int p = p0; p < p1; ++p) {
-                int r0, r1;
-                dev::part_rings(a, p, r0, r1);
-                if (r1 <= r0) continue;  // (no zero-length rings in an eligible column)
-                have = true;
-                const RsVal<OP> e = val(r0);  // Polygon::bounding_rect scans the exterior only
-                b.v[0] = fmin(b.v[0], e.v[0]);
-                b.v[1] = fmin(b.v[1], e.v[1]);
-                b.v[2] = fmax(b.v[2], e.v[2]);
-                b.v[3] = fmax(b.v[3], e.v[3]);
-            }
-        reinterpret_cast<double4*>(out)[g] = have ? make_double4(b.v[0], b.v[1], b.v[2], b.v[3]) : make_double4(NAN, NAN, NAN, NAN);
-    } else {
-        if (!valid) {
-            out[g] = NAN;
-            return;
-        }
-        double v = 0.0;
-        for (int p = p0; p < p1; ++p) {
-            int r0, r1;
-            dev::part_rings(a, p, r0, r1);
-            if (r1 <= r0) continue;
-            if constexpr (OP == RS_LENGTH) {
-                v += val(r0).v[0];  // exterior rings only
-            } else {
-                double area = val(r0).v[0] / 2.0;
-                const bool neg = area < 0.0;
-                area = fabs(area);
-                for (int r = r0 + 1; r < r1; ++r) area -= fabs(val(r).v[0] / 2.0);
-                const double sa = neg ? -area : area;
-                v += OP == RS_SIGNED_AREA ? sa : fabs(sa);
-            }
-        }
-        out[g] = v;
+    if (!valid) {
+        out[g] = NAN;
+        return;
     }
+    double v = 0.0;
+    for (int p = p0; p < p1; ++p) {
+        int r0, r1;
+        dev::part_rings(a, p, r0, r1);
+        if (r1 <= r0) continue;
+        if constexpr (OP == RS_LENGTH) {
+            v += val(r0).v;  // exterior rings only
+        } else {
+            double area = val(r0).v / 2.0;
+            const bool neg = area < 0.0;
+            area = fabs(area);
+            for (int r = r0 + 1; r < r1; ++r) area -= fabs(val(r).v / 2.0);
+            const double sa = neg ? -area : area;
+            v += OP == RS_SIGNED_AREA ? sa : fabs(sa);
+        }
+    }
+    out[g] = v;
 }
 // first ring of geometry g and the ring after its last one (g = n_geoms: the column's ring count twice)
 __device__ __forceinline__ void rs_geom_rings(const DevGeo& a, int64_t g, int& r_begin, int& r_end) {
@@ -176,31 +136,23 @@ constexpr int RS_MASK_WORDS = RS_STRIP / 32 + 2;
 constexpr int RS_OPEN_WORDS = (RS_CAP + 2 + 31) / 32;
 
 // One more term into a ring's slot of the strip's table.  The table belongs to ONE wave and every update is an LDS read-modify-write
-// instruction of that wave (ds_add_f64 / ds_min_f64 / ds_max_f64, nothing returned, nothing waited for): the updates of a slot happen in
+// instruction of that wave (ds_add_f64, nothing returned, nothing waited for): the updates of a slot happen in
 // program order, lanes of one instruction in the hardware's fixed order — the sums are reproducible run to run.
 template <int OP>
 __device__ __forceinline__ void rs_flush(double* s_val, int lid, const RsVal<OP>& v) {
-    if constexpr (OP == RS_BOUNDS) {
-        __hip_atomic_fetch_min(&s_val[lid * 4 + 0], v.v[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_min(&s_val[lid * 4 + 1], v.v[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_max(&s_val[lid * 4 + 2], v.v[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __hip_atomic_fetch_max(&s_val[lid * 4 + 3], v.v[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    } else {
-        __hip_atomic_fetch_add(&s_val[lid], v.v[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    }
+    __hip_atomic_fetch_add(&s_val[lid], v.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
 template <int OP>
 __global__ __launch_bounds__(64 * RS_WAVES) void ring_stream_kernel(DevGeo a, const int32_t* __restrict__ ring_first, const int32_t* __restrict__ geom_first,
                                                                     int64_t n_strips, double* __restrict__ ring_vals, double* __restrict__ strip_part,
                                                                     double* __restrict__ out) {
-    constexpr int K = rs_k<OP>();
     constexpr bool AREA = OP == RS_AREA || OP == RS_SIGNED_AREA;
     __shared__ double2 s_xy_all[RS_WAVES][RS_XY_SLOTS];
     __shared__ uint32_t s_mask_all[RS_WAVES][RS_MASK_WORDS];
     __shared__ uint32_t s_wpre_all[RS_WAVES][RS_MASK_WORDS];
     __shared__ uint32_t s_open_all[RS_WAVES][RS_OPEN_WORDS];
-    __shared__ double s_val_all[RS_WAVES][(RS_CAP + 2) * K];
+    __shared__ double s_val_all[RS_WAVES][RS_CAP + 2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t strip = (int64_t)blockIdx.x * RS_WAVES + wave;
     if (strip >= n_strips) return;  // (no work-group barrier anywhere: the waves of a work-group only share its launch)
@@ -232,7 +184,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void ring_stream_kernel(DevGeo a, co
     // where rings begin: one bit per coordinate of the strip (+ one for the coordinate after it: is the strip's last coordinate a ring's last?)
     for (int w = lane; w < RS_MASK_WORDS; w += 64) s_mask[w] = 0u;
     if (lane < RS_OPEN_WORDS) s_open[lane] = 0u;
-    for (int i = lane; i < (RS_CAP + 2) * K; i += 64) s_val[i] = rs_identity<OP>().v[i % K];
+    for (int i = lane; i < RS_CAP + 2; i += 64) s_val[i] = rs_identity<OP>().v;
     rs_wave_fence();
     for (int i = lane; i <= s_next - s_lo; i += 64) {  // (ring s_next too: it begins at the strip's end or later; the column's end is offset n_rings)
         const int64_t c = (int64_t)ring_off[s_lo + i] - base;
@@ -268,33 +220,33 @@ __global__ __launch_bounds__(64 * RS_WAVES) void ring_stream_kernel(DevGeo a, co
         rs_wave_fence();
         const int pos0 = b * RS_BLOCK + CPL * lane;  // my first coordinate within the strip
         const uint32_t m_lo = s_mask[pos0 >> 5], m_hi = s_mask[(pos0 >> 5) + 1];
-        const uint32_t hb = (uint32_t)(((((unsigned long long)m_hi) << 32) | m_lo) >> (pos0 & 31)) & ((2u << CPL) - 1u);  // bit j: a ring begins at my coordinate j (j = 8: at the next lane's first)
+        const uint32_t hb = (uint32_t)(((((unsigned long long)m_hi) << 32) | m_lo) >> (pos0 & 31)) & ((2u << CPL) - 1u);  // bit j: a ring begins at my coordinate j (j = CPL: at the next lane's first)
         int lid = (int)(s_wpre[pos0 >> 5] + __popc(m_lo & ((1u << (pos0 & 31)) - 1u)));  // rings begun before my first coordinate: its ring's number in the strip (0: the ring that entered the strip)
         double2 c[CPL + 1];
 #pragma unroll
         for (int j = 0; j < CPL; ++j) c[j] = s_xy[(CPL + 1) * lane + j];
         c[CPL] = s_xy[(CPL + 1) * lane + CPL + 1];  // (the next lane's first coordinate; lane 63: the coordinate after the block)
-        const uint32_t heads8 = hb & CMASK, tails8 = (hb >> 1) & CMASK;
+        const uint32_t heads = hb & CMASK, tails = (hb >> 1) & CMASK;
         const int64_t left = n_coords - (b0 + CPL * lane);
-        const uint32_t live8 = left >= CPL ? CMASK : (left <= 0 ? 0u : (1u << (int)left) - 1u);
-        const uint32_t drop8 = tails8 | ~live8;  // no edge leaves a ring's last coordinate (or the column)
+        const uint32_t live = left >= CPL ? CMASK : (left <= 0 ? 0u : (1u << (int)left) - 1u);
+        const uint32_t drop = tails | ~live;  // no edge leaves a ring's last coordinate (or the column)
         // the first coordinate of the ring my first coordinate belongs to: the last ring begun in a lane before mine, else the block's carry
         double2 first = first_carry;
         if (AREA) {
-            const unsigned long long head_lanes = __ballot(heads8 != 0u);
+            const unsigned long long head_lanes = __ballot(heads != 0u);
             const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-            if (heads8) {
+            if (heads) {
                 double2 h = c[0];
 #pragma unroll
                 for (int j = 1; j < CPL; ++j)
-                    if ((heads8 >> j) & 1u) h = c[j];
+                    if ((heads >> j) & 1u) h = c[j];
                 s_xy[(CPL + 1) * lane + CPL] = h;  // (my scratch slot)
             }
             rs_wave_fence();
             if (head_lanes & below) first = s_xy[(CPL + 1) * (63 - __clzll(head_lanes & below)) + CPL];
             if (head_lanes) first_carry = s_xy[(CPL + 1) * (63 - __clzll(head_lanes)) + CPL];
         }
-        // my 8 coordinates in order.  The area terms are geo's (twice_signed_ring_area shifts every coordinate by the ring's first one): the same
+        // my CPL coordinates in order.  The area terms are geo's (twice_signed_ring_area shifts every coordinate by the ring's first one): the same
         // products bit for bit, only the order of the sum differs — a ring whose terms are all exactly 0 (collinear) has area exactly 0.
         // e = my coordinate minus ITS ring's first coordinate; an edge's far end belongs to another ring only when the edge is dropped anyway.
         RsVal<OP> acc = rs_identity<OP>();
@@ -308,40 +260,33 @@ __global__ __launch_bounds__(64 * RS_WAVES) void ring_stream_kernel(DevGeo a, co
         for (int j = 0; j < CPL; ++j) {
             if ((hb >> j) & 1u) ++lid;
             bool closed_j = true;  // (area: my coordinate j is its ring's first coordinate again — e, its offset from it, is exactly 0)
-            if constexpr (OP == RS_BOUNDS) {
-                if ((live8 >> j) & 1u) {
-                    acc.v[0] = c[j].x < acc.v[0] ? c[j].x : acc.v[0];
-                    acc.v[1] = c[j].y < acc.v[1] ? c[j].y : acc.v[1];
-                    acc.v[2] = c[j].x > acc.v[2] ? c[j].x : acc.v[2];
-                    acc.v[3] = c[j].y > acc.v[3] ? c[j].y : acc.v[3];
-                }
-            } else if constexpr (OP == RS_LENGTH) {
+            if constexpr (OP == RS_LENGTH) {
                 const double l = hypot(c[j + 1].x - c[j].x, c[j + 1].y - c[j].y);
-                acc.v[0] += ((drop8 >> j) & 1u) ? 0.0 : l;
+                acc.v += ((drop >> j) & 1u) ? 0.0 : l;
             } else {
                 closed_j = e.x == 0.0 && e.y == 0.0;
                 if ((hb >> (j + 1)) & 1u) first = c[j + 1];
                 const double2 en = make_double2(c[j + 1].x - first.x, c[j + 1].y - first.y);
                 const double cr = e.x * en.y - e.y * en.x;
-                acc.v[0] += ((drop8 >> j) & 1u) ? 0.0 : cr;
+                acc.v += ((drop >> j) & 1u) ? 0.0 : cr;
                 e = en;
             }
-            if ((tails8 >> j) & 1u) {
+            if ((tails >> j) & 1u) {
                 flush();
                 if (AREA && !closed_j) atomicOr(&s_open[lid >> 5], 1u << (lid & 31));  // not closed: its area is 0 (area.rs)
                 acc = rs_identity<OP>();
             }
         }
-        if (!((tails8 >> (CPL - 1)) & 1u) && ((live8 >> (CPL - 1)) & 1u)) flush();  // the run still open at my last coordinate: its ring goes on in the next lane
+        if (!((tails >> (CPL - 1)) & 1u) && ((live >> (CPL - 1)) & 1u)) flush();  // the run still open at my last coordinate: its ring goes on in the next lane
         rs_wave_fence();  // (the next block overwrites s_xy)
     }
     rs_wave_fence();
     const int lid_end = (int)s_wpre[RS_STRIP / 32];  // rings begun in the strip (the bit of the coordinate after the strip is in the next word: not counted)
-    // what the strip leaves for rings that cross its boundaries: [0, K) the sum from its start to the first ring end (the whole strip when no
-    // ring ends in it), [K, 2K) the sum after its last ring end (the same whole when none)
-    if (lane < K) {
-        strip_part[(strip * 2) * K + lane] = s_val[lane];
-        strip_part[(strip * 2 + 1) * K + lane] = s_val[lid_end * K + lane];
+    // what the strip leaves for rings that cross its boundaries: [0] the sum from its start to the first ring end (the whole strip when no
+    // ring ends in it), [1] the sum after its last ring end (the same whole when none)
+    if (lane < 1) {
+        strip_part[strip * 2 + lane] = s_val[lane];
+        strip_part[strip * 2 + 1 + lane] = s_val[lid_end + lane];
     }
 
     // ---- the geometries that began in this strip ----
@@ -350,15 +295,12 @@ __global__ __launch_bounds__(64 * RS_WAVES) void ring_stream_kernel(DevGeo a, co
     auto val = [&](int r) {
         const int l = r - s_lo + 1;
         RsVal<OP> v;
-#pragma unroll
-        for (int k = 0; k < K; ++k) v.v[k] = s_val[l * K + k];
-        if (AREA && ((s_open[l >> 5] >> (l & 31)) & 1u)) v.v[0] = 0.0;
+        v.v = s_val[l];
+        if (AREA && ((s_open[l >> 5] >> (l & 31)) & 1u)) v.v = 0.0;
         return v;
     };
     auto spill = [&](int r) {
-        const RsVal<OP> v = val(r);
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring_vals[(int64_t)r * K + k] = v.v[k];
+        ring_vals[r] = val(r).v;
     };
     {  // complete rings of the geometry that entered the strip: gpk_ring_stream_fix folds that geometry
         int r_in, r_unused;
@@ -432,7 +374,6 @@ template <int OP>
 __global__ __launch_bounds__(256) void ring_stream_fix_kernel(DevGeo a, const RsCross* __restrict__ cross, const RsDesc* __restrict__ desc, int64_t n_strips,
                                                               const double* __restrict__ ring_vals, const double* __restrict__ strip_part,
                                                               double* __restrict__ out) {
-    constexpr int K = rs_k<OP>();
     const int64_t strip = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (strip >= n_strips) return;
     const int4 hv = reinterpret_cast<const int4*>(cross)[strip];
@@ -443,19 +384,15 @@ __global__ __launch_bounds__(256) void ring_stream_fix_kernel(DevGeo a, const Rs
         const int64_t sa = d.y / RS_STRIP, sb = (d.z - 1) / RS_STRIP;
         RsVal<OP> v;
         if (sa == sb) {  // complete in one strip: that strip's wave left its value
-#pragma unroll
-            for (int k = 0; k < K; ++k) v.v[k] = ring_vals[(int64_t)d.x * K + k];
+            v.v = ring_vals[d.x];
             return v;
         }
         const double2 first = a.xy[d.y], last = a.xy[d.z - 1];  // (requested before the sums: one more round trip otherwise)
-#pragma unroll
-        for (int k = 0; k < K; ++k) v.v[k] = strip_part[(sa * 2 + 1) * K + k];
+        v.v = strip_part[sa * 2 + 1];
         for (int64_t t = sa + 1; t <= sb; t += 8) {  // (a ring of 100 000 coordinates: a hundred strips — eight reads in flight, folded in strip order)
             RsVal<OP> p[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int k = 0; k < K; ++k) p[u].v[k] = t + u <= sb ? strip_part[((t + u) * 2) * K + k] : rs_identity<OP>().v[k];
+            for (int u = 0; u < 8; ++u) p[u].v = t + u <= sb ? strip_part[(t + u) * 2] : rs_identity<OP>().v;
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 if (t + u <= sb) v = rs_combine<OP>(v, p[u]);
@@ -466,44 +403,32 @@ __global__ __launch_bounds__(256) void ring_stream_fix_kernel(DevGeo a, const Rs
     // always valid), are each ONE round trip for the batch; only a ring that crosses a strip boundary (one or two a geometry) then takes its
     // own.  Record by record the fold of a multipolygon of six rings was twelve dependent round trips.
     const int4* dd = reinterpret_cast<const int4*>(desc) + hv.y;
-    RsVal<OP> b = rs_identity<OP>();
-    bool have = false;
     double v = 0.0, area = 0.0;
     bool open_part = false, neg = false;
     auto close_part = [&]() {
         const double sa = neg ? -area : area;
         v += OP == RS_SIGNED_AREA ? sa : fabs(sa);
     };
-    if (OP != RS_BOUNDS && !valid) {
+    if (!valid) {
         out[g] = NAN;
         return;
     }
-    const int n_desc = (OP == RS_BOUNDS && !valid) ? 0 : hv.z;
+    const int n_desc = hv.z;
     for (int i0 = 0; i0 < n_desc; i0 += 8) {
         int4 d[8];
         RsVal<OP> rv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) d[u] = dd[i0 + u < n_desc ? i0 + u : n_desc - 1];
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int k = 0; k < K; ++k) rv[u].v[k] = ring_vals[(int64_t)d[u].x * K + k];
+        for (int u = 0; u < 8; ++u) rv[u].v = ring_vals[d[u].x];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             if (i0 + u >= n_desc) break;
             const bool crossing = d[u].y / RS_STRIP != (d[u].z - 1) / RS_STRIP;
-            if constexpr (OP == RS_BOUNDS) {
-                if (!d[u].w) continue;  // Polygon::bounding_rect scans the exterior only
-                have = true;
-                const RsVal<OP> e = crossing ? val(d[u]) : rv[u];
-                b.v[0] = fmin(b.v[0], e.v[0]);
-                b.v[1] = fmin(b.v[1], e.v[1]);
-                b.v[2] = fmax(b.v[2], e.v[2]);
-                b.v[3] = fmax(b.v[3], e.v[3]);
-            } else if constexpr (OP == RS_LENGTH) {
-                if (d[u].w) v += (crossing ? val(d[u]) : rv[u]).v[0];  // exterior rings only
+            if constexpr (OP == RS_LENGTH) {
+                if (d[u].w) v += (crossing ? val(d[u]) : rv[u]).v;  // exterior rings only
             } else {
-                const double h = (crossing ? val(d[u]) : rv[u]).v[0] / 2.0;
+                const double h = (crossing ? val(d[u]) : rv[u]).v / 2.0;
                 if (d[u].w) {
                     if (open_part) close_part();
                     open_part = true;
@@ -515,12 +440,8 @@ __global__ __launch_bounds__(256) void ring_stream_fix_kernel(DevGeo a, const Rs
             }
         }
     }
-    if constexpr (OP == RS_BOUNDS) {
-        reinterpret_cast<double4*>(out)[g] = have ? make_double4(b.v[0], b.v[1], b.v[2], b.v[3]) : make_double4(NAN, NAN, NAN, NAN);
-    } else {
-        if (OP != RS_LENGTH && open_part) close_part();
-        out[g] = v;
-    }
+    if (OP != RS_LENGTH && open_part) close_part();
+    out[g] = v;
 }
 
 // ---- the strip table of a column (once per handle) ----
@@ -635,7 +556,6 @@ int32_t ring_stream_launch(int op, const DevGeo& a, const int32_t* ring_first, c
     case RS_AREA: return ring_stream_launch_op<RS_AREA>(a, ring_first, geom_first, cross, desc, ring_vals, strip_part, out, s, "gpk_ring_stream_area");
     case RS_SIGNED_AREA: return ring_stream_launch_op<RS_SIGNED_AREA>(a, ring_first, geom_first, cross, desc, ring_vals, strip_part, out, s, "gpk_ring_stream_area");
     case RS_LENGTH: return ring_stream_launch_op<RS_LENGTH>(a, ring_first, geom_first, cross, desc, ring_vals, strip_part, out, s, "gpk_ring_stream_length");
-    case RS_BOUNDS: return ring_stream_launch_op<RS_BOUNDS>(a, ring_first, geom_first, cross, desc, ring_vals, strip_part, out, s, "gpk_ring_stream_bounds");
     default: return fail(GPK_ERR_INVALID_ARGUMENT, "ring_stream_launch: op %d", op);
     }
 }

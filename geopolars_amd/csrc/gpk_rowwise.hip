@@ -445,7 +445,8 @@ __device__ __forceinline__ double vmin_f64(double a, double b) {  // one instruc
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-// Round 6: the step by instruction count (the kernel is bound by f64 issue: 0.59 of the issue rate, PMC).  What does not depend on the
+// Round 6: the step by instruction count (the kernel is bound by its permuted point gathers and result scatters, not by f64 issue:
+// DESIGN.md section 4.3 "Round 6").  What does not depend on the
 // point — the reciprocal of the segment's squared length — is computed ONCE per staged window by the lane that copied the vertex and
 // read back from LDS with it; the distance to a segment is the distance to the clamped projection a + clamp(q.d / d.d, 0, 1) d, whose
 // end points ARE the vertices (no separate vertex minimum, no cross-multiplied fraction compare): 12 vector instructions a segment
@@ -471,13 +472,7 @@ __device__ __forceinline__ void seg_step(SegState& st, double2 b, double inv_d2,
 constexpr int DC_K = 31;      // segments per staged window of one linestring (32 vertices)
 constexpr int DC_SLOT = 33;   // LDS stride of a staged window in vertices (odd: windows of different targets sit on different banks)
 constexpr int DC_MAXD = 8;    // targets staged at once per wave (a chunk with more distinct targets goes in several groups)
-#ifndef GPK_DIST_ABLATE
-#define GPK_DIST_ABLATE 0  // tuning builds only (answers wrong on purpose): 1 = points read and results written in map order (no gather, no scatter)
-#endif
-#ifndef GPK_DIST_ROWS
-#define GPK_DIST_ROWS 1  // (2: measured 3 % slower on C3 — 122 registers halve the occupancy)
-#endif
-constexpr int DC_R = GPK_DIST_ROWS;       // rows per lane: a wave's chunk is 128 ordered rows (lane l holds rows l and 64 + l of it)
+constexpr int DC_R = 1;       // rows per lane (2: measured 3 % slower on C3 — 122 registers halve the occupancy)
 // what does not depend on the point, once per linestring column (kept with the row map): the reciprocal of every segment's squared
 // length (0 for a zero-length one, and for the last vertex of the array) and every linestring's longest squared segment
 __global__ __launch_bounds__(256) void seg_inv_kernel(const double2* __restrict__ xy, int64_t n_coords, double* __restrict__ inv) {
@@ -539,7 +534,7 @@ __global__ __launch_bounds__(256) void distance_grouped_kernel(DevGeo pts, DevGe
             t[r] = active[r] ? tsorted[pos] : 0xFFFFFFFFu;
             i[r] = active[r] ? perm[pos] : 0u;
             p[r] = make_double2(NAN, NAN);
-            if (active[r] && dev::valid_row(pts.validity, i[r])) p[r] = pts.xy[GPK_DIST_ABLATE ? (uint32_t)pos : i[r]];
+            if (active[r] && dev::valid_row(pts.validity, i[r])) p[r] = pts.xy[i[r]];
             c0[r] = nv[r] = 0;
             mx[r] = 0.0;
             if (active[r]) {
@@ -660,7 +655,7 @@ __global__ __launch_bounds__(256) void distance_grouped_kernel(DevGeo pts, DevGe
                     d = 0.0;
                 else
                     d = best[r] == INFINITY ? DBL_MAX : sqrt(best[r]);
-                out[GPK_DIST_ABLATE ? (uint32_t)(ch * CHUNK + r * 64 + lane) : i[r]] = d;
+                out[i[r]] = d;
             }
         }
     }

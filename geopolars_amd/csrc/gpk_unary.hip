@@ -1278,15 +1278,6 @@ extern "C" {
 static bool ring_stream_ok(const gpk_geoarray* a, const UnaryCtx& c) {
     return is_polygonal(a->d.type) && c.classes && c.classes->strips_ok && c.strip_part;
 }
-// bounds (four running values a coordinate, four LDS updates a flush) is measured slower in the one-pass form on every test column
-// (2M x 64: 0.73 against 0.44 ms; power-law: 0.23 against 0.19): it stays on the two-stage form unless GPK_RING_STREAM_BOUNDS=1 (A/B runs)
-static bool ring_stream_bounds_on() {
-    static const bool on = [] {
-        const char* e = getenv("GPK_RING_STREAM_BOUNDS");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
 static int32_t ring_stream_run(int op, const gpk_geoarray* a, const UnaryCtx& c, hipStream_t s) {
     const int64_t n_strips = ring_stream_strips(a->d.n_coords);
     return ring_stream_launch(op, a->d, c.classes->strip_first, c.classes->strip_first + n_strips + 1, c.classes->strip_cross, c.classes->strip_desc, c.stats,
@@ -1382,9 +1373,7 @@ int32_t gpk_bounds(const gpk_geoarray* a, double* out4, int32_t out_space, void*
     if (n == 0) return GPK_OK;
     if (a->d.type == GPK_GEOM_POINT) {
         GPK_LAUNCH("gpk_point_unary", point_unary_kernel, grid_for(n), dim3(256), 0, s, a->d, 2, (double*)c.out_dev, (uint8_t*)nullptr);
-    } else if (ring_stream_ok(a, c) && ring_stream_bounds_on()) {
-        GPK_TRY(ring_stream_run(RS_BOUNDS, a, c, s));
-    } else {
+    } else {  // (two-stage on every column: a one-pass bounds was measured slower on each)
         const gpk_seq_classes* cl;
         GPK_TRY(seq_classes_of(a, s, &cl));
         if (cl->one_to_one) {  // stage 1 writes the boxes, no combine pass

@@ -6,15 +6,13 @@
 //   sizes   : one lane per row -> bytes of its record (closed form from the offsets);
 //   scan    : exclusive scan -> Arrow i32 offsets;
 //   headers : one lane per row writes the geometry header (and the member headers of multi types);
-//   bodies  : 8 lanes per ring / linestring write `count` + coordinates (16-byte unaligned stores).
+//   bodies  : a work-group per WKB_EB_TILE consecutive input coordinates writes them (16-byte unaligned stores).
 // A record's bytes depend only on the row's own offsets, so every stage is a map; HBM-bound
 // (16 B read + 16 B written per coordinate).
 #include "gpk_device.h"
 #include "gpk_scan.h"
 
 namespace gpk {
-
-constexpr int WKB_GS = 8;  // lanes per ring / linestring in the body kernel
 
 __device__ __forceinline__ void put_u32(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 __device__ __forceinline__ void put_xy(uint8_t* p, double2 v) { __builtin_memcpy(p, &v, 16); }
@@ -136,42 +134,7 @@ __device__ __forceinline__ int owner_of(const int32_t* __restrict__ off, int64_t
     return (int)lo;
 }
 
-// bodies: WKB_GS lanes per sequence (a ring / member line, or the row of a LINESTRING column) copy its coordinates to
-// out + seq_dst[q]; sequences longer than WKB_ENC_LONG are listed for wkb_bodies_long_kernel, which spreads each of them
-// over the whole grid (a 100k-vertex ring would otherwise be 8 lanes' job)
-constexpr int WKB_ENC_LONG = 4096;
-__global__ __launch_bounds__(256) void wkb_bodies_kernel(DevGeo a, const int32_t* __restrict__ seq_dst, uint8_t* __restrict__ out,
-                                                          int32_t* __restrict__ long_list) {
-    const int lane = threadIdx.x & (WKB_GS - 1);
-    const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WKB_GS;
-    const bool rows = a.type == GPK_GEOM_LINESTRING;
-    const int64_t n_seq = rows ? a.n_geoms : a.n_rings;
-    if (q >= n_seq) return;
-    const int32_t dst = seq_dst[q];
-    if (dst < 0) return;
-    const int32_t* so = rows ? a.geom_off : a.ring_off;
-    const int c0 = so[q], c1 = so[q + 1];
-    if (c1 - c0 > WKB_ENC_LONG) {
-        if (lane == 0) long_list[1 + atomicAdd(&long_list[0], 1)] = (int32_t)q;
-        return;
-    }
-    uint8_t* p = out + dst;
-    for (int i = c0 + lane; i < c1; i += WKB_GS) put_xy(p + 16 * (int64_t)(i - c0), a.xy[i]);
-}
-__global__ __launch_bounds__(256) void wkb_bodies_long_kernel(DevGeo a, const int32_t* __restrict__ seq_dst, uint8_t* __restrict__ out,
-                                                               const int32_t* __restrict__ long_list) {
-    const int n_long = long_list[0];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-    const int32_t* so = a.type == GPK_GEOM_LINESTRING ? a.geom_off : a.ring_off;
-    for (int k = 0; k < n_long; ++k) {
-        const int q = long_list[1 + k];
-        const int c0 = so[q], c1 = so[q + 1];
-        uint8_t* p = out + seq_dst[q];
-        for (int64_t i = c0 + tid; i < c1; i += stride) put_xy(p + 16 * (i - c0), a.xy[i]);
-    }
-}
-
-// The same bodies cut by INPUT coordinate (the decoder's wkb_copy_kernel in reverse): a work-group owns WKB_EB_TILE consecutive
+// bodies: cut by INPUT coordinate (the decoder's wkb_copy_kernel in reverse): a work-group owns WKB_EB_TILE consecutive
 // coordinates of the column whatever sequences they belong to — a power-law column keeps half of its coordinates in rings of at most
 // 16 and a few in rings of 100k, and eight lanes per ring serve neither.  The offsets of the sequences that meet the tile and their
 // destinations are staged in LDS; a lane finds the sequence of each of its coordinates there (a null row's sequences have no
@@ -269,14 +232,13 @@ extern "C" int32_t gpk_geoarray_to_wkb(const gpk_geoarray* a, int32_t* out_offse
     const int64_t nb = (n + 255) / 256;
     const int64_t n_seq_enc = d.type == GPK_GEOM_LINESTRING ? n : d.n_rings;
     size_t need = 2 * align256(sizeof(int32_t) * (size_t)(n + 1)) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) +
-                  2 * align256(sizeof(int32_t) * (size_t)(n_seq_enc + 2)) + 1024;
+                  align256(sizeof(int32_t) * (size_t)(n_seq_enc + 2)) + 1024;
     if (host_out && out_values) need += align256((size_t)capacity);
     GPK_TRY(workspace().begin(need));
     int32_t* sizes = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
     int32_t* off_dev = (host_out || !out_offsets) ? (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1)) : out_offsets;
     unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
     uint8_t* val_dev = out_values ? (host_out ? (uint8_t*)workspace().take((size_t)capacity) : out_values) : nullptr;
-    int32_t* long_list = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_seq_enc + 2));
     int32_t* seq_dst = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_seq_enc + 2));
 
     int32_t total = 0;
@@ -300,21 +262,12 @@ extern "C" int32_t gpk_geoarray_to_wkb(const gpk_geoarray* a, int32_t* out_offse
                 GPK_LAUNCH("gpk_wkb_multipoint", wkb_multipoint_kernel, dim3((unsigned)((d.n_coords + 255) / 256)), dim3(256), 0, s, d,
                            (const int32_t*)off_dev, val_dev);
         } else if (d.type != GPK_GEOM_POINT) {
-            const int64_t n_seq = n_seq_enc;
-            // the bodies are cut by coordinate (2M x 64-vertex polygons 1.41 -> 0.98 ms, 1M power-law multipolygons 0.67 -> 0.42 ms, 8M x 8
-            // 1.25 -> 1.28 ms); GPK_WKB_ENC_GROUPS=1: the round-3 form, eight lanes per sequence (A/B runs)
-            static const bool force_groups = getenv("GPK_WKB_ENC_GROUPS") != nullptr;
-            const bool flat = !force_groups && n_seq > 0 && d.n_coords > 0;
-            if (flat) {
+            // the bodies are cut by coordinate (against eight lanes per sequence: 2M x 64-vertex polygons 1.41 -> 0.98 ms, 1M power-law
+            // multipolygons 0.67 -> 0.42 ms, 8M x 8 1.25 -> 1.28 ms); sequences without coordinates have nothing to copy (the headers
+            // kernel writes their counts)
+            if (n_seq_enc > 0 && d.n_coords > 0)
                 GPK_LAUNCH("gpk_wkb_bodies", wkb_bodies_flat_kernel, dim3((unsigned)((d.n_coords + WKB_EB_TILE - 1) / WKB_EB_TILE)), dim3(WKB_EB_BLOCK), 0, s, d,
                            (const int32_t*)seq_dst, val_dev);
-            } else if (n_seq > 0) {
-                GPK_HIP(hipMemsetAsync(long_list, 0, sizeof(int32_t), s));
-                GPK_LAUNCH("gpk_wkb_bodies", wkb_bodies_kernel, dim3((unsigned)((n_seq * WKB_GS + 255) / 256)), dim3(256), 0, s, d,
-                           (const int32_t*)seq_dst, val_dev, long_list);
-                GPK_LAUNCH("gpk_wkb_bodies_long", wkb_bodies_long_kernel, dim3((unsigned)(cu_count() * 8)), dim3(256), 0, s, d,
-                           (const int32_t*)seq_dst, val_dev, (const int32_t*)long_list);
-            }
         }
     }
     if (host_out) GPK_TRY(copy_out(out_values, out_space, val_dev, (size_t)total, s));

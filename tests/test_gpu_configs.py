@@ -48,8 +48,8 @@ def test_c2_scale_sampled(gpk, oracle):
 
 
 def test_c2_scale_general_kernel_equals_lean(gpk, oracle):
-    """the same join through the general tile kernel (GPK_NO_LEAN is read once per process: use a right side the lean
-    kernel does not take — two overlapping copies of the polygons) equals the union of the single-copy answers"""
+    """the same join through the general tile kernel (a right side the lean kernel does not take — two overlapping copies
+    of the polygons) equals the union of the single-copy answers"""
     polys = synth.star_polygons(400, 32)
     both = GeoArrowArray.concat([polys, polys])
     pts = synth.uniform_points(1_000_000, seed=102)

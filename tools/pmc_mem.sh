@@ -1,4 +1,4 @@
-# PMC passes (memory side + instruction mix) over tools/tile_time.py:  bash tools/pmc_mem.sh <tag>   (GPK_FUSED_FORM / GPK_LIB_PATH from the environment)
+# PMC passes (memory side + instruction mix) over tools/tile_time.py:  bash tools/pmc_mem.sh <tag>   (GPK_LIB_PATH from the environment)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=$1; OUT=$R/gpurun_out/pmcm_$TAG; mkdir -p $OUT
 CMD="python $R/tools/tile_time.py --steps 6"

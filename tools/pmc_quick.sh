@@ -1,4 +1,4 @@
-# two PMC passes (instruction mix, waits) over tools/tile_time.py:  bash tools/pmc_quick.sh <tag>   (GPK_FUSED_FORM / GPK_LIB_PATH from the environment)
+# two PMC passes (instruction mix, waits) over tools/tile_time.py:  bash tools/pmc_quick.sh <tag>   (GPK_LIB_PATH from the environment)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=$1; OUT=$R/gpurun_out/pmcq_$TAG; mkdir -p $OUT
 CMD="python $R/tools/tile_time.py --steps 6"

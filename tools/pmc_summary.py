@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise tools/pmc_ablate.sh output: per-wave means of every counter for kernels matching a name."""
+"""Summarise rocprofv3 counter output, one subdirectory per variant: per-wave means of every counter for kernels matching a name."""
 import csv, collections, glob, sys
 root, pat = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else "pip_tile")
 for vdir in sorted(glob.glob(root + "/*/")):

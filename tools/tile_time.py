@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Tuning: HIP-event time of the kernels of the C2 join (gpk_join_prep / gpk_pip_tile / gpk_pip_write) on cold rotating inputs,
 plus the wall time of a queued step, for the build named by GPK_LIB_PATH (default: the in-tree library).  No parity, no bench line
-(bench.py is the measurement of record); environment switches of the library apply (GPK_NO_CHAINS=1: queue kernel on an index
-without chains, GPK_TILE_KERNEL=chain: the chain kernel instead of the routed one serves an index with chains).
+(bench.py is the measurement of record); environment switches of the library apply (GPK_TILE_KERNEL=chain: the chain kernel instead of the routed one serves an
+index with chains).
     GPK_LIB_PATH=geopolars_amd/variants/r2.so python tools/tile_time.py [--polys 1000] [--points 10000000]"""
 import argparse, ctypes as C, os, sys, time
 import torch
