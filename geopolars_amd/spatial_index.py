@@ -3,6 +3,7 @@
     SpatialJoinArgs         spatial_index.rs:15-35   (join_type, predicate, suffixes, prebuilt indexes)
     SpatialIndex            spatial_index.rs:314-350 (TryFrom<&Series>)
     spatial_join            spatial_index.rs:37-204
+    spatial_join_nearest    GeoPandas' sjoin_nearest (not in the reference): every point with the nearest geometries of another table
 
 The candidate generation + exact refine (spatial_index.rs:74-143) run on the GPU through
 gpk_spatial_join; this module only marshals buffers and — for dataframe-shaped callers — assembles
@@ -278,6 +279,16 @@ def _geometry_type_of(table, hint: int, hint_name: str) -> int:
     return -1
 
 
+def _as_wkb(column, geo: GeoSeries):
+    """a native GeoArrow geometry column leaves a join the way the reference's geometry columns are held — WKB binary
+    (from_geom_vec, util.rs:11-24) — encoded on the GPU from the series the join already uploaded"""
+    import pyarrow as pa
+
+    if pa.types.is_binary(column.type) or pa.types.is_large_binary(column.type):
+        return column
+    return geo.device().to_arrow("wkb")  # (gpk_geoarray_to_arrow: the library's buffers, validity included, released by pyarrow)
+
+
 def spatial_join(lhs, rhs, options: Optional[SpatialJoinArgs] = None):
     """spatial_join(lhs, rhs, SpatialJoinArgs) over pyarrow Tables with a `geometry` column (spatial_index.rs:44-45) — WKB binary as the
     reference holds it, or a native GeoArrow nesting.  Returns a pyarrow Table shaped like the reference's result: suffixed left columns,
@@ -295,18 +306,147 @@ def spatial_join(lhs, rhs, options: Optional[SpatialJoinArgs] = None):
     r_index = options.r_index or SpatialIndex(rgeo)
     pairs, counts = join_pairs(lgeo, rgeo, options.predicate, r_index)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    def as_wkb(column, geo: GeoSeries):
-        """a native GeoArrow geometry column leaves the join the way the reference's geometry columns are held — WKB binary
-        (from_geom_vec, util.rs:11-24) — encoded on the GPU from the series the join already uploaded"""
-        if pa.types.is_binary(column.type) or pa.types.is_large_binary(column.type):
-            return column
-        return geo.device().to_arrow("wkb")  # (gpk_geoarray_to_arrow: the library's buffers, validity included, released by pyarrow)
-
     cols, names = [], []
     for name in lhs.column_names:
-        cols.append(take_column(as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
+        cols.append(take_column(_as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
         names.append(name + (options.l_suffix or ""))
     for name in rhs.column_names:
-        cols.append(take_column(as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
+        cols.append(take_column(_as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
         names.append(name + (options.r_suffix or ""))
+    return pa.table(cols, names=names)
+
+
+# ---- nearest-neighbour join (gpk_nearest_join) ----------------------------------------------------------------------------------
+
+
+@dataclass
+class SpatialJoinNearestArgs:
+    """Options of spatial_join_nearest (GeoPandas' sjoin_nearest over this module's table shape)."""
+
+    join_type: str = "inner"  # "inner" | "left" (unmatched left rows once, with nulls on the right)
+    max_distance: Optional[float] = None  # None: no limit; else only pairs with distance <= max_distance
+    distance_col: Optional[str] = None  # name of a float64 column with each pair's distance (null for unmatched left rows)
+    l_suffix: Optional[str] = "_left"
+    r_suffix: Optional[str] = "_right"
+    r_index: Optional[SpatialIndex] = None
+    l_geom_type: int = -1  # as in SpatialJoinArgs
+    r_geom_type: int = -1
+
+
+def _max_distance_arg(max_distance: Optional[float]) -> float:
+    """None -> INFINITY; a negative or NaN bound is refused here, before any device call"""
+    if max_distance is None:
+        return float("inf")
+    d = float(max_distance)
+    if not d >= 0.0:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"nearest join: max_distance must be >= 0 (None: no limit), got {max_distance!r}")
+    return d
+
+
+def _require_point_series(left: GeoSeries) -> None:
+    """the left side of a nearest join holds points (checked on the series' own buffers: nothing is uploaded for it)"""
+    t = left._array.geom_type if left._array is not None else left._dev.geom_type
+    if t != _abi.GEOM_POINT:
+        raise _abi.MismatchedGeometry(_abi.GPK_ERR_MISMATCHED_GEOMETRY, f"nearest join: the left side must be POINT (found type {t})")
+
+
+def nearest_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    r_index: Optional[SpatialIndex] = None,
+    max_distance: Optional[float] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """For every point of `left`, the rows of `right` at the smallest distance (ties all returned; within max_distance when given):
+    (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32, distances (H,) float64).  Host-buffer variant: the pair buffer
+    is sized like join_pairs'."""
+    md = _max_distance_arg(max_distance)
+    _require_point_series(left)
+    lib = _abi.lib()
+    n = len(left)
+    counts = np.empty(n, dtype=np.uint32)
+    n_pairs = C.c_int64(0)
+    rh = r_index.handle if r_index is not None else None
+    capacity = max(1024, 4 * n)
+    while True:
+        pairs = np.empty((capacity, 2), dtype=np.uint32)
+        dist = np.empty(capacity, dtype=np.float64)
+        rc = lib.gpk_nearest_join(
+            left.device().handle, right.device().handle, rh, md, left_row_base, counts.ctypes.data, pairs.ctypes.data, dist.ctypes.data, capacity,
+            C.byref(n_pairs), MEM_HOST, None
+        )
+        if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
+            capacity = int(n_pairs.value)
+            continue
+        _abi.check(rc)
+        h = int(n_pairs.value)
+        return pairs[:h].copy(), counts, dist[:h].copy()
+
+
+def nearest_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    out_counts,
+    out_pairs,
+    out_dist=None,
+    max_distance: Optional[float] = None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_dist (cap,) float64 torch CUDA tensors (any
+    may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
+    md = _max_distance_arg(max_distance)
+    if left.geom_type != _abi.GEOM_POINT:
+        raise _abi.MismatchedGeometry(_abi.GPK_ERR_MISMATCHED_GEOMETRY, f"nearest join: the left side must be POINT (found type {left.geom_type})")
+    n_pairs = C.c_int64(0)
+    _abi.check(
+        _abi.lib().gpk_nearest_join(
+            left.handle,
+            right.handle,
+            r_index.handle if r_index is not None else None,
+            md,
+            left_row_base,
+            out_counts.data_ptr() if out_counts is not None else None,
+            out_pairs.data_ptr() if out_pairs is not None else None,
+            out_dist.data_ptr() if out_dist is not None else None,
+            out_pairs.shape[0] if out_pairs is not None else 0,
+            C.byref(n_pairs),
+            MEM_DEVICE,
+            stream,
+        )
+    )
+    return int(n_pairs.value)
+
+
+def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = None):
+    """GeoPandas' sjoin_nearest over pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes them): every
+    left point with every right geometry at its smallest distance (ties all kept), shaped like spatial_join's result — suffixed left
+    columns, suffixed right columns, then `distance_col` when asked for.  The left geometry column must hold points."""
+    import pyarrow as pa
+
+    options = options or SpatialJoinNearestArgs()
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"nearest join: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    md = _max_distance_arg(options.max_distance)
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    _require_point_series(lgeo)
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, dist = nearest_pairs(lgeo, rgeo, options.r_index, md)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    cols, names = [], []
+    for name in lhs.column_names:
+        cols.append(take_column(_as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
+        names.append(name + (options.l_suffix or ""))
+    for name in rhs.column_names:
+        cols.append(take_column(_as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
+        names.append(name + (options.r_suffix or ""))
+    if options.distance_col is not None:
+        # join_indices keeps the pairs' order and puts an unmatched left row (r = -1) where its pairs would be: pair k of the sorted
+        # output is joined row k among the rows with r >= 0
+        matched = ri >= 0
+        d = np.zeros(len(ri), dtype=np.float64)
+        d[matched] = dist
+        cols.append(pa.array(d, type=pa.float64(), mask=~matched))
+        names.append(options.distance_col)
     return pa.table(cols, names=names)

@@ -420,6 +420,29 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right,
                          int64_t* n_pairs, int32_t out_space, void* stream);
 
 /*
+ * Nearest-neighbour join (GeoPandas sjoin_nearest): for every left row l, every right row r whose distance equals the row's minimum
+ * distance EXACTLY, in the kernel's own f64 arithmetic — ties are all returned.  Left: POINT.  Right: POINT, MULTIPOINT, LINESTRING,
+ * MULTILINESTRING, POLYGON or MULTIPOLYGON (anything else: GPK_ERR_MISMATCHED_GEOMETRY).
+ *   distance(l, r)       geo's Euclidean distance as gpk_distance_rowwise defines it (0 for a point inside or on a polygon); every
+ *                        returned distance is bit for bit what gpk_distance_rowwise's per-row kernel returns for the pair (its grouped
+ *                        schedule for LINESTRING right sides with >= 8 rows per target agrees within its 1e-9 contract)
+ *   max_distance         only pairs with d <= max_distance (closed); INFINITY = no limit; negative or NaN: GPK_ERR_INVALID_ARGUMENT
+ *   never matched        null or empty left rows, left points with a NaN coordinate: count 0
+ *   never candidates     null and empty right rows (they have no leaf in the index) — unlike row-wise distance, which gives 0.0 for an
+ *                        empty linestring.  An empty right side, or one of null / empty rows only, gives no pairs.
+ *   out_counts[n_left]   u32 matches per left row (may be NULL)
+ *   out_pairs[2*cap]     u32 (l, r) interleaved, sorted by (l, r) (NULL with cap == 0: count-only mode)
+ *   out_dist[cap]        f64 distance of each pair (may be NULL)
+ *   *n_pairs             total, always set; GPK_ERR_CAPACITY when > cap and pairs were asked for
+ * `left_row_base` is added to every emitted l.  All buffers live in `out_space`.  `right_index`: an index of `right` carrying the bbox
+ * grid (else GPK_ERR_INVALID_ARGUMENT), or NULL: a GPK_INDEX_BBOX_GRID index is built for the call and freed (it is not kept on the
+ * handle).  Synchronous, like gpk_spatial_join.
+ */
+int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, double max_distance,
+                         uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_dist, int64_t pair_capacity,
+                         int64_t* n_pairs, int32_t out_space, void* stream);
+
+/*
  * Stream-ordered form of gpk_spatial_join for callers that keep everything in HBM (the idiom a pipeline of
  * kernels on one HIP stream wants; the reference's call is synchronous, spatial_index.rs:44-58): the join is
  * ENQUEUED on `stream` and the call returns without waiting.
