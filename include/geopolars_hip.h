@@ -325,6 +325,13 @@ int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_t* out_ring
  * LINESTRING, POLYGON, MULTIPOLYGON, MULTILINESTRING, MULTIPOINT} and the mirrored pairs. */
 int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows,
                              double* out, int32_t out_space, void* stream);
+/* Magnitude range of gpk_distance_rowwise and gpk_nearest_join.  The kernels compare squared point-segment distances as
+ * fractions by cross-multiplication (gpk_distance.h segment_dist2 / frac_less): the products grow as the sixth power of the
+ * coordinate differences.  Measured on MI355X by scaling georeferenced columns (Web Mercator coordinates ~2^24, features of
+ * 0.5 - 50 m, points from 1 ulp to 3 m off an edge) by 2^k: both return exactly 2^k times the unscaled answer (and the same
+ * pairs) for |k| <= 166 and depart at |k| = 168, i.e. at coordinates near 2^192 (6e57) or 2^-144 (5e-44).  Supported:
+ * coordinates and coordinate differences within 2^-120 .. 2^120 (1e-36 .. 1e36) in magnitude; tests/test_gpu_georeferenced.py
+ * holds |k| <= 100 of the same columns to exact scaling. */
 /* A row map that is used more than once (a dataframe's foreign-key column joined against the same geometry column for
  * every batch of points) can be prepared ONCE: gpk_rowmap_build orders the left rows by target (targets by descending
  * vertex count, so that the 64 rows one wave takes walk equally long linestrings) and keeps the order in HBM;
@@ -434,6 +441,7 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right,
  *   out_pairs[2*cap]     u32 (l, r) interleaved, sorted by (l, r) (NULL with cap == 0: count-only mode)
  *   out_dist[cap]        f64 distance of each pair (may be NULL)
  *   *n_pairs             total, always set; GPK_ERR_CAPACITY when > cap and pairs were asked for
+ * Magnitude range: as gpk_distance_rowwise (exact for coordinates within 2^-120 .. 2^120).
  * `left_row_base` is added to every emitted l.  All buffers live in `out_space`.  `right_index`: an index of `right` carrying the bbox
  * grid (else GPK_ERR_INVALID_ARGUMENT), or NULL: a GPK_INDEX_BBOX_GRID index is built for the call and freed (it is not kept on the
  * handle).  Synchronous, like gpk_spatial_join.
