@@ -735,3 +735,363 @@ def canon(ring):
     if len(ring) == 0:
         return ring
     return np.roll(ring, -np.lexsort((ring[:, 1], ring[:, 0]))[0], axis=0)
+
+
+# ---- point -> geometry distance for every right family (row-wise distance and the nearest join) ---------------------------------
+#
+# A column is described on the host as (kind, rows, validity): rows[i] is a POINT (x, y) (None: empty), a MULTIPOINT's list of
+# points, a LINESTRING's list of coordinates, a MULTILINESTRING's list of linestrings, a POLYGON's list of closed rings (exterior
+# first) or a MULTIPOLYGON's list of polygons.  Null rows keep their coordinates (the index lists them; the kernels must skip them).
+
+POLYGONAL = (_abi.GEOM_POLYGON, _abi.GEOM_MULTIPOLYGON)
+FAMILIES = {
+    "point": _abi.GEOM_POINT,
+    "multipoint": _abi.GEOM_MULTIPOINT,
+    "linestring": _abi.GEOM_LINESTRING,
+    "multilinestring": _abi.GEOM_MULTILINESTRING,
+    "polygon": _abi.GEOM_POLYGON,
+    "multipolygon": _abi.GEOM_MULTIPOLYGON,
+}
+DBL_MAX = float(np.finfo(np.float64).max)
+# what geo's distance gives for an empty right row: an empty LINESTRING / POLYGON is at 0, an empty multi-geometry folds its
+# (no) parts from f64::MAX; an empty POINT (NaN coordinates) gives NaN
+EMPTY_DISTANCE = {_abi.GEOM_POINT: float("nan"), _abi.GEOM_MULTIPOINT: DBL_MAX, _abi.GEOM_LINESTRING: 0.0,
+                  _abi.GEOM_MULTILINESTRING: DBL_MAX, _abi.GEOM_POLYGON: 0.0, _abi.GEOM_MULTIPOLYGON: DBL_MAX}
+
+
+def distance_group_size(kind: int, n_coords: int, n_geoms: int) -> int:
+    """lanes per row of gpk_distance_rowwise's per-row kernel and of gpk_nearest_join, restated from gpk_distance.h
+    (pick_group_rows / distance_group_size): about 8 segments per lane from the column's mean vertex count (empty and null rows
+    count), rounded to the instantiated sizes 1 / 8 / 32 — 1 below a mean of 16, 8 from 16 to 127, 32 from 128 up; POINT: 1"""
+    if kind == _abi.GEOM_POINT:
+        return 1
+    mean = n_coords / n_geoms if n_geoms > 0 else 1.0
+    G = 1
+    while G < 64 and G * 2 * 8 <= mean:
+        G <<= 1
+    return 1 if G <= 1 else (8 if G <= 8 else 32)
+
+
+def group_size_of(a: GeoArrowArray) -> int:
+    return distance_group_size(a.geom_type, a.n_coords, a.n_geoms)
+
+
+def column(kind: int, rows, validity=None) -> GeoArrowArray:
+    """(kind, rows, validity) -> GeoArrowArray (rings taken as they are)"""
+    bits = None if validity is None else np.packbits(np.asarray(validity, dtype=bool), bitorder="little")
+    if kind == _abi.GEOM_POINT:
+        xy = np.array([(np.nan, np.nan) if r is None else r for r in rows], dtype=np.float64).reshape(-1, 2)
+        return GeoArrowArray(kind, xy, validity=bits)
+    if kind in (_abi.GEOM_MULTIPOINT, _abi.GEOM_LINESTRING):
+        off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        xy = np.array([c for r in rows for c in r], dtype=np.float64).reshape(-1, 2)
+        return GeoArrowArray(kind, xy, geom_offsets=off, validity=bits)
+    if kind == _abi.GEOM_MULTILINESTRING:
+        goff = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        parts = [p for r in rows for p in r]
+        roff = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int32)
+        xy = np.array([c for p in parts for c in p], dtype=np.float64).reshape(-1, 2)
+        return GeoArrowArray(kind, xy, geom_offsets=goff, ring_offsets=roff, validity=bits)
+    if kind == _abi.GEOM_POLYGON:
+        a = GeoArrowArray.from_polygons([[np.asarray(r).tolist() for r in g] for g in rows], close=False)
+    else:
+        a = GeoArrowArray.from_multipolygons([[[np.asarray(r).tolist() for r in p] for p in g] for g in rows], close=False)
+    return GeoArrowArray(a.geom_type, a.xy, geom_offsets=a.geom_offsets, part_offsets=a.part_offsets, ring_offsets=a.ring_offsets,
+                         validity=bits)
+
+
+def row_is_empty(kind: int, row) -> bool:
+    return row is None if kind == _abi.GEOM_POINT else len(row) == 0
+
+
+def row_polys(kind: int, row):
+    """a polygonal row as a list of polygons"""
+    return [row] if kind == _abi.GEOM_POLYGON else row
+
+
+def row_seqs(kind: int, row):
+    """the coordinate sequences whose segments a row's distance is taken over (points: one point per sequence)"""
+    if kind == _abi.GEOM_POINT:
+        return [] if row is None else [[row]]
+    if kind == _abi.GEOM_MULTIPOINT:
+        return [[q] for q in row]
+    if kind == _abi.GEOM_LINESTRING:
+        return [row] if len(row) else []
+    if kind == _abi.GEOM_MULTILINESTRING:
+        return list(row)
+    return [r for p in row_polys(kind, row) for r in p]
+
+
+def row_lmax(kind: int, row) -> float:
+    """longest segment of the row (0 for points)"""
+    m = 0.0
+    for s in row_seqs(kind, row):
+        s = np.asarray(s, dtype=np.float64)
+        if len(s) >= 2:
+            m = max(m, float(np.max(np.hypot(*(s[1:] - s[:-1]).T))))
+    return m
+
+
+def exact_row_distance2(p, kind: int, row):
+    """exact squared distance (Fraction) from point p to a non-empty row, and the row's longest segment; None for an empty row.
+    Polygonal: 0 when p is not outside, else the minimum over every ring of every part.  Only near-minimal segments and points
+    (by the f64 pre-filter of point_seqs_dist2) are evaluated exactly."""
+    if row_is_empty(kind, row):
+        return None, 0.0
+    if kind in (_abi.GEOM_POINT, _abi.GEOM_MULTIPOINT):
+        q = np.asarray([row] if kind == _abi.GEOM_POINT else row, dtype=np.float64)
+        pf = np.asarray(p, dtype=np.float64)
+        df = np.hypot(q[:, 0] - pf[0], q[:, 1] - pf[1])
+        cut = np.min(df) * (1 + 1e-9) + 1e-9 * np.max(np.abs(pf)) * 1e-6
+        px, py = Fraction(float(p[0])), Fraction(float(p[1]))
+        return min((px - Fraction(float(q[i, 0]))) ** 2 + (py - Fraction(float(q[i, 1]))) ** 2 for i in np.nonzero(df <= cut)[0]), 0.0
+    if kind in POLYGONAL and geom_position(p, row_polys(kind, row)) >= 0:
+        return Fraction(0), row_lmax(kind, row)
+    return point_seqs_dist2(p, row_seqs(kind, row))
+
+
+def exact_row_distance(p, kind: int, row):
+    """(Decimal distance or None for an empty row, distance_bound of the f64 evaluation)"""
+    d2, lmax = exact_row_distance2(p, kind, row)
+    if d2 is None:
+        return None, 0.0
+    d = dec_sqrt(d2)
+    return d, distance_bound(float(d), lmax)
+
+
+def f64_distance_matrix(P, kind: int, rows, usable=None, chunk_elems: int = 1 << 22) -> np.ndarray:
+    """(n_points, n_rows) f64 estimate of every point -> row distance, vectorised: the nearest segment (or point) of the row, 0
+    inside a polygonal row by an even-odd crossing count over all its rings; inf for empty rows and rows not `usable`.  A filter
+    only: near a boundary the crossing count may be wrong, but there the boundary distance is near 0 anyway."""
+    P = np.asarray(P, dtype=np.float64).reshape(-1, 2)
+    nr = len(rows)
+    A, B, owner, part = [], [], [], []
+    n_parts = 0
+    for j, row in enumerate(rows):
+        if (usable is not None and not usable[j]) or row_is_empty(kind, row):
+            continue
+        polys = row_polys(kind, row) if kind in POLYGONAL else [row_seqs(kind, row)]
+        for rings in polys:  # (the crossing count is taken per polygon: the parts of a multipolygon may overlap)
+            n_parts += 1
+            for s in rings:
+                s = np.asarray(s, dtype=np.float64).reshape(-1, 2)
+                a, b = (s, s) if len(s) == 1 else (s[:-1], s[1:])
+                A.append(a)
+                B.append(b)
+                owner.append(np.full(len(a), j))
+                part.append(np.full(len(a), n_parts))
+    out = np.full((len(P), nr), np.inf)
+    if not A:
+        return out
+    A, B, owner, part = np.concatenate(A), np.concatenate(B), np.concatenate(owner), np.concatenate(part)
+    starts = np.flatnonzero(np.concatenate([[True], owner[1:] != owner[:-1]]))
+    pstarts = np.flatnonzero(np.concatenate([[True], part[1:] != part[:-1]]))
+    ids = owner[starts]
+    D = B - A
+    d2 = np.sum(D * D, axis=1)
+    step = max(1, chunk_elems // len(A))
+    for c in range(0, len(P), step):
+        px, py = P[c : c + step, 0:1], P[c : c + step, 1:2]
+        qx, qy = px - A[:, 0], py - A[:, 1]
+        t = np.clip((qx * D[:, 0] + qy * D[:, 1]) / np.where(d2 > 0, d2, 1.0), 0.0, 1.0)
+        seg = np.hypot(qx - t * D[:, 0], qy - t * D[:, 1])
+        best = np.minimum.reduceat(seg, starts, axis=1)
+        if kind in POLYGONAL:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                xc = A[:, 0] + (py - A[:, 1]) * D[:, 0] / D[:, 1]
+            cross = ((A[:, 1] > py) != (B[:, 1] > py)) & (px < xc)
+            inside_part = np.add.reduceat(cross.astype(np.int32), pstarts, axis=1) % 2 == 1
+            inside = np.zeros(best.shape, dtype=bool)
+            np.logical_or.at(inside, (slice(None), np.searchsorted(starts, pstarts, side="right") - 1), inside_part)
+            best = np.where(inside, 0.0, best)
+        out[c : c + step, ids] = best
+    return out
+
+
+def exact_min_distance(p, kind: int, rows, frow, lmax=None):
+    """exact minimum distance (Decimal) from p over the rows, given the f64 estimates `frow` of f64_distance_matrix (inf: not a
+    candidate), and its bound: the largest distance_bound among the rows the f64 pre-filter kept.  (None, 0) when no row counts.
+    lmax: row_lmax of every row (computed when not given)."""
+    m = float(np.min(frow))
+    if not np.isfinite(m):
+        return None, 0.0
+    fin = np.flatnonzero(np.isfinite(frow))
+    lm = np.asarray(lmax)[fin] if lmax is not None else [row_lmax(kind, rows[j]) for j in fin]
+    cut = m * (1 + 1e-9) + 1e-9 * (float(np.max(lm)) + float(np.max(np.abs(p))) * 1e-6)
+    best, bound = None, 0.0
+    for j in np.flatnonzero(frow <= cut):
+        d2, lmax = exact_row_distance2(p, kind, rows[j])
+        best = d2 if best is None or d2 < best else best
+        bound = max(bound, lmax)
+    d = dec_sqrt(best)
+    return d, distance_bound(float(d), bound)
+
+
+# ---- one fixture per (family, G) instance of the distance kernels -------------------------------------------------------------
+
+INSTANCES = [(f, g) for f in FAMILIES for g in ((1,) if f == "point" else (1, 8, 32))]
+DOMAIN = 1000.0
+# per G: vertices per row (MULTIPOINT: points) well inside the band distance_group_size maps to G
+_VERTS = {1: (2, 9), 8: (30, 60), 32: (200, 300)}
+_ROWS = {1: 300, 8: 150, 32: 60}
+
+
+def _walk(rng, cx, cy, size, n):
+    xy = np.cumsum(np.concatenate([[[cx, cy]], rng.normal(0, size / np.sqrt(n), (n - 1, 2))]), axis=0)
+    return [tuple(c) for c in xy]
+
+
+def _dyadic_rect(cx, cy, m, s=0.125):
+    """closed axis-parallel square with m vertices per side on multiples of s (4 m vertices): every coordinate, and the middle of
+    every edge piece, is an exact double"""
+    x0, y0 = np.floor(cx / s) * s, np.floor(cy / s) * s
+    w = m * s * 8
+    side = [x0 + i * w / m for i in range(m)]
+    ring = [(x, y0) for x in side] + [(x0 + w, y0 + i * w / m) for i in range(m)]
+    ring += [(x0 + w - i * w / m, y0 + w) for i in range(m)] + [(x0, y0 + w - i * w / m) for i in range(m)]
+    return ring + ring[:1], (x0 + 0.5 * w / m, y0)
+
+
+def instance_rows(family: str, G: int, seed: int = 0):
+    """(kind, rows, validity, meta) of a right column built for (family, G): rows of a vertex count inside G's band, every
+    23rd row empty, every 19th null (its coordinates kept), every 10th an exact copy of an earlier row (exact ties), and — lines
+    and polygons — every 7th row dyadic (points exactly on its edges).  Polygons carry holes.  meta[i]: dict of the row's
+    centre, size, a point inside a hole (or None) and a point exactly on an edge (or None)."""
+    kind = FAMILIES[family]
+    rng = np.random.default_rng(1000 * kind + G + seed)
+    n = 400 if kind == _abi.GEOM_POINT else _ROWS[G]
+    lo, hi = _VERTS[G]
+    rows, meta = [], []
+    for i in range(n):
+        cx, cy = rng.uniform(0.02 * DOMAIN, 0.98 * DOMAIN, 2)
+        size = float(rng.uniform(5.0, 30.0))
+        hole = edge = None
+        k = int(rng.integers(lo, hi + 1))
+        dy = i % 7 == 3
+        if kind == _abi.GEOM_POINT:
+            row = (float(cx), float(cy))
+        elif kind == _abi.GEOM_MULTIPOINT:
+            row = [tuple(q) for q in rng.normal((cx, cy), size / 3, (max(k, 1), 2))]
+        elif kind == _abi.GEOM_LINESTRING:
+            if dy:
+                x0, y0 = np.floor(cx * 8) / 8, np.floor(cy * 8) / 8
+                row = [(x0 + j * 0.5, y0) for j in range(k)]
+                edge = (x0 + 0.25, y0)
+            else:
+                row = _walk(rng, cx, cy, size, k)
+        elif kind == _abi.GEOM_MULTILINESTRING:
+            parts = int(rng.integers(1, 3)) if G == 1 else int(rng.integers(2, 4))
+            kk = max(2, k // parts)
+            row = [_walk(rng, cx + 2 * size * p, cy, size, kk) for p in range(parts)]
+            if dy:
+                x0, y0 = np.floor(cx * 8) / 8, np.floor(cy * 8) / 8
+                row[0] = [(x0, y0 + j * 0.5) for j in range(kk)]
+                edge = (x0, y0 + 0.25)
+        else:
+            parts = 1 if kind == _abi.GEOM_POLYGON else (int(rng.integers(1, 3)) if G == 1 else 2)
+            kk = max(3, k // parts - (3 if G == 1 else 0))
+            row = []
+            for p in range(parts):
+                ox = cx + 1.5 * size * p
+                if dy:
+                    ring, e = _dyadic_rect(ox, cy, max(1, kk // 4))
+                    edge = edge or e
+                    rings = [np.asarray(ring)]
+                else:
+                    rings = [_star(rng, ox, cy, size, kk)]
+                if (G > 1 or i % 3 == 0) and not dy:
+                    rings.append(_star(rng, ox, cy, 0.15 * size, 3 if G == 1 else max(4, kk // 8), cw=True))
+                    hole = hole or (float(ox), float(cy))
+                row.append([np.asarray(r, dtype=np.float64) for r in rings])
+            if kind == _abi.GEOM_POLYGON:
+                row = row[0]
+        if i % 10 == 9 and not row_is_empty(kind, rows[i - 3]):
+            row, m = rows[i - 3], dict(meta[i - 3])
+        else:
+            m = {"center": (float(cx), float(cy)), "size": size, "hole": hole, "edge": edge}
+        if i % 23 == 11:
+            row = None if kind == _abi.GEOM_POINT else []
+            m = dict(m, hole=None, edge=None)
+        rows.append(row)
+        meta.append(m)
+    validity = [i % 19 != 4 for i in range(n)]
+    return kind, rows, validity, meta
+
+
+def _vertices(kind, row):
+    return [c for s in row_seqs(kind, row) for c in s]
+
+
+def _query(rng, kind, row, m, q):
+    """one query point for a row: q selects a point in the widened bbox, a vertex, a hole's inside, a vertex moved by one ulp, a
+    point exactly on an edge"""
+    cx, cy = m["center"]
+    s = m["size"]
+    if row_is_empty(kind, row) or q in (0, 5):
+        return (float(cx + rng.uniform(-s, s)), float(cy + rng.uniform(-s, s)))
+    vs = _vertices(kind, row)
+    v = vs[int(rng.integers(0, len(vs)))]
+    if q == 1:
+        return (float(v[0]), float(v[1]))
+    if q == 2:
+        if m["hole"] is not None:
+            return m["hole"]
+        a = rng.uniform(0, 2 * np.pi)
+        return (float(cx + 3 * s * np.cos(a)), float(cy + 3 * s * np.sin(a)))
+    if q == 3:
+        return (float(np.nextafter(v[0], np.inf)), float(v[1]))
+    return m["edge"] if m["edge"] is not None else (float(v[0]), float(np.nextafter(v[1], -np.inf)))
+
+
+_CACHE = {}
+
+
+def instance_fixture(family: str, G: int):
+    """dict: kind, rows, validity, meta, array (the right column), queries ((n_rows, 2): query i pairs with row i), left ((300, 2):
+    the nearest join's points: uniform over the extent, vertices, vertices moved by one ulp, points inside holes and on edges, near
+    duplicated rows); cached per process"""
+    key = (family, G)
+    if key in _CACHE:
+        return _CACHE[key]
+    kind, rows, validity, meta = instance_rows(family, G)
+    rng = np.random.default_rng(7 + 100 * kind + G)
+    queries = np.array([_query(rng, kind, rows[i], meta[i], i % 6) for i in range(len(rows))], dtype=np.float64)
+    usable = [validity[i] and not row_is_empty(kind, rows[i]) for i in range(len(rows))]
+    good = np.flatnonzero(usable)
+    copies = [j for j in range(9, len(rows), 10) if usable[j] and usable[j - 3] and rows[j] is rows[j - 3]]  # rows with an exact twin
+    left = [tuple(rng.uniform(-0.05 * DOMAIN, 1.05 * DOMAIN, 2)) for _ in range(140)]
+    for t in range(160):
+        j = int(good[rng.integers(0, len(good))]) if t % 4 else copies[int(rng.integers(0, len(copies)))]
+        left.append(_query(rng, kind, rows[j], meta[j], t % 6))
+    fx = {"kind": kind, "rows": rows, "validity": validity, "meta": meta, "array": column(kind, rows, validity),
+          "queries": queries, "left": np.array(left, dtype=np.float64), "usable": np.array(usable)}
+    _CACHE[key] = fx
+    return fx
+
+
+def exact_rowwise(fx, queries=None, rows_of=None):
+    """exact (Decimal or None for empty rows) and bound of distance(queries[i], rows[rows_of[i]]); cached for the fixture's own
+    queries"""
+    own = queries is None
+    if own and "exact_rowwise" in fx:
+        return fx["exact_rowwise"]
+    queries = fx["queries"] if own else queries
+    rows_of = np.arange(len(queries)) if rows_of is None else rows_of
+    out = [exact_row_distance(queries[i], fx["kind"], fx["rows"][int(rows_of[i])]) for i in range(len(queries))]
+    if own:
+        fx["exact_rowwise"] = out
+    return out
+
+
+def exact_nearest_minima(fx, left=None):
+    """per left point the exact minimum distance over the usable rows and its bound (None where no row counts)"""
+    own = left is None
+    if own and "exact_min" in fx:
+        return fx["exact_min"]
+    left = fx["left"] if own else left
+    F = f64_distance_matrix(left, fx["kind"], fx["rows"], fx["usable"])
+    lmax = [row_lmax(fx["kind"], r) for r in fx["rows"]]
+    out = [exact_min_distance(left[l], fx["kind"], fx["rows"], F[l], lmax) for l in range(len(left))]
+    if own:
+        fx["exact_min"] = out
+    return out
