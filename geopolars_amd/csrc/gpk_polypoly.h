@@ -210,6 +210,16 @@ __device__ inline void polygon_bboxes_group(const DevGeo& a, int r0, int r1, int
 //      decides containment (upstream tests every endpoint; the outcome is identical) — evaluated cooperatively.
 // Neighbouring polygons overlap in a small window, which takes the O(n*m) pruning loop down to the few segments
 // that can matter.  seg_list: 2 * PP_LIST double4 owned by this group (all lanes of a group sit in one wave).
+// every non-empty ring of the polygon is closed with at least two coordinates: then a ring of the other polygon that touches none
+// of its segments lies on one side of it, and one vertex of that ring decides its position
+__device__ inline bool ring_sided(const double2* __restrict__ r, int n) {
+    return n == 0 || (n >= 2 && r[0].x == r[n - 1].x && r[0].y == r[n - 1].y);
+}
+__device__ inline bool rings_sided(const DevGeo& g, int r0, int r1) {
+    for (int r = r0; r < r1; ++r)
+        if (!ring_sided(g.xy + g.ring_off[r], g.ring_off[r + 1] - g.ring_off[r])) return false;
+    return true;
+}
 constexpr int PP_VOTE = 4;   // list entries between two group votes in the cross test
 constexpr int PP_LIST = 32;  // per list; a group owns two lists (2 * PP_LIST double4 = 2 KB)
 template <int G>
@@ -307,15 +317,28 @@ __device__ inline bool polygon_intersects_polygon_group(const DevGeo& a, int ar0
     if (mb > 0 && against_a(mb)) return true;
 
     // containment: one vertex per ring of B against A, then A's exterior against B (a vertex outside the other polygon's exterior box
-    // is outside the polygon: no walk)
+    // is outside the polygon: no walk).  Upstream tests the endpoints of every segment: a ring of fewer than two coordinates has
+    // none, and when the polygon tested against has an open or one-coordinate ring, its sides do not stay put along a ring that
+    // misses its boundary, so then every endpoint is tested (invalid input only).
+    const bool a_sided = rings_sided(a, ar0, ar1), b_sided = rings_sided(b, br0, br1);
     for (int rb = br0; rb < br1; ++rb) {
-        const int c = b.ring_off[rb];
-        if (b.ring_off[rb + 1] > c) {
+        const int c = b.ring_off[rb], ce = b.ring_off[rb + 1];
+        if (ce - c < 2) continue;
+        if (a_sided) {
             const double2 q = b.xy[c];
             // (a vertex outside the other polygon's exterior box is outside it: the containment walk is skipped)
             if (!(q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w)) continue;
             if (polygon_pos_group<G>(a, ar0, ar1, q.x, q.y, lane) != dev::POS_OUTSIDE) return true;
+        } else {
+            for (int v = c; v < ce; ++v)
+                if (polygon_pos_group<G>(a, ar0, ar1, b.xy[v].x, b.xy[v].y, lane) != dev::POS_OUTSIDE) return true;
         }
+    }
+    if (a.ring_off[ar0 + 1] - a_c0 < 2) return false;
+    if (!b_sided) {
+        for (int v = a_c0; v < a.ring_off[ar0 + 1]; ++v)
+            if (polygon_pos_group<G>(b, br0, br1, a.xy[v].x, a.xy[v].y, lane) != dev::POS_OUTSIDE) return true;
+        return false;
     }
     const double2 p = a.xy[a_c0];
     if (!(p.x >= eb.x && p.x <= eb.z && p.y >= eb.y && p.y <= eb.w)) return false;
@@ -407,12 +430,20 @@ __device__ inline bool polygon_pair_small(const double2* __restrict__ axy, int n
     if (!hit) {
         // no boundary pair touches: one vertex per ring decides containment (see polygon_intersects_polygon_group).  A vertex outside the
         // other ring's BOX is outside the ring: neighbours whose boxes merely overlap — most candidates that do not intersect — skip both
-        // ring walks (round 6: the walks were a third of the refine)
-        const double2 q = t->b[0];
-        if (q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w) hit = coord_pos_ring_group<G>(t->a, na, q.x, q.y, lane) != dev::POS_OUTSIDE;
-        if (!hit) {
+        // ring walks (round 6: the walks were a third of the refine).  A ring of one coordinate has no segment endpoint to test; against
+        // an open or one-coordinate ring every endpoint is tested (polygon_intersects_polygon_group)
+        const bool a_sided = ring_sided(t->a, na), b_sided = ring_sided(t->b, nb);
+        if (nb >= 2 && a_sided) {
+            const double2 q = t->b[0];
+            if (q.x >= ea.x && q.x <= ea.z && q.y >= ea.y && q.y <= ea.w) hit = coord_pos_ring_group<G>(t->a, na, q.x, q.y, lane) != dev::POS_OUTSIDE;
+        } else if (nb >= 2) {
+            for (int v = 0; v < nb && !hit; ++v) hit = coord_pos_ring_group<G>(t->a, na, t->b[v].x, t->b[v].y, lane) != dev::POS_OUTSIDE;
+        }
+        if (!hit && na >= 2 && b_sided) {
             const double2 p = t->a[0];
             if (p.x >= eb.x && p.x <= eb.z && p.y >= eb.y && p.y <= eb.w) hit = coord_pos_ring_group<G>(t->b, nb, p.x, p.y, lane) != dev::POS_OUTSIDE;
+        } else if (!hit && na >= 2) {
+            for (int v = 0; v < na && !hit; ++v) hit = coord_pos_ring_group<G>(t->b, nb, t->a[v].x, t->a[v].y, lane) != dev::POS_OUTSIDE;
         }
     }
     __builtin_amdgcn_wave_barrier();  // the slice may be overwritten after this point
