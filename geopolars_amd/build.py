@@ -30,6 +30,7 @@ SOURCES = [
     "gpk_pipflow.hip",
     "gpk_pipindex.hip",
     "gpk_rowwise.hip",
+    "gpk_pairdist.hip",
     "gpk_nearest.hip",
     "gpk_hull.hip",
     "gpk_wkb.cpp",

@@ -668,6 +668,32 @@ static int32_t distance_rowmap_dev(const gpk_geoarray* pts, const gpk_geoarray* 
     return GPK_OK;
 }
 
+// neither side a POINT column: gpk_pairdist.hip.  Same row-count, b_rows and out_space rules as the point pairs.
+int32_t pair_distance_dev(const DevGeo& a, const DevGeo& b, const uint32_t* rows, int64_t n, double* out, uint32_t* large_rows,
+                          uint32_t* n_large, hipStream_t s);
+static int32_t distance_pairs(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double* out, int32_t out_space,
+                              hipStream_t s) {
+    if (!b_rows && a->d.n_geoms != b->d.n_geoms)
+        return fail(GPK_ERR_INVALID_ARGUMENT, "distance: row counts differ (%lld vs %lld)", (long long)a->d.n_geoms,
+                    (long long)b->d.n_geoms);
+    const int64_t n = a->d.n_geoms;
+    if (n == 0) return GPK_OK;
+    const size_t ob = sizeof(double) * (size_t)n, lb = sizeof(uint32_t) * (size_t)n;
+    const bool host_out = out_space != GPK_MEM_DEVICE;
+    GPK_TRY(workspace().begin((host_out ? align256(ob) : 0) + (b_rows && host_out ? align256(lb) : 0) + align256(lb) + 768));
+    double* out_dev = host_out ? (double*)workspace().take(ob) : out;
+    const uint32_t* rows_dev = b_rows;
+    if (b_rows && host_out) {
+        uint32_t* r = (uint32_t*)workspace().take(lb);
+        GPK_HIP(hipMemcpyAsync(r, b_rows, lb, hipMemcpyHostToDevice, s));
+        rows_dev = r;
+    }
+    uint32_t* large_rows = (uint32_t*)workspace().take(lb);  // rows for the work-group schedule, then their number
+    uint32_t* n_large = (uint32_t*)workspace().take(sizeof(uint32_t));
+    GPK_TRY(pair_distance_dev(a->d, b->d, rows_dev, n, out_dev, large_rows, n_large, s));
+    return copy_out(out, out_space, out_dev, ob, s);
+}
+
 }  // namespace gpk
 
 using namespace gpk;
@@ -747,10 +773,8 @@ int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const gpk_geoarray *pts = a, *other = b;
+    if (a->d.type != GPK_GEOM_POINT && b->d.type != GPK_GEOM_POINT) return distance_pairs(a, b, b_rows, out, out_space, s);
     if (a->d.type != GPK_GEOM_POINT) {
-        if (b->d.type != GPK_GEOM_POINT)
-            return fail(GPK_ERR_MISMATCHED_GEOMETRY, "distance: one side must be a POINT array (found types %d, %d)",
-                        a->d.type, b->d.type);
         if (b_rows) return fail(GPK_ERR_INVALID_ARGUMENT, "distance: b_rows requires the POINT array on the left");
         pts = b;
         other = a;

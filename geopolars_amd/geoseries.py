@@ -287,7 +287,12 @@ class GeoSeries:
     def distance(self, other: "GeoSeries", other_rows: Optional[np.ndarray] = None, row_map: Optional["RowMap"] = None) -> np.ndarray:
         """geoseries.rs:141-146: 1-to-1 row-wise Euclidean distance.  `other_rows` pairs row i with
         other[other_rows[i]] (the take() a dataframe caller would have materialised); a `row_map` prepared once from
-        such a pairing (RowMap(other, other_rows)) skips the per-call ordering of the rows."""
+        such a pairing (RowMap(other, other_rows)) skips the per-call ordering of the rows.
+
+        Every pair of families runs on the GPU.  When neither side is a POINT column: NaN for a null or empty row, 0.0
+        exactly when the two geometries intersect (exact orientations), else the set distance (include/geopolars_hip.h,
+        gpk_distance_rowwise).  The result has one value per row of `self` (with `other_rows`, or when `self` is a POINT
+        column or neither side is), else per row of `other`: the two then have equally many rows."""
         if row_map is not None:
             out = np.empty(len(self), dtype=np.float64)
             _abi.check(_abi.lib().gpk_distance_rowmap(self.device().handle, other.device().handle, row_map.handle, out.ctypes.data, MEM_HOST, None))

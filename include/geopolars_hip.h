@@ -321,8 +321,21 @@ int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_t* out_ring
 /* distance: geoseries.rs:141-146,248-251 ("1-to-1 row-wise").  `b_rows` (optional, same space as
  * out) maps row i of `a` to row b_rows[i] of `b` — the take() a caller would otherwise materialise;
  * NULL = identity (then n_geoms must match); an entry >= n_geoms(b) behaves like a null row of b
- * (distance NaN, predicate false — the out-of-range rule of gpk_take_*).  out[n_geoms(a)].  Supported: POINT x {POINT,
- * LINESTRING, POLYGON, MULTIPOLYGON, MULTILINESTRING, MULTIPOINT} and the mirrored pairs. */
+ * (distance NaN, predicate false — the out-of-range rule of gpk_take_*).  out[n_geoms(a)].  Supported: every pair of POINT,
+ * MULTIPOINT, LINESTRING, MULTILINESTRING, POLYGON and MULTIPOLYGON.
+ * Pairs with a POINT column: the point kernels (geo's EuclideanDistance per family; b_rows needs the POINT array on the left).
+ * Pairs of two non-point columns (gpk_pairdist.hip), for A = a[i], B = b[b_rows[i]]:
+ *   - a null or EMPTY side gives NaN; empty = no member has a coordinate (empty members of a multi-geometry are ignored).
+ *     NaN is what shapely 2 / GeoPandas return; geo 0.27 panics or returns f64::MAX there [verify: recalled, not checked];
+ *   - 0.0 exactly when A and B intersect as closed point sets, decided with exact orientations (a segment of A meets a segment
+ *     of B, touching and collinear overlap included, or a vertex of one side is inside or on a polygonal other side; holes
+ *     excluded).  A disjoint pair is never 0: a vertex one ulp off a segment gives a tiny positive distance;
+ *   - otherwise the minimum over every vertex of one side and every segment of the other, both ways, of the point-segment
+ *     distance, compared exactly as fractions, one square root at the end.  A one-coordinate sequence and every MULTIPOINT
+ *     member is a degenerate segment; every ring of a polygon counts.  For disjoint sets this is the set distance, within
+ *     16 u (d + 2 lmax) of the exact value (lmax: the longest segment of the pair).
+ *   distance(a, b) and distance(b, a) evaluate the same pairs in the same order.  Device outputs are stream-ordered (rows above
+ *   the large-row threshold are finished by a second launch on the same stream, without a read-back). */
 int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows,
                              double* out, int32_t out_space, void* stream);
 /* Magnitude range of gpk_distance_rowwise and gpk_nearest_join.  The kernels compare squared point-segment distances as
@@ -331,7 +344,9 @@ int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const
  * 0.5 - 50 m, points from 1 ulp to 3 m off an edge) by 2^k: both return exactly 2^k times the unscaled answer (and the same
  * pairs) for |k| <= 166 and depart at |k| = 168, i.e. at coordinates near 2^192 (6e57) or 2^-144 (5e-44).  Supported:
  * coordinates and coordinate differences within 2^-120 .. 2^120 (1e-36 .. 1e36) in magnitude; tests/test_gpu_georeferenced.py
- * holds |k| <= 100 of the same columns to exact scaling. */
+ * holds |k| <= 100 of the same columns to exact scaling.  The non-point pairs use the same fraction comparison (products of the
+ * sixth power of coordinate differences) and are held to exact 2^k scaling for |k| <= 100 by tests/test_gpu_distance_pairs.py
+ * (hand-made cases, also at UTM and Web Mercator placements, and random columns); beyond that they were not measured. */
 /* A row map that is used more than once (a dataframe's foreign-key column joined against the same geometry column for
  * every batch of points) can be prepared ONCE: gpk_rowmap_build orders the left rows by target (targets by descending
  * vertex count, so that the 64 rows one wave takes walk equally long linestrings) and keeps the order in HBM;
