@@ -168,6 +168,11 @@ _PROTOS = {
         C.c_int32,
         [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
+    "gpk_dwithin_join": (
+        C.c_int32,
+        [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
+    ),
+    "gpk_dwithin_rowwise": (C.c_int32, [_VP, _VP, _VP, C.c_double, _VP, C.c_int32, _VP]),
     "gpk_wkb_encode": (C.c_int32, [_VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "gpk_geoarray_to_wkb": (C.c_int32, [_VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP]),
     "gpk_join_indices": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int64, C.c_uint32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP]),

@@ -32,6 +32,7 @@ SOURCES = [
     "gpk_rowwise.hip",
     "gpk_pairdist.hip",
     "gpk_nearest.hip",
+    "gpk_dwithin.hip",
     "gpk_hull.hip",
     "gpk_wkb.cpp",
     "gpk_arrow.cpp",

@@ -23,6 +23,7 @@
 
 #include "gpk_device.h"
 #include "gpk_index.h"
+#include "gpk_candjoin.h"
 #include "gpk_pip.h"
 #include "gpk_polypoly.h"
 #include "gpk_contains.h"
@@ -1477,7 +1478,9 @@ __global__ __launch_bounds__(WR_BLOCK) void pip_write_kernel(DevGeo pts, DevGeo 
 
 // ---- join statistics (bench.py's edge_tests/s; off unless enabled) ---------------------------------------------------
 constexpr size_t JOIN_STATS_WORDS = 8 + 8 * 8000;  // + the stage stamps a GPK_TILE_TRACE build of gpk_pipflow.hip leaves (512 KB, only when statistics are on)
-static unsigned long long* g_join_stats = nullptr;  // device: {queued (point, part) pairs, slab edges walked by the exact phase, 0, 0}
+static unsigned long long* g_join_stats = nullptr;  // device: {queued (point, part) pairs, slab edges walked by the exact phase, rows the chain kernel deferred, 0};
+                                                    // a within-distance join (gpk_dwithin.hip, through CandRefine::refine) adds its candidates to [2] and the
+                                                    // candidates its box test rejected to [3]
 static bool g_join_stats_on = false;
 static unsigned long long* join_stats_buffer() { return g_join_stats_on ? g_join_stats : nullptr; }
 
@@ -1780,7 +1783,7 @@ static inline dim3 grid_for(int64_t n, int block) {
 }
 
 // polygonal x polygonal: candidates (count, scan, fill) -> pair-parallel exact refine -> hits (count, scan, emit)
-enum { REFINE_POLYGONAL = 0, REFINE_LINEAL_POINT = 1, REFINE_CONTAINS = 2, REFINE_ENVELOPE_INTERSECTS = 3, REFINE_ENVELOPE_CONTAINED = 4 };
+enum { REFINE_POLYGONAL = 0, REFINE_LINEAL_POINT = 1, REFINE_CONTAINS = 2, REFINE_ENVELOPE_INTERSECTS = 3, REFINE_ENVELOPE_CONTAINED = 4, REFINE_EXTERNAL = 5 };
 // gpk_index_query_envelope's refine (rstar's locate_in_envelope_intersecting / locate_in_envelope, spatial_index.rs:385-387,424-426): a
 // candidate's box already meets the query box (closed intervals: for_each_bbox_candidate); `contained` additionally asks that it lies
 // inside it, bounds included (rstar AABB::contains_envelope)
@@ -1803,8 +1806,10 @@ __global__ __launch_bounds__(256) void envelope_refine_kernel(const uint32_t* __
 }
 static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, uint32_t left_row_base,
                          uint32_t* out_counts, uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space,
-                         hipStream_t s, int refine = REFINE_POLYGONAL, const double4* given_lbbox = nullptr) {
+                         hipStream_t s, int refine = REFINE_POLYGONAL, const double4* given_lbbox = nullptr, const CandRefine* ext = nullptr) {
+    // (ext: the refine of another translation unit, REFINE_EXTERNAL — gpk_candjoin.h; the arms of this file pass none)
     const int64_t n = left->d.n_geoms;
+    const char* what = ext ? ext->name : "spatial_join";
     const bool host_out = out_space != GPK_MEM_DEVICE;
     const bool want_pairs = pair_capacity > 0;
     // per-call allocations that outlive a workspace reset (gpk_bounds uses the workspace itself)
@@ -1868,11 +1873,11 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
     if (rc != GPK_OK) return done(rc);
     // candidate offsets are i32 (one slice per left row): more than 2^31 - 1 bbox candidates cannot be addressed
     if (cand_total > (unsigned long long)INT32_MAX)
-        return done(fail(GPK_ERR_CAPACITY, "spatial_join: %llu bbox candidates exceed the i32 candidate offsets: shard the left side", cand_total));
+        return done(fail(GPK_ERR_CAPACITY, "%s: %llu bbox candidates exceed the i32 candidate offsets: shard the left side", what, cand_total));
     n_cand = (int32_t)cand_total;
     uint32_t *cand_r = nullptr, *cand_l = nullptr, *cand_sorted = nullptr;
     uint8_t* hit = nullptr;
-    void* seg_tmp = nullptr;
+    void *seg_tmp = nullptr, *ext_scratch = nullptr;
     size_t seg_bytes = 0;
     unsigned seg_bits = 1;
     while (seg_bits < 32 && ((int64_t)1 << seg_bits) < right->d.n_geoms) ++seg_bits;
@@ -1881,9 +1886,10 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
         if (has_big_rows) {
             const hipError_t qe = rocprim::segmented_radix_sort_keys(nullptr, seg_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned)n_cand,
                                                                      (unsigned)n, (const int32_t*)cand_off, (const int32_t*)cand_off + 1, 0, seg_bits, s);
-            if (qe != hipSuccess) return done(fail(GPK_ERR_DEVICE, "spatial_join: %s", hipGetErrorString(qe)));
+            if (qe != hipSuccess) return done(fail(GPK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(qe)));
         }
-        rc = workspace_aux(1).begin((has_big_rows ? 3 : 2) * align256(sizeof(uint32_t) * nc1) + align256(nc1) + align256(seg_bytes) + 512);
+        const size_t ext_bytes = ext ? align256(ext->scratch_fixed + ext->scratch_per_cand * nc1) : 0;
+        rc = workspace_aux(1).begin((has_big_rows ? 3 : 2) * align256(sizeof(uint32_t) * nc1) + align256(nc1) + align256(seg_bytes) + ext_bytes + 512);
         if (rc != GPK_OK) return done(rc);
         cand_r = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
         cand_l = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
@@ -1892,6 +1898,7 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
             cand_sorted = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
             seg_tmp = workspace_aux(1).take(seg_bytes ? seg_bytes : 1);
         }
+        if (ext) ext_scratch = workspace_aux(1).take(ext_bytes);
     }
     auto stage23 = [&]() -> int32_t {
         if (staged && !has_big_rows)
@@ -1909,7 +1916,9 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
             int64_t blocks = ((int64_t)n_cand + (256 / JOIN_GS) - 1) / (256 / JOIN_GS);
             const int64_t cap = (int64_t)cu_count() * 64;
             if (blocks > cap) blocks = cap;
-            if (refine == REFINE_ENVELOPE_INTERSECTS || refine == REFINE_ENVELOPE_CONTAINED)
+            if (refine == REFINE_EXTERNAL)
+                GPK_TRY(ext->refine(ext->ctx, cand_l, cand_r, n_cand, ext_scratch, hit, join_stats_buffer(), s));
+            else if (refine == REFINE_ENVELOPE_INTERSECTS || refine == REFINE_ENVELOPE_CONTAINED)
                 GPK_LAUNCH("gpk_envelope_refine", envelope_refine_kernel, dim3((unsigned)(((int64_t)n_cand + 255) / 256)), dim3(256), 0, s,
                            (const uint32_t*)cand_l, (const uint32_t*)cand_r, (int64_t)n_cand, (const double4*)lbbox, right_index->v.bbox,
                            refine == REFINE_ENVELOPE_CONTAINED ? 1 : 0, hit);
@@ -1935,6 +1944,7 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
             GPK_LAUNCH("gpk_pair_emit", pair_emit_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, n, (const int32_t*)cand_off,
                        (const uint32_t*)cand_r, (const uint8_t*)hit, counts, (const int32_t*)offsets, left_row_base, (uint2*)pairs_dev,
                        pair_capacity);
+        if (want_pairs && ext && ext->emitted) GPK_TRY(ext->emitted(ext->ctx, n, cand_off, hit, offsets, ext_scratch, pair_capacity, s));
         return GPK_OK;
     };
     rc = stage23();
@@ -1942,7 +1952,7 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
     unsigned long long total = 0;  // 64-bit grand total of the hit scan (hits <= candidates <= INT32_MAX, checked above)
     hipError_t e = hipMemcpyAsync(&total, btot + nb, sizeof total, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return done(fail(GPK_ERR_DEVICE, "spatial_join: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return done(fail(GPK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e)));
     *n_pairs = (int64_t)total;
     if (host_out) {
         if (out_counts) {
@@ -1956,8 +1966,14 @@ static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, co
         }
     }
     if (want_pairs && (int64_t)total > pair_capacity)
-        return done(fail(GPK_ERR_CAPACITY, "spatial_join: %lld pairs but capacity %lld", (long long)total, (long long)pair_capacity));
+        return done(fail(GPK_ERR_CAPACITY, "%s: %lld pairs but capacity %lld", what, (long long)total, (long long)pair_capacity));
     return done(GPK_OK);
+}
+int32_t bbox_join_refined(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, uint32_t left_row_base,
+                          uint32_t* out_counts, uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, hipStream_t s,
+                          const double4* lbbox, const CandRefine& refine) {
+    return bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, REFINE_EXTERNAL, lbbox,
+                     &refine);
 }
 
 // The epoch words of the fused point joins: one buffer per device (zeroed when created; a launch's tag is never 0), a process-wide

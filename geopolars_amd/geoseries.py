@@ -328,6 +328,31 @@ class GeoSeries:
     def intersects(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
         return self._predicate(other, "intersects", other_rows)
 
+    def dwithin(self, other: "GeoSeries", distance: float, other_rows=None) -> np.ndarray:
+        """GeoPandas' GeoSeries.dwithin: row i is True when distance(self[i], other[other_rows[i]]) <= `distance` (closed; the
+        distance is the one `distance()` returns for the pair).  Null, empty and NaN-point rows are never within any distance.
+        Every pair of families (gpk_dwithin_rowwise); `distance` must be finite and >= 0."""
+        d = dwithin_distance_arg(distance)
+        out = np.empty(len(self), dtype=np.uint8)
+        rows = None if other_rows is None else np.ascontiguousarray(other_rows, dtype=np.uint32)
+        _abi.check(
+            _abi.lib().gpk_dwithin_rowwise(
+                self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, d, out.ctypes.data, MEM_HOST, None
+            )
+        )
+        return out.astype(bool)
+
+
+def dwithin_distance_arg(distance) -> float:
+    """the `distance` of a dwithin call as a float; anything but a finite number >= 0 is refused here, before any device call"""
+    try:
+        d = float(distance)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if not (d >= 0.0) or d == float("inf"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"dwithin: distance must be a finite number >= 0, got {distance!r}")
+    return d
+
 
 class RowMap:
     """A row pairing (left row i -> right row rows[i]) ordered once for the grouped distance kernel (gpk_rowmap_build):

@@ -4,6 +4,7 @@
     SpatialIndex            spatial_index.rs:314-350 (TryFrom<&Series>)
     spatial_join            spatial_index.rs:37-204
     spatial_join_nearest    GeoPandas' sjoin_nearest (not in the reference): every point with the nearest geometries of another table
+    spatial_join_dwithin    GeoPandas' sjoin(predicate="dwithin", distance=d) (not in the reference): every pair within a distance
 
 The candidate generation + exact refine (spatial_index.rs:74-143) run on the GPU through
 gpk_spatial_join; this module only marshals buffers and — for dataframe-shaped callers — assembles
@@ -21,7 +22,7 @@ import numpy as np
 from . import _abi
 from ._abi import MEM_DEVICE, MEM_HOST, PREDICATES
 from .geoarrow import DeviceGeoArray
-from .geoseries import GeoSeries
+from .geoseries import GeoSeries, dwithin_distance_arg
 
 
 class SpatialIndex:
@@ -448,5 +449,118 @@ def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = N
         d = np.zeros(len(ri), dtype=np.float64)
         d[matched] = dist
         cols.append(pa.array(d, type=pa.float64(), mask=~matched))
+        names.append(options.distance_col)
+    return pa.table(cols, names=names)
+
+
+# ---- within-distance join (gpk_dwithin_join) ------------------------------------------------------------------------------------
+
+
+@dataclass
+class SpatialJoinDWithinArgs:
+    """Options of spatial_join_dwithin (GeoPandas' sjoin(predicate="dwithin", distance=...) over this module's table shape)."""
+
+    distance: Optional[float] = None  # required: finite and >= 0; pairs with distance(l, r) <= distance are joined
+    join_type: str = "inner"  # "inner" | "left" (unmatched left rows once, with nulls on the right)
+    distance_col: Optional[str] = None  # name of a float64 column with each pair's distance (null for unmatched left rows)
+    l_suffix: Optional[str] = "_left"
+    r_suffix: Optional[str] = "_right"
+    r_index: Optional[SpatialIndex] = None
+    l_geom_type: int = -1  # as in SpatialJoinArgs
+    r_geom_type: int = -1
+
+
+def dwithin_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    distance: float,
+    r_index: Optional[SpatialIndex] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every (l, r) with distance(left[l], right[r]) <= `distance`, any two geometry families: (pairs (H, 2) uint32 sorted by (l, r),
+    counts (n_left,) uint32, distances (H,) float64 — the doubles GeoSeries.distance returns for the pairs).  Host-buffer variant: the
+    pair buffer is sized like join_pairs'."""
+    d = dwithin_distance_arg(distance)
+    lib = _abi.lib()
+    n = len(left)
+    counts = np.zeros(n, dtype=np.uint32)
+    n_pairs = C.c_int64(0)
+    rh = r_index.handle if r_index is not None else None
+    capacity = max(1024, 4 * n)
+    while True:
+        pairs = np.empty((capacity, 2), dtype=np.uint32)
+        dist = np.empty(capacity, dtype=np.float64)
+        rc = lib.gpk_dwithin_join(
+            left.device().handle, right.device().handle, rh, d, left_row_base, counts.ctypes.data, pairs.ctypes.data, dist.ctypes.data, capacity,
+            C.byref(n_pairs), MEM_HOST, None
+        )
+        if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
+            capacity = int(n_pairs.value)
+            continue
+        _abi.check(rc)
+        h = int(n_pairs.value)
+        return pairs[:h].copy(), counts, dist[:h].copy()
+
+
+def dwithin_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    distance: float,
+    out_counts,
+    out_pairs,
+    out_dist=None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_dist (cap,) float64 torch CUDA tensors (any
+    may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
+    d = dwithin_distance_arg(distance)
+    n_pairs = C.c_int64(0)
+    _abi.check(
+        _abi.lib().gpk_dwithin_join(
+            left.handle,
+            right.handle,
+            r_index.handle if r_index is not None else None,
+            d,
+            left_row_base,
+            out_counts.data_ptr() if out_counts is not None else None,
+            out_pairs.data_ptr() if out_pairs is not None else None,
+            out_dist.data_ptr() if out_dist is not None else None,
+            out_pairs.shape[0] if out_pairs is not None else 0,
+            C.byref(n_pairs),
+            MEM_DEVICE,
+            stream,
+        )
+    )
+    return int(n_pairs.value)
+
+
+def spatial_join_dwithin(lhs, rhs, options: Optional[SpatialJoinDWithinArgs] = None):
+    """GeoPandas' sjoin(predicate="dwithin", distance=d) over pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as
+    spatial_join takes them): every left row with every right row within `options.distance` of it, shaped like spatial_join's result —
+    suffixed left columns, suffixed right columns, then `distance_col` when asked for.  Any two geometry families."""
+    import pyarrow as pa
+
+    options = options or SpatialJoinDWithinArgs()
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"dwithin join: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    d = dwithin_distance_arg(options.distance)
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, dist = dwithin_pairs(lgeo, rgeo, d, options.r_index)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    cols, names = [], []
+    for name in lhs.column_names:
+        cols.append(take_column(_as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
+        names.append(name + (options.l_suffix or ""))
+    for name in rhs.column_names:
+        cols.append(take_column(_as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
+        names.append(name + (options.r_suffix or ""))
+    if options.distance_col is not None:
+        matched = ri >= 0  # (pair k of the sorted output is joined row k among the rows with r >= 0: see spatial_join_nearest)
+        dd = np.zeros(len(ri), dtype=np.float64)
+        dd[matched] = dist
+        cols.append(pa.array(dd, type=pa.float64(), mask=~matched))
         names.append(options.distance_col)
     return pa.table(cols, names=names)

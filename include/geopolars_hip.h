@@ -466,6 +466,39 @@ int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray* right, co
                          int64_t* n_pairs, int32_t out_space, void* stream);
 
 /*
+ * Within-distance join (GeoPandas sjoin(predicate="dwithin", distance=d)): every (l, r) with distance(left[l], right[r]) <= distance.
+ * Left and right are each any of POINT, MULTIPOINT, LINESTRING, MULTILINESTRING, POLYGON, MULTIPOLYGON — all 36 ordered pairs
+ * (anything else: GPK_ERR_MISMATCHED_GEOMETRY).
+ *   distance             finite and >= 0; negative, NaN or infinite: GPK_ERR_INVALID_ARGUMENT before any device work.  0 is legal and
+ *                        means "the closed sets meet" (the exact zero of the distance contract).
+ *   the pair test        (l, r) is returned iff d(l, r) <= distance (closed, compared as doubles), where d(l, r) is the library's own
+ *                        row-wise distance of the pair: the value the per-row kernel of gpk_distance_rowwise(left, right, ...) computes for
+ *                        these two columns — the same device routine, the same lane-group size (chosen from the non-point column when
+ *                        one side is POINT, from both columns and the large-row switch otherwise) and the same lane order, so the
+ *                        returned distances and the pair set are bit for bit what that call and a comparison would give.  (Its grouped
+ *                        schedule for LINESTRING right sides with >= 8 rows per target agrees within its 1e-9 contract.)
+ *   never matched        null rows, EMPTY rows (no member has a coordinate) and POINT rows with a NaN coordinate, on either side —
+ *                        unlike row-wise distance, which gives 0.0 for a point against an empty linestring
+ *   out_counts[n_left]   u32 matches per left row (may be NULL)
+ *   out_pairs[2*cap]     u32 (l, r) interleaved, sorted by (l, r) (NULL with cap == 0: count-only mode)
+ *   out_dist[cap]        f64 d(l, r) of each pair (may be NULL)
+ *   *n_pairs             total, always set; GPK_ERR_CAPACITY when > cap and pairs were asked for.  More than 2^31 - 1 bbox candidates
+ *                        (right boxes meeting a left box grown by `distance`) or pairs: GPK_ERR_CAPACITY, shard the left side.
+ * `left_row_base` is added to every emitted l.  All buffers live in `out_space`.  `right_index`: an index of `right` carrying the bbox
+ * grid (else GPK_ERR_INVALID_ARGUMENT), or NULL: a GPK_INDEX_BBOX_GRID index is built for the call and freed (it is not kept on the
+ * handle).  Synchronous, like gpk_spatial_join.  Magnitude range: as gpk_distance_rowwise.
+ */
+int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, double distance,
+                         uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_dist, int64_t pair_capacity,
+                         int64_t* n_pairs, int32_t out_space, void* stream);
+/* Row-wise dwithin (shapely / GeoPandas GeoSeries.dwithin): out[i] = 1 iff distance(a[i], b[b_rows[i]]) <= distance, else 0; the shape
+ * rules of gpk_distance_rowwise (same n without b_rows; b_rows with a POINT column needs the POINT array on the left; an entry out of
+ * range behaves like a null row), the `distance` and never-matched rules of gpk_dwithin_join (out[i] = 0).  The distance is the one
+ * gpk_distance_rowwise returns for the call, so dwithin(a, b, d)[i] == dwithin(b, a, d)[i] for identity rows.  out[n_geoms(a)] bytes. */
+int32_t gpk_dwithin_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double distance, uint8_t* out,
+                            int32_t out_space, void* stream);
+
+/*
  * Stream-ordered form of gpk_spatial_join for callers that keep everything in HBM (the idiom a pipeline of
  * kernels on one HIP stream wants; the reference's call is synchronous, spatial_index.rs:44-58): the join is
  * ENQUEUED on `stream` and the call returns without waiting.
@@ -552,7 +585,8 @@ int32_t gpk_allgatherv_rows_f64(gpk_comm* comm, const double* local_dev, int64_t
  * leave it off in timed regions).  out = {(point, part) pairs sent to the exact winding walk, edges walked for them,
  * left rows a chain-kernel join deferred to the generic walk (list cells, sub-cells without a chain entry, orientations
  * the floating-point filter could not certify), 0}, accumulated over the joins since the last reset; gpk_join_stats waits
- * for the device. */
+ * for the device.  gpk_dwithin_join uses the last two words for its own counts: out[2] += bbox candidates, out[3] += candidates its
+ * box-to-box test rejected before reading a coordinate (reset between joins of the two kinds to keep the meanings apart). */
 int32_t gpk_join_stats_enable(int32_t on);
 int32_t gpk_join_stats(int64_t out[4], int32_t reset);
 
