@@ -26,6 +26,8 @@ SOURCES = [
     "gpk_runtime.hip",
     "gpk_unary.hip",
     "gpk_ringstream.hip",
+    "gpk_gridindex.hip",
+    "gpk_bboxjoin.hip",
     "gpk_join.hip",
     "gpk_pipflow.hip",
     "gpk_pipindex.hip",

@@ -1,7 +1,8 @@
-// gpk_candjoin.h — the staged bbox candidate generator of gpk_join.hip (bbox_join: candidates per left box from the right side's grid
-// directory, a per-candidate refine, then count / scan / emit of the hits sorted by (l, r)) opened to a refine that lives in another
-// translation unit.  The within-distance join (gpk_dwithin.hip) hands over left boxes grown by its distance and refines every
-// candidate with the library's distance routines.
+// gpk_candjoin.h — what the joins share: the staged bbox candidate generator of gpk_bboxjoin.hip (bbox_join: candidates per left box from
+// the right side's grid directory, a per-candidate refine, then count / scan / emit of the hits sorted by (l, r)) with its one refine
+// interface, and the host steps every pairs join repeats.  The predicates of gpk_spatial_join refine with the kernels of
+// gpk_bboxjoin.hip; the within-distance join (gpk_dwithin.hip) hands over left boxes grown by its distance and refines every candidate
+// with the library's distance routines.
 #pragma once
 
 #include "gpk_index.h"
@@ -23,10 +24,68 @@ struct CandRefine {
                        int64_t pair_capacity, hipStream_t s);
 };
 
-// bbox_join of gpk_join.hip with the caller's left boxes (device, one per left row; NaN: no candidates) and the caller's refine.
-// Outputs, capacity rule and errors as gpk_spatial_join; uses workspace() and workspace_aux(1), leaves workspace_aux(0) alone.
-int32_t bbox_join_refined(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, uint32_t left_row_base,
-                          uint32_t* out_counts, uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, hipStream_t s,
-                          const double4* lbbox, const CandRefine& refine);
+// The box-candidate join with the caller's left boxes (device, one per left row; NaN: no candidates; nullptr: the rows' own boxes,
+// computed with gpk_bounds) and the caller's refine.  Outputs, capacity rule and errors as gpk_spatial_join; uses workspace() and
+// workspace_aux(1), leaves workspace_aux(0) alone unless it computes the boxes itself.
+int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, uint32_t left_row_base,
+                  uint32_t* out_counts, uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, hipStream_t s,
+                  const double4* lbbox, const CandRefine& refine);
+// the rows' own boxes in workspace_aux(0), for a caller whose refine reads the boxes it hands to bbox_join
+int32_t left_boxes(const gpk_geoarray* left, hipStream_t s, const double4** out);
+
+// The refines of gpk_spatial_join (gpk_bboxjoin.hip) over one context: the two columns, the boxes bbox_join is handed and the index's
+// boxes of the right rows.  The lineal x point refine reads no boxes (lbbox may be nullptr).
+struct BoxRefineCtx {
+    const gpk_geoarray *left, *right;
+    const double4 *lbbox, *rbbox;
+    bool l_one_ring, r_one_ring;  // every polygon of that POLYGON column is known to have exactly one ring
+};
+// (filled AFTER the left boxes were computed: gpk_bounds classifies the column's rings, which is where l_one_ring comes from)
+BoxRefineCtx box_refine_ctx(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, const double4* lbbox);
+CandRefine polygonal_intersects_refine(BoxRefineCtx* cx);
+CandRefine polygonal_contains_refine(BoxRefineCtx* cx);
+CandRefine lineal_point_refine(BoxRefineCtx* cx);
+
+// gpk_join.hip: the join statistics words, or nullptr unless gpk_join_stats_enable(1)
+unsigned long long* join_stats_buffer();
+
+// ---- host steps of every pairs join ---------------------------------------------------------------------------------------------
+// (an index whose slabs name coordinates by index reads THIS array's coordinates: rows alone do not identify the column)
+inline int32_t index_matches(const gpk_index* right_index, const gpk_geoarray* right) {
+    if (right_index->n_geoms != right->d.n_geoms || right_index->n_coords != right->d.n_coords || right_index->n_rings != right->d.n_rings)
+        return fail(GPK_ERR_INVALID_ARGUMENT, "right_index was built over a different array");
+    return GPK_OK;
+}
+inline int32_t index_matches_with_grid(const gpk_index* right_index, const gpk_geoarray* right, const char* who) {
+    GPK_TRY(index_matches(right_index, right));
+    if (!right_index->v.grid || !right_index->v.cell_off || !right_index->v.items || !right_index->v.bbox)
+        return fail(GPK_ERR_INVALID_ARGUMENT, "%s: right_index carries no bbox grid", who);
+    return GPK_OK;
+}
+
+// an empty join: every count is zero (enqueued on `s` for a device caller)
+inline int32_t zero_counts(uint32_t* out_counts, int64_t n, int32_t out_space, hipStream_t s) {
+    if (!out_counts || n <= 0) return GPK_OK;
+    if (out_space == GPK_MEM_DEVICE)
+        GPK_HIP(hipMemsetAsync(out_counts, 0, sizeof(uint32_t) * (size_t)n, s));
+    else
+        memset(out_counts, 0, sizeof(uint32_t) * (size_t)n);
+    return GPK_OK;
+}
+
+// The end of a pairs join whose total is on the host: *n_pairs, then — for a host caller — the n counts and the first
+// min(total, pair_capacity) pairs from their device staging, then the capacity error.
+inline int32_t finish_pairs(const char* who, int64_t total, int64_t n, uint32_t* out_counts, const uint32_t* counts_dev, uint32_t* out_pairs,
+                            const uint32_t* pairs_dev, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, hipStream_t s) {
+    *n_pairs = total;
+    if (out_space != GPK_MEM_DEVICE) {
+        if (out_counts) GPK_TRY(copy_out(out_counts, out_space, counts_dev, sizeof(uint32_t) * (size_t)n, s));
+        if (pair_capacity > 0)
+            GPK_TRY(copy_out(out_pairs, out_space, pairs_dev, sizeof(uint32_t) * 2 * (size_t)(total < pair_capacity ? total : pair_capacity), s));
+    }
+    if (pair_capacity > 0 && total > pair_capacity)
+        return fail(GPK_ERR_CAPACITY, "%s: %lld pairs but capacity %lld", who, (long long)total, (long long)pair_capacity);
+    return GPK_OK;
+}
 
 }  // namespace gpk

@@ -163,6 +163,16 @@ bool debug_sync();  // GPK_DEBUG_SYNC=1: name every launch on stderr and wait fo
             return ::gpk::fail(GPK_ERR_DEVICE, "launch of %s failed: %s", name,          \
                                hipGetErrorString(_le));                                  \
     } while (0)
+// GPK_LAUNCH in a function that holds something it must release: a failed launch returns on_fail(rc) instead of rc
+#define GPK_LAUNCH_OR(on_fail, ...)              \
+    do {                                         \
+        auto _f = [&]() -> int32_t {             \
+            GPK_LAUNCH(__VA_ARGS__);             \
+            return GPK_OK;                       \
+        };                                       \
+        int32_t _rc = _f();                      \
+        if (_rc != GPK_OK) return on_fail(_rc);  \
+    } while (0)
 
 int32_t require_device();  // GPK_ERR_DEVICE unless the current device is a gfx950
 int cu_count();

@@ -4,7 +4,7 @@
 //
 // Pipeline of the join (one for all 36 ordered pairs):
 //   1. left boxes (gpk_bounds) grown on every side by g = distance + margin (dwithin_grow_kernel);
-//   2. candidates: the staged bbox candidate generator of gpk_join.hip (gpk_candjoin.h) with the grown boxes in the left boxes' place —
+//   2. candidates: the staged bbox candidate generator of gpk_bboxjoin.hip (gpk_candjoin.h) with the grown boxes in the left boxes' place —
 //      every (l, r) whose right box meets the grown left box, once, ordered by (l, r);
 //   3. refine, G lanes per CANDIDATE (the unit of parallelism is the candidate, not the left row: ragged candidate lists do not
 //      unbalance waves): first the distance between the two UNGROWN boxes — above distance + margin the candidate is rejected before a
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void dwithin_grow_kernel(const double4* __rest
 }
 
 // Can the pair lie within t?  The distance between the two (exact) boxes against t plus the margin; false when a box has a NaN.
-// Null rows never reach the refine: every candidate kernel of gpk_join.hip (bbox_cand_stage_kernel, cand_compact_kernel, bbox_cand_kernel)
+// Null rows never reach the refine: every candidate kernel of gpk_bboxjoin.hip (bbox_cand_stage_kernel, cand_compact_kernel, bbox_cand_kernel)
 // tests the validity bit of the left and of the right row before it lists a pair, whatever the rows' boxes hold, so the refine kernels
 // read (l, r) without a validity test of their own (one in the point kernels cost 15 % of the C3 refine: 350 against 304 ms).
 __device__ __forceinline__ bool boxes_within(const double4 a, const double4 b, double t) {
@@ -327,12 +327,7 @@ extern "C" int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray
     if (pair_capacity < 0 || (pair_capacity > 0 && !out_pairs)) return fail(GPK_ERR_INVALID_ARGUMENT, "pair_capacity without out_pairs");
     if (!dwithin_family(left->d.type) || !dwithin_family(right->d.type))
         return fail(GPK_ERR_MISMATCHED_GEOMETRY, "dwithin_join: unsupported geometry types %d, %d", left->d.type, right->d.type);
-    if (right_index) {
-        if (right_index->n_geoms != right->d.n_geoms || right_index->n_coords != right->d.n_coords || right_index->n_rings != right->d.n_rings)
-            return fail(GPK_ERR_INVALID_ARGUMENT, "right_index was built over a different array");
-        if (!right_index->v.grid || !right_index->v.cell_off || !right_index->v.items || !right_index->v.bbox)
-            return fail(GPK_ERR_INVALID_ARGUMENT, "dwithin_join: right_index carries no bbox grid");
-    }
+    if (right_index) GPK_TRY(index_matches_with_grid(right_index, right, "dwithin_join"));
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = left->d.n_geoms;
@@ -340,14 +335,8 @@ extern "C" int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray
     if (n > (int64_t)INT32_MAX) return fail(GPK_ERR_INVALID_ARGUMENT, "dwithin_join: more than 2^31 - 1 left rows: shard the left side");
     const bool host_out = out_space != GPK_MEM_DEVICE;
     if (right->d.n_geoms == 0) {  // nothing to meet: every count is zero
-        if (out_counts) {
-            if (host_out) {
-                memset(out_counts, 0, sizeof(uint32_t) * (size_t)n);
-            } else {
-                GPK_HIP(hipMemsetAsync(out_counts, 0, sizeof(uint32_t) * (size_t)n, s));
-                GPK_HIP(hipStreamSynchronize(s));
-            }
-        }
+        GPK_TRY(zero_counts(out_counts, n, out_space, s));
+        if (out_counts && !host_out) GPK_HIP(hipStreamSynchronize(s));
         return GPK_OK;
     }
 
@@ -375,13 +364,8 @@ extern "C" int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray
     // the magnitude the margin scales with: the directory's origin and extent (an axis of zero extent has inv = 0: one column / row)
     const GridParams& h = right_index->host_grid;
     const double scale = fabs(h.x0) + fabs(h.y0) + (h.inv_w > 0.0 ? (double)h.gx / h.inv_w : 0.0) + (h.inv_h > 0.0 ? (double)h.gy / h.inv_h : 0.0);
-    auto grow = [&]() -> int32_t {
-        GPK_LAUNCH("gpk_dwithin_grow", dwithin_grow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double4*)lbox, n, distance,
-                   scale, grown);
-        return GPK_OK;
-    };
-    rc = grow();
-    if (rc != GPK_OK) return done(rc);
+    GPK_LAUNCH_OR(done, "gpk_dwithin_grow", dwithin_grow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double4*)lbox, n, distance,
+                  scale, grown);
 
     DwCtx cx{left, right, lbox, right_index->v.bbox, distance, dist_dev, left->d.type != GPK_GEOM_POINT && right->d.type != GPK_GEOM_POINT};
     CandRefine hook;
@@ -391,7 +375,7 @@ extern "C" int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray
     hook.scratch_per_cand = (dist_dev ? sizeof(double) : 0) + (cx.pair_kernels ? sizeof(uint32_t) : 0);
     hook.refine = dwithin_refine;
     hook.emitted = dwithin_emitted;
-    rc = bbox_join_refined(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, grown, hook);
+    rc = bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, grown, hook);
     if (rc != GPK_OK) return done(rc);
     if (want_dist && host_out && *n_pairs > 0) rc = copy_out(out_dist, out_space, dist_dev, sizeof(double) * (size_t)*n_pairs, s);
     return done(rc);

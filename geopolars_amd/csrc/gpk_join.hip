@@ -1,8 +1,9 @@
-// gpk_join.hip — spatial index build + the join refine of geopolars/src/spatial_index.rs:37-143.
+// gpk_join.hip — the point x polygonal join and the dispatch of geopolars/src/spatial_index.rs:37-143.
 //
-//   gpk_index_build   == SpatialIndex::try_from(&Series)            spatial_index.rs:320-334
 //   gpk_spatial_join  == intersection_candidates_with_other_tree     spatial_index.rs:74-76
 //                        + the exact refine loop                     spatial_index.rs:83-143
+// The index handle and its grid directory are built in gpk_gridindex.hip; polygonal x polygonal and lineal x point rows go through the
+// box-candidate join of gpk_bboxjoin.hip.
 //
 // Point x polygonal rows (the 10M x 1k headline) run as
 //   pip_tile   : a work-group classifies a tile of points (raster routing + LDS-compacted exact phase over
@@ -12,143 +13,21 @@
 //                work-group totals (no scan kernel).
 // (A single-pass variant with decoupled look-back was measured and was slower on MI355X: the in-order
 // commit makes finished work-groups hold their LDS/wave slots while they wait — see DESIGN.md.)
-#include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <type_traits>
 
 #include <rocprim/rocprim.hpp>
 
-#include <chrono>
-
 #include "gpk_device.h"
 #include "gpk_index.h"
 #include "gpk_candjoin.h"
 #include "gpk_pip.h"
-#include "gpk_polypoly.h"
-#include "gpk_contains.h"
-#include "gpk_lineal.h"
 #include "gpk_scan.h"
 #include "gpk_pipshared.h"
 
 namespace gpk {
-
-// ================================= index build ==================================================
-// stage 1 of the extent: one closed box per work-group (NaN = nothing but empty geometries), in the boxes' own format, so
-// that extent_kernel folds them like boxes (min / max are exact: the result does not depend on the split)
-__global__ __launch_bounds__(256) void extent_partial_kernel(const double4* __restrict__ bbox, int64_t n, double4* __restrict__ part) {
-    __shared__ double red[4][4];
-    double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double4 b = bbox[i];
-        if (b.x == b.x) {
-            mnx = fmin(mnx, b.x);
-            mny = fmin(mny, b.y);
-            mxx = fmax(mxx, b.z);
-            mxy = fmax(mxy, b.w);
-        }
-    }
-    mnx = dev::wave_min(mnx);
-    mny = dev::wave_min(mny);
-    mxx = dev::wave_max(mxx);
-    mxy = dev::wave_max(mxy);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = mnx;
-        red[1][wave] = mny;
-        red[2][wave] = mxx;
-        red[3][wave] = mxy;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) {
-            mnx = fmin(mnx, red[0][w]);
-            mny = fmin(mny, red[1][w]);
-            mxx = fmax(mxx, red[2][w]);
-            mxy = fmax(mxy, red[3][w]);
-        }
-        part[blockIdx.x] = mnx <= mxx ? make_double4(mnx, mny, mxx, mxy) : make_double4(NAN, NAN, NAN, NAN);
-    }
-}
-__global__ __launch_bounds__(1024) void extent_kernel(const double4* __restrict__ bbox, int64_t n,
-                                                      int gx, int gy, GridParams* __restrict__ out) {
-    __shared__ double red[4][16];
-    double mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) {
-        const double4 b = bbox[i];
-        if (b.x == b.x) {  // NaN marks an empty geometry
-            mnx = fmin(mnx, b.x);
-            mny = fmin(mny, b.y);
-            mxx = fmax(mxx, b.z);
-            mxy = fmax(mxy, b.w);
-        }
-    }
-    mnx = dev::wave_min(mnx);
-    mny = dev::wave_min(mny);
-    mxx = dev::wave_max(mxx);
-    mxy = dev::wave_max(mxy);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = mnx;
-        red[1][wave] = mny;
-        red[2][wave] = mxx;
-        red[3][wave] = mxy;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) {
-            mnx = fmin(mnx, red[0][w]);
-            mny = fmin(mny, red[1][w]);
-            mxx = fmax(mxx, red[2][w]);
-            mxy = fmax(mxy, red[3][w]);
-        }
-        GridParams g;
-        const bool any = mnx <= mxx;
-        g.x0 = any ? mnx : 0.0;
-        g.y0 = any ? mny : 0.0;
-        const double w = any ? mxx - mnx : 0.0, h = any ? mxy - mny : 0.0;
-        g.inv_w = w > 0.0 ? (double)gx / w : 0.0;
-        g.inv_h = h > 0.0 ? (double)gy / h : 0.0;
-        g.gx = gx;
-        g.gy = gy;
-        *out = g;
-    }
-}
-
-template <bool FILL>
-__global__ void grid_register_kernel(const double4* __restrict__ bbox, int64_t n,
-                                     const GridParams* __restrict__ gp, int32_t* __restrict__ cell_cnt,
-                                     int32_t* __restrict__ items) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const double4 b = bbox[j];
-    if (!(b.x == b.x)) return;
-    const GridParams g = *gp;
-    const int cx0 = dev::cell_of(b.x, g.x0, g.inv_w, g.gx), cx1 = dev::cell_of(b.z, g.x0, g.inv_w, g.gx);
-    const int cy0 = dev::cell_of(b.y, g.y0, g.inv_h, g.gy), cy1 = dev::cell_of(b.w, g.y0, g.inv_h, g.gy);
-    for (int cy = cy0; cy <= cy1; ++cy)
-        for (int cx = cx0; cx <= cx1; ++cx) {
-            const int c = cy * g.gx + cx;
-            const int slot = atomicAdd(&cell_cnt[c], 1);
-            if (FILL) items[slot] = (int32_t)j;
-        }
-}
-
-// ascending ids within each cell -> deterministic candidate order, hence sorted (l, r) output
-__global__ void cell_sort_kernel(const int32_t* __restrict__ cell_off, int64_t n_cells, int32_t* __restrict__ items) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_cells) return;
-    const int b = cell_off[c], e = cell_off[c + 1];
-    for (int i = b + 1; i < e; ++i) {
-        const int32_t key = items[i];
-        int k = i - 1;
-        while (k >= b && items[k] > key) {
-            items[k + 1] = items[k];
-            --k;
-        }
-        items[k + 1] = key;
-    }
-}
 
 // ================================= point-in-polygon join =========================================
 constexpr int PIP_BLOCK = 256;                 // threads per work-group of pip_tile
@@ -1482,499 +1361,7 @@ static unsigned long long* g_join_stats = nullptr;  // device: {queued (point, p
                                                     // a within-distance join (gpk_dwithin.hip, through CandRefine::refine) adds its candidates to [2] and the
                                                     // candidates its box test rejected to [3]
 static bool g_join_stats_on = false;
-static unsigned long long* join_stats_buffer() { return g_join_stats_on ? g_join_stats : nullptr; }
-
-// ================================= polygonal x polygonal join ======================================
-// Candidate generation of spatial_index.rs:74-76 for bbox-shaped left rows: every directory cell the left
-// bbox touches is visited; a pair seen in several cells is processed only in the cell that holds the lower
-// left corner of the two boxes' intersection (computed with the same monotone cell function, so that cell
-// is in both registration ranges).  The exact refine is Intersects<Polygon> (gpk_polypoly.h).
-template <typename F>
-__device__ __forceinline__ void for_each_bbox_candidate(const IndexView& ix, const GridParams& g, const double4 lb, F&& f) {
-    if (!(lb.x == lb.x)) return;  // empty left geometry
-    const int cx0 = dev::cell_of(lb.x, g.x0, g.inv_w, g.gx), cx1 = dev::cell_of(lb.z, g.x0, g.inv_w, g.gx);
-    const int cy0 = dev::cell_of(lb.y, g.y0, g.inv_h, g.gy), cy1 = dev::cell_of(lb.w, g.y0, g.inv_h, g.gy);
-    for (int cy = cy0; cy <= cy1; ++cy)
-        for (int cx = cx0; cx <= cx1; ++cx) {
-            const int c = cy * g.gx + cx;
-            auto visit = [&](int j, const double4 rb) {
-                if (lb.z < rb.x || lb.w < rb.y || rb.z < lb.x || rb.w < lb.y) return;  // closed-interval overlap test
-                const double rx = lb.x > rb.x ? lb.x : rb.x, ry = lb.y > rb.y ? lb.y : rb.y;
-                if (dev::cell_of(rx, g.x0, g.inv_w, g.gx) != cx || dev::cell_of(ry, g.y0, g.inv_h, g.gy) != cy) return;
-                f(j);
-            };
-            const int k1 = ix.cell_off[c + 1];
-            for (int k = ix.cell_off[c]; k < k1; k += 2) {  // two items per trip: both ids, then both boxes, in flight together
-                const bool two = k + 1 < k1;
-                const int j0 = ix.items[k], j1 = ix.items[two ? k + 1 : k];
-                const double4 b0 = ix.bbox[j0], b1 = ix.bbox[j1];
-                visit(j0, b0);
-                if (two) visit(j1, b1);
-            }
-        }
-}
-
-// Stage 1: candidates.  One lane per left row lists the right rows whose closed bbox overlaps the row's bbox
-// (count pass, then fill pass into the row's slice, sorted by right id: the hits then come out sorted).  Rows with a
-// handful of candidates sort their slice in place; a row with more than CAND_INLINE_SORT (one country against a
-// column of parcels) raises *big_rows in the count pass and every slice goes through one segmented radix sort instead.
-constexpr int CAND_INLINE_SORT = 48;
-template <bool WRITE>
-__global__ __launch_bounds__(256) void bbox_cand_kernel(DevGeo left, DevGeo right, IndexView ix, const double4* __restrict__ lbbox,
-                                                         int32_t* __restrict__ cand_cnt, const int32_t* __restrict__ cand_off,
-                                                         uint32_t* __restrict__ cand_r, uint32_t* __restrict__ cand_l,
-                                                         int32_t* __restrict__ big_rows) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= left.n_geoms) return;
-    int cnt = 0;
-    const int64_t o0 = WRITE ? (int64_t)cand_off[i] : 0;
-    if (dev::valid_row(left.validity, i)) {
-        const GridParams g = *ix.grid;
-        for_each_bbox_candidate(ix, g, lbbox[i], [&](int j) {
-            if (!dev::valid_row(right.validity, j)) return;
-            if (WRITE) cand_r[o0 + cnt] = (uint32_t)j;
-            ++cnt;
-        });
-    }
-    if (!WRITE) {
-        cand_cnt[i] = cnt;
-        if (cnt > CAND_INLINE_SORT) *big_rows = 1;
-        return;
-    }
-    for (int a = 1; a < cnt && cnt <= CAND_INLINE_SORT; ++a) {  // rows have a handful of candidates
-        const uint32_t key = cand_r[o0 + a];
-        int b = a - 1;
-        while (b >= 0 && cand_r[o0 + b] > key) {
-            cand_r[o0 + b + 1] = cand_r[o0 + b];
-            --b;
-        }
-        cand_r[o0 + b + 1] = key;
-    }
-    for (int a = 0; a < cnt; ++a) cand_l[o0 + a] = (uint32_t)i;  // left row of every candidate: the refine reads it directly
-}
-
-// One search instead of two for ordinary rows: the count pass also leaves each row's first CAND_STAGE candidates (sorted) in a padded
-// staging slice; when no row has more (nearly every join: rows have a handful), cand_compact_kernel moves the slices to their scanned
-// offsets and the second directory walk (bbox_cand_kernel<true>: 0.90 ms of the 6.1 ms C4 join) does not run.
-constexpr int CAND_STAGE = 16;
-static_assert(CAND_STAGE <= CAND_INLINE_SORT, "a staged row is one that the fill pass would have sorted inline");
-// Round 6: CAND_LANES lanes per left row.  One lane per row walked its cells' items as a chain of dependent requests — cell offsets, then
-// ids two at a time, then their boxes — about eight round trips a row with the lanes of a wave on rows of different lengths (0.82 ms
-// for the 1 M rows of C4); the lanes of a row now take the items of a cell side by side (ids together, boxes together: two round trips
-// a cell) and append their finds to the row's slice with one ballot.
-constexpr int CAND_LANES = 8;
-__global__ __launch_bounds__(256) void bbox_cand_stage_kernel(DevGeo left, DevGeo right, IndexView ix, const double4* __restrict__ lbbox,
-                                                               int32_t* __restrict__ cand_cnt, uint32_t* __restrict__ stage,
-                                                               int32_t* __restrict__ flags /* [0]: big rows, [1]: rows beyond CAND_STAGE */) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = t / CAND_LANES;
-    const int sub = (int)(threadIdx.x & (CAND_LANES - 1)), gbase = (int)(threadIdx.x & 63) & ~(CAND_LANES - 1);
-    if (i >= left.n_geoms) return;  // (whole groups: CAND_LANES divides the block)
-    int cnt = 0;
-    uint32_t* mine = stage + i * CAND_STAGE;
-    const double4 lb = lbbox[i];
-    if (dev::valid_row(left.validity, i) && lb.x == lb.x) {
-        const GridParams g = *ix.grid;
-        const int cx0 = dev::cell_of(lb.x, g.x0, g.inv_w, g.gx), cx1 = dev::cell_of(lb.z, g.x0, g.inv_w, g.gx);
-        const int cy0 = dev::cell_of(lb.y, g.y0, g.inv_h, g.gy), cy1 = dev::cell_of(lb.w, g.y0, g.inv_h, g.gy);
-        for (int cy = cy0; cy <= cy1; ++cy)
-            for (int cx = cx0; cx <= cx1; ++cx) {
-                const int c = cy * g.gx + cx;
-                const int k0 = ix.cell_off[c], k1 = ix.cell_off[c + 1];
-                for (int kb = k0; kb < k1; kb += CAND_LANES) {  // (group-uniform trip count)
-                    const int k = kb + sub;
-                    bool keep = false;
-                    int j = 0;
-                    if (k < k1) {
-                        j = ix.items[k];
-                        const double4 rb = ix.bbox[j];
-                        // closed-interval overlap, and the pair belongs to THIS cell: the one that holds the lower-left corner of the two
-                        // boxes' intersection (for_each_bbox_candidate)
-                        if (!(lb.z < rb.x || lb.w < rb.y || rb.z < lb.x || rb.w < lb.y)) {
-                            const double rx = lb.x > rb.x ? lb.x : rb.x, ry = lb.y > rb.y ? lb.y : rb.y;
-                            keep = dev::cell_of(rx, g.x0, g.inv_w, g.gx) == cx && dev::cell_of(ry, g.y0, g.inv_h, g.gy) == cy && dev::valid_row(right.validity, j);
-                        }
-                    }
-                    const uint32_t m = (uint32_t)((__ballot(keep) >> gbase) & ((1u << CAND_LANES) - 1u));
-                    const int at = cnt + __popc(m & ((1u << sub) - 1u));
-                    if (keep && at < CAND_STAGE) mine[at] = (uint32_t)j;  // (in directory order: cand_compact_kernel sorts the slice across its 16 lanes)
-                    cnt += __popc(m);
-                }
-            }
-    }
-    if (sub == 0) {
-        cand_cnt[i] = cnt;
-        if (cnt > CAND_STAGE) flags[1] = 1;
-        if (cnt > CAND_INLINE_SORT) flags[0] = 1;
-    }
-}
-// (a row with more than CAND_STAGE candidates — a dense cluster — walks the directory again, like bbox_cand_kernel<true>: one lane of
-// its CAND_STAGE; rows beyond CAND_INLINE_SORT send the whole join down the two-search path with its segmented sort)
-__global__ __launch_bounds__(256) void cand_compact_kernel(DevGeo left, DevGeo right, IndexView ix, const double4* __restrict__ lbbox,
-                                                            const int32_t* __restrict__ cand_cnt, const int32_t* __restrict__ cand_off,
-                                                            const uint32_t* __restrict__ stage, uint32_t* __restrict__ cand_r,
-                                                            uint32_t* __restrict__ cand_l) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = t / CAND_STAGE;
-    const int j = (int)(t % CAND_STAGE);
-    if (i >= left.n_geoms) return;
-    const int cnt = cand_cnt[i];
-    const int64_t o0 = (int64_t)cand_off[i];
-    if (cnt <= CAND_STAGE) {
-        // the row's slice, sorted by right id across the row's CAND_STAGE lanes: a bitonic network of ten shuffle steps (the count
-        // pass used to keep the slice sorted by insertion — a chain of dependent global loads per candidate)
-        static_assert(CAND_STAGE == 16, "the sorting network below is written for 16 lanes per row");
-        uint32_t v = j < cnt ? stage[t] : 0xFFFFFFFFu;
-#pragma unroll
-        for (int k = 2; k <= CAND_STAGE; k <<= 1) {
-#pragma unroll
-            for (int d = k >> 1; d > 0; d >>= 1) {
-                const uint32_t w = __shfl_xor(v, d, CAND_STAGE);
-                const bool keep_min = ((j & d) == 0) == ((j & k) == 0);
-                v = keep_min ? (v < w ? v : w) : (v > w ? v : w);
-            }
-        }
-        if (j < cnt) {
-            cand_r[o0 + j] = v;
-            cand_l[o0 + j] = (uint32_t)i;
-        }
-        return;
-    }
-    if (j != 0) return;
-    int m = 0;
-    const GridParams g = *ix.grid;
-    for_each_bbox_candidate(ix, g, lbbox[i], [&](int r) {
-        if (!dev::valid_row(right.validity, r)) return;
-        int b = m - 1;  // insertion into the ascending prefix
-        while (b >= 0 && cand_r[o0 + b] > (uint32_t)r) {
-            cand_r[o0 + b + 1] = cand_r[o0 + b];
-            --b;
-        }
-        cand_r[o0 + b + 1] = (uint32_t)r;
-        ++m;
-    });
-    for (int a = 0; a < m; ++a) cand_l[o0 + a] = (uint32_t)i;
-}
-
-// Stage 2: exact refine, JOIN_GS lanes per candidate pair (pairs are independent: the unit of parallelism is the
-// pair, not the row, so ragged candidate lists do not unbalance waves).
-constexpr int JOIN_GS = 16;
-__device__ __forceinline__ int64_t row_of_candidate(const int32_t* __restrict__ off, int64_t n_rows, int64_t c) {
-    int64_t lo = 0, hi = n_rows;  // largest row with off[row] <= c
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)off[mid] <= c)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-// (a minimum of four waves per SIMD — 128 registers instead of 141 — was 4 % faster, 4.06 -> 3.90 ms, and wrote 1.1 GB of spilled
-// registers per launch to scratch memory, WRITE_SIZE 9.7 MB -> 1.14 GB: not taken)
-__global__ __launch_bounds__(256, 1) void pair_refine_kernel(DevGeo left, DevGeo right, const uint32_t* __restrict__ cand_l,
-                                                           const uint32_t* __restrict__ cand_r, int64_t n_cand,
-                                                           const double4* __restrict__ lbbox, const double4* __restrict__ rbbox,
-                                                           uint8_t* __restrict__ hit, bool l_one_ring, bool r_one_ring) {
-    // (l_one_ring / r_one_ring: every polygon of that POLYGON column is known to have exactly one ring — ring r is geometry r)
-    // per group: the staging slice of the small-pair path, which doubles as the two in-window segment lists of the general one
-    static_assert(sizeof(PairSmallLds) >= 2 * PP_LIST * sizeof(double4), "the general routine's lists fit the small-pair slice");
-    __shared__ PairSmallLds slices[256 / JOIN_GS];
-    const int lane = threadIdx.x & (JOIN_GS - 1);
-    PairSmallLds* slice = slices + threadIdx.x / JOIN_GS;
-    const bool plain = left.type == GPK_GEOM_POLYGON && right.type == GPK_GEOM_POLYGON && lbbox && rbbox;  // (uniform)
-    // A group takes a CONTIGUOUS run of candidates: they are ordered by left row, so consecutive ones mostly share it and its ring stays
-    // staged (round 6; a group used to stride over the list, staging both rings of every pair)
-    const int64_t groups = (int64_t)gridDim.x * (256 / JOIN_GS);
-    const int64_t per = (n_cand + groups - 1) / groups, g_id = (int64_t)blockIdx.x * (256 / JOIN_GS) + threadIdx.x / JOIN_GS;
-    const int64_t c_lo = g_id * per, c_hi = c_lo + per < n_cand ? c_lo + per : n_cand;
-    int64_t staged_i = -1;  // the left row whose ring is in slice->a
-    for (int64_t c = c_lo; c < c_hi; ++c) {
-        const int64_t i = (int64_t)cand_l[c], j = (int64_t)cand_r[c];
-        bool h;
-        bool small = false;
-        int ca = 0, na = 0, cb = 0, nb = 0;
-        if (plain) {  // two single-ring polygons of at most PP_SMALL coordinates: the staged path (gpk_polypoly.h)
-            int ra0 = (int)i, ra1 = (int)i + 1, rb0 = (int)j, rb1 = (int)j + 1;
-            if (!l_one_ring) {
-                ra0 = left.geom_off[i];
-                ra1 = left.geom_off[i + 1];
-            }
-            if (!r_one_ring) {
-                rb0 = right.geom_off[j];
-                rb1 = right.geom_off[j + 1];
-            }
-            if (ra1 - ra0 == 1 && rb1 - rb0 == 1) {
-                ca = left.ring_off[ra0];
-                na = left.ring_off[ra0 + 1] - ca;
-                cb = right.ring_off[rb0];
-                nb = right.ring_off[rb0 + 1] - cb;
-                small = na >= 1 && nb >= 1 && na <= PP_SMALL && nb <= PP_SMALL;
-            }
-        }
-        if (small) {
-            h = polygon_pair_small<JOIN_GS>(left.xy + ca, na, right.xy + cb, nb, lbbox[i], rbbox[j], lane, slice, staged_i == i);
-            staged_i = i;
-        } else {
-            h = polygonal_intersects_polygonal_group<JOIN_GS>(left, i, right, j, lane, reinterpret_cast<double4*>(slice), lbbox, rbbox);
-            staged_i = -1;  // (the general routine keeps its segment lists in the slice)
-        }
-        if (lane == 0) hit[c] = h;
-    }
-}
-
-// Contains<Polygon> for Polygon / MultiPolygon (spatial_index.rs:99-101,107-111; gpk_contains.h): the right polygon can only
-// lie in a left geometry whose box holds its box, which settles most candidates of the (closed-overlap) candidate list.
-__global__ __launch_bounds__(256) void pair_contains_kernel(DevGeo left, DevGeo right, const uint32_t* __restrict__ cand_l,
-                                                             const uint32_t* __restrict__ cand_r, int64_t n_cand,
-                                                             const double4* __restrict__ lbbox, const double4* __restrict__ rbbox,
-                                                             uint8_t* __restrict__ hit) {
-    const int lane = threadIdx.x & (JOIN_GS - 1);
-    const int64_t groups = (int64_t)gridDim.x * (256 / JOIN_GS);
-    for (int64_t c = (int64_t)blockIdx.x * (256 / JOIN_GS) + threadIdx.x / JOIN_GS; c < n_cand; c += groups) {
-        const int64_t i = (int64_t)cand_l[c], j = (int64_t)cand_r[c];
-        const double4 lb = lbbox[i], rb = rbbox[j];
-        bool h = false;
-        if (rb.x >= lb.x && rb.y >= lb.y && rb.z <= lb.z && rb.w <= lb.w) h = cont::polygonal_contains_polygonal_group<JOIN_GS>(left, i, right, j, lane);
-        if (lane == 0) hit[c] = h;
-    }
-}
-
-__global__ __launch_bounds__(256) void lineal_point_refine_kernel(DevGeo left, DevGeo right, const uint32_t* __restrict__ cand_l,
-                                                                   const uint32_t* __restrict__ cand_r, int64_t n_cand,
-                                                                   uint8_t* __restrict__ hit) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_cand) return;
-    const int64_t i = cand_l[c], j = cand_r[c];
-    const bool point_left = left.type == GPK_GEOM_POINT;
-    const double2 p = point_left ? left.xy[i] : right.xy[j];
-    bool h = false;
-    if (p.x == p.x && p.y == p.y) h = point_left ? lineal_contains_point(right, j, p.x, p.y) : lineal_contains_point(left, i, p.x, p.y);
-    hit[c] = h;
-}
-
-// Stage 3: per-row hit counts, then (after a scan) the (l, r) pairs in candidate order == sorted by (l, r).
-template <bool WRITE>
-__global__ __launch_bounds__(256) void pair_emit_kernel(int64_t n_rows, const int32_t* __restrict__ cand_off,
-                                                         const uint32_t* __restrict__ cand_r, const uint8_t* __restrict__ hit,
-                                                         int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
-                                                         uint32_t left_base, uint2* __restrict__ pairs, int64_t capacity) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    int cnt = 0;
-    const int64_t o0 = WRITE ? (int64_t)offsets[i] : 0;
-    for (int c = cand_off[i]; c < cand_off[i + 1]; ++c) {
-        if (!hit[c]) continue;
-        if (WRITE && o0 + cnt < capacity) pairs[o0 + cnt] = make_uint2(left_base + (uint32_t)i, cand_r[c]);
-        ++cnt;
-    }
-    if (!WRITE) counts[i] = cnt;
-}
-
-__global__ void i32_to_u32_copy_kernel(const int32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (uint32_t)in[i];
-}
-
-// ================================= host drivers ================================================
-static inline dim3 grid_for(int64_t n, int block) {
-    int64_t b = (n + block - 1) / block;
-    return dim3((unsigned)(b > 0 ? b : 1));
-}
-
-// polygonal x polygonal: candidates (count, scan, fill) -> pair-parallel exact refine -> hits (count, scan, emit)
-enum { REFINE_POLYGONAL = 0, REFINE_LINEAL_POINT = 1, REFINE_CONTAINS = 2, REFINE_ENVELOPE_INTERSECTS = 3, REFINE_ENVELOPE_CONTAINED = 4, REFINE_EXTERNAL = 5 };
-// gpk_index_query_envelope's refine (rstar's locate_in_envelope_intersecting / locate_in_envelope, spatial_index.rs:385-387,424-426): a
-// candidate's box already meets the query box (closed intervals: for_each_bbox_candidate); `contained` additionally asks that it lies
-// inside it, bounds included (rstar AABB::contains_envelope)
-__global__ __launch_bounds__(256) void query_boxes_kernel(const double4* __restrict__ in, int64_t n, double4* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double4 b = in[i];
-    const bool nan = !(b.x == b.x && b.y == b.y && b.z == b.z && b.w == b.w);
-    out[i] = nan ? make_double4(NAN, NAN, NAN, NAN) : make_double4(fmin(b.x, b.z), fmin(b.y, b.w), fmax(b.x, b.z), fmax(b.y, b.w));
-}
-__global__ __launch_bounds__(256) void envelope_refine_kernel(const uint32_t* __restrict__ cand_l, const uint32_t* __restrict__ cand_r, int64_t n,
-                                                               const double4* __restrict__ lbbox, const double4* __restrict__ rbbox, int contained,
-                                                               uint8_t* __restrict__ hit) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double4 lb = lbbox[cand_l[i]], rb = rbbox[cand_r[i]];
-    bool ok = rb.x == rb.x && lb.x == lb.x;
-    if (contained) ok = ok && rb.x >= lb.x && rb.z <= lb.z && rb.y >= lb.y && rb.w <= lb.w;
-    hit[i] = ok ? 1 : 0;
-}
-static int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, uint32_t left_row_base,
-                         uint32_t* out_counts, uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space,
-                         hipStream_t s, int refine = REFINE_POLYGONAL, const double4* given_lbbox = nullptr, const CandRefine* ext = nullptr) {
-    // (ext: the refine of another translation unit, REFINE_EXTERNAL — gpk_candjoin.h; the arms of this file pass none)
-    const int64_t n = left->d.n_geoms;
-    const char* what = ext ? ext->name : "spatial_join";
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    const bool want_pairs = pair_capacity > 0;
-    // per-call allocations that outlive a workspace reset (gpk_bounds uses the workspace itself)
-    void* owned[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto done = [&](int32_t rc) {
-        for (void* p : owned)
-            if (p) (void)hipFree(p);
-        return rc;
-    };
-    // left boxes and the candidate buffers live in the thread's auxiliary arenas (no hipMalloc / hipFree per call)
-    // (given_lbbox: gpk_index_query_envelope hands its query boxes over — in device memory — in the left boxes' place)
-    double4* lbbox = const_cast<double4*>(given_lbbox);
-    int32_t rc = GPK_OK;
-    if (!given_lbbox) {
-        GPK_TRY(workspace_aux(0).begin(sizeof(double4) * (size_t)n + 256));
-        lbbox = (double4*)workspace_aux(0).take(sizeof(double4) * (size_t)n);
-        rc = gpk_bounds(left, (double*)lbbox, GPK_MEM_DEVICE, (void*)s);
-        if (rc != GPK_OK) return done(rc);
-    }
-    const int64_t nb = (n + 255) / 256;
-    const size_t pairs_bytes = sizeof(uint32_t) * 2 * (size_t)pair_capacity;
-    const size_t i32n = align256(sizeof(int32_t) * (size_t)(n + 1));
-    size_t need = 4 * i32n + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + 256 + 1024;
-    if (host_out && out_counts) need += align256(sizeof(uint32_t) * (size_t)n);
-    if (host_out && want_pairs) need += align256(pairs_bytes);
-    // (padded staging of the candidates: up to 512 MB — 8M left rows; beyond that the two-search path)
-    const size_t stage_bytes = sizeof(uint32_t) * CAND_STAGE * (size_t)(n > 0 ? n : 1);
-    const bool staged = stage_bytes <= (size_t(512) << 20);
-    if (staged) need += align256(stage_bytes);
-    rc = workspace().begin(need);
-    if (rc != GPK_OK) return done(rc);
-    int32_t* cand_cnt = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* cand_off = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* counts = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* offsets = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
-    int32_t* big_rows = (int32_t*)workspace().take(256);
-    uint32_t* counts_out = out_counts ? (host_out ? (uint32_t*)workspace().take(sizeof(uint32_t) * (size_t)n) : out_counts) : nullptr;
-    uint32_t* pairs_dev = want_pairs ? (host_out ? (uint32_t*)workspace().take(pairs_bytes) : out_pairs) : nullptr;
-    uint32_t* stage = staged ? (uint32_t*)workspace().take(stage_bytes) : nullptr;
-
-    int32_t n_cand = 0, has_big_rows = 0;
-    unsigned long long cand_total = 0;  // the 64-bit grand total of the scan: cand_off[n] is its truncation to i32
-    auto stage1 = [&]() -> int32_t {
-        GPK_HIP(hipMemsetAsync(big_rows, 0, 2 * sizeof(int32_t), s));
-        if (staged)
-            GPK_LAUNCH("gpk_bbox_cand_count", bbox_cand_stage_kernel, dim3((unsigned)((n * CAND_LANES + 255) / 256)), dim3(256), 0, s, left->d, right->d,
-                       right_index->v, lbbox, cand_cnt, stage, big_rows);
-        else
-            GPK_LAUNCH("gpk_bbox_cand_count", bbox_cand_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, left->d, right->d, right_index->v,
-                       lbbox, cand_cnt, (const int32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, big_rows);
-        GPK_TRY(exclusive_scan_i32(cand_cnt, n, cand_off, nullptr, btot, s));
-        int32_t fl[2] = {0, 0};
-        GPK_HIP(hipMemcpyAsync(&cand_total, btot + nb, sizeof cand_total, hipMemcpyDeviceToHost, s));
-        GPK_HIP(hipMemcpyAsync(fl, big_rows, sizeof fl, hipMemcpyDeviceToHost, s));
-        GPK_HIP(hipStreamSynchronize(s));
-        has_big_rows = fl[0];
-        return GPK_OK;
-    };
-    rc = stage1();
-    if (rc != GPK_OK) return done(rc);
-    // candidate offsets are i32 (one slice per left row): more than 2^31 - 1 bbox candidates cannot be addressed
-    if (cand_total > (unsigned long long)INT32_MAX)
-        return done(fail(GPK_ERR_CAPACITY, "%s: %llu bbox candidates exceed the i32 candidate offsets: shard the left side", what, cand_total));
-    n_cand = (int32_t)cand_total;
-    uint32_t *cand_r = nullptr, *cand_l = nullptr, *cand_sorted = nullptr;
-    uint8_t* hit = nullptr;
-    void *seg_tmp = nullptr, *ext_scratch = nullptr;
-    size_t seg_bytes = 0;
-    unsigned seg_bits = 1;
-    while (seg_bits < 32 && ((int64_t)1 << seg_bits) < right->d.n_geoms) ++seg_bits;
-    {
-        const size_t nc1 = (size_t)(n_cand > 0 ? n_cand : 1);
-        if (has_big_rows) {
-            const hipError_t qe = rocprim::segmented_radix_sort_keys(nullptr, seg_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned)n_cand,
-                                                                     (unsigned)n, (const int32_t*)cand_off, (const int32_t*)cand_off + 1, 0, seg_bits, s);
-            if (qe != hipSuccess) return done(fail(GPK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(qe)));
-        }
-        const size_t ext_bytes = ext ? align256(ext->scratch_fixed + ext->scratch_per_cand * nc1) : 0;
-        rc = workspace_aux(1).begin((has_big_rows ? 3 : 2) * align256(sizeof(uint32_t) * nc1) + align256(nc1) + align256(seg_bytes) + ext_bytes + 512);
-        if (rc != GPK_OK) return done(rc);
-        cand_r = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
-        cand_l = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
-        hit = (uint8_t*)workspace_aux(1).take(nc1);
-        if (has_big_rows) {
-            cand_sorted = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
-            seg_tmp = workspace_aux(1).take(seg_bytes ? seg_bytes : 1);
-        }
-        if (ext) ext_scratch = workspace_aux(1).take(ext_bytes);
-    }
-    auto stage23 = [&]() -> int32_t {
-        if (staged && !has_big_rows)
-            GPK_LAUNCH("gpk_cand_compact", cand_compact_kernel, dim3((unsigned)((n * CAND_STAGE + 255) / 256)), dim3(256), 0, s, left->d, right->d,
-                       right_index->v, (const double4*)lbbox, (const int32_t*)cand_cnt, (const int32_t*)cand_off, (const uint32_t*)stage, cand_r, cand_l);
-        else
-            GPK_LAUNCH("gpk_bbox_cand_fill", bbox_cand_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, left->d, right->d, right_index->v,
-                       lbbox, cand_cnt, (const int32_t*)cand_off, cand_r, cand_l, big_rows);
-        if (has_big_rows && n_cand > 0) {  // some slice is long: sort every slice by right id, segment = left row
-            GPK_HIP(rocprim::segmented_radix_sort_keys(seg_tmp, seg_bytes, (const uint32_t*)cand_r, cand_sorted, (unsigned)n_cand, (unsigned)n,
-                                                       (const int32_t*)cand_off, (const int32_t*)cand_off + 1, 0, seg_bits, s));
-            cand_r = cand_sorted;
-        }
-        if (n_cand > 0) {
-            int64_t blocks = ((int64_t)n_cand + (256 / JOIN_GS) - 1) / (256 / JOIN_GS);
-            const int64_t cap = (int64_t)cu_count() * 64;
-            if (blocks > cap) blocks = cap;
-            if (refine == REFINE_EXTERNAL)
-                GPK_TRY(ext->refine(ext->ctx, cand_l, cand_r, n_cand, ext_scratch, hit, join_stats_buffer(), s));
-            else if (refine == REFINE_ENVELOPE_INTERSECTS || refine == REFINE_ENVELOPE_CONTAINED)
-                GPK_LAUNCH("gpk_envelope_refine", envelope_refine_kernel, dim3((unsigned)(((int64_t)n_cand + 255) / 256)), dim3(256), 0, s,
-                           (const uint32_t*)cand_l, (const uint32_t*)cand_r, (int64_t)n_cand, (const double4*)lbbox, right_index->v.bbox,
-                           refine == REFINE_ENVELOPE_CONTAINED ? 1 : 0, hit);
-            else if (refine == REFINE_LINEAL_POINT)
-                GPK_LAUNCH("gpk_lineal_point_refine", lineal_point_refine_kernel, dim3((unsigned)(((int64_t)n_cand + 255) / 256)), dim3(256), 0, s,
-                           left->d, right->d, (const uint32_t*)cand_l, (const uint32_t*)cand_r, (int64_t)n_cand, hit);
-            else if (refine == REFINE_CONTAINS)
-                GPK_LAUNCH("gpk_pair_contains", pair_contains_kernel, dim3((unsigned)blocks), dim3(256), 0, s, left->d, right->d,
-                           (const uint32_t*)cand_l, (const uint32_t*)cand_r, (int64_t)n_cand, (const double4*)lbbox,
-                           right_index->v.bbox, hit);
-            else
-                GPK_LAUNCH("gpk_pair_refine", pair_refine_kernel, dim3((unsigned)blocks), dim3(256), 0, s, left->d, right->d,
-                           (const uint32_t*)cand_l, (const uint32_t*)cand_r, (int64_t)n_cand, (const double4*)lbbox,
-                           right_index->v.bbox, hit, left->d.type == GPK_GEOM_POLYGON && left->classes && left->classes->one_to_one,
-                           right->d.type == GPK_GEOM_POLYGON && right->classes && right->classes->one_to_one);
-        }
-        GPK_LAUNCH("gpk_pair_count", pair_emit_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, n, (const int32_t*)cand_off,
-                   (const uint32_t*)cand_r, (const uint8_t*)hit, counts, (const int32_t*)nullptr, left_row_base, (uint2*)nullptr, (int64_t)0);
-        GPK_TRY(exclusive_scan_i32(counts, n, offsets, nullptr, btot, s));
-        if (counts_out)
-            GPK_LAUNCH("gpk_counts_copy", i32_to_u32_copy_kernel, dim3((unsigned)nb), dim3(256), 0, s, counts, counts_out, n);
-        if (want_pairs)
-            GPK_LAUNCH("gpk_pair_emit", pair_emit_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, n, (const int32_t*)cand_off,
-                       (const uint32_t*)cand_r, (const uint8_t*)hit, counts, (const int32_t*)offsets, left_row_base, (uint2*)pairs_dev,
-                       pair_capacity);
-        if (want_pairs && ext && ext->emitted) GPK_TRY(ext->emitted(ext->ctx, n, cand_off, hit, offsets, ext_scratch, pair_capacity, s));
-        return GPK_OK;
-    };
-    rc = stage23();
-    if (rc != GPK_OK) return done(rc);
-    unsigned long long total = 0;  // 64-bit grand total of the hit scan (hits <= candidates <= INT32_MAX, checked above)
-    hipError_t e = hipMemcpyAsync(&total, btot + nb, sizeof total, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return done(fail(GPK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e)));
-    *n_pairs = (int64_t)total;
-    if (host_out) {
-        if (out_counts) {
-            rc = copy_out(out_counts, out_space, counts_out, sizeof(uint32_t) * (size_t)n, s);
-            if (rc != GPK_OK) return done(rc);
-        }
-        if (want_pairs) {
-            const int64_t w = (int64_t)total < pair_capacity ? (int64_t)total : pair_capacity;
-            rc = copy_out(out_pairs, out_space, pairs_dev, sizeof(uint32_t) * 2 * (size_t)w, s);
-            if (rc != GPK_OK) return done(rc);
-        }
-    }
-    if (want_pairs && (int64_t)total > pair_capacity)
-        return done(fail(GPK_ERR_CAPACITY, "%s: %lld pairs but capacity %lld", what, (long long)total, (long long)pair_capacity));
-    return done(GPK_OK);
-}
-int32_t bbox_join_refined(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, uint32_t left_row_base,
-                          uint32_t* out_counts, uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, hipStream_t s,
-                          const double4* lbbox, const CandRefine& refine) {
-    return bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, REFINE_EXTERNAL, lbbox,
-                     &refine);
-}
+unsigned long long* join_stats_buffer() { return g_join_stats_on ? g_join_stats : nullptr; }
 
 // The epoch words of the fused point joins: one buffer per device (zeroed when created; a launch's tag is never 0), a process-wide
 // launch counter, and an event that keeps launches from DIFFERENT streams apart — they share the words, and two such launches
@@ -2131,17 +1518,6 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
     uint32_t* counts_dev = out_counts ? (host_out ? (uint32_t*)ws.take(counts_bytes) : out_counts) : nullptr;
     uint32_t* pairs_dev = want_pairs ? (host_out ? (uint32_t*)ws.take(pairs_bytes) : out_pairs) : nullptr;
 
-
-#define J_LAUNCH(...)                          \
-    do {                                       \
-        auto _f = [&]() -> int32_t {           \
-            GPK_LAUNCH(__VA_ARGS__);           \
-            return GPK_OK;                     \
-        };                                     \
-        int32_t _rc = _f();                    \
-        if (_rc != GPK_OK) return _rc;         \
-    } while (0)
-
     unsigned long long* stats = join_stats_buffer();  // nullptr unless gpk_join_stats_enable(1)
     if (fused) {  // nothing to zero; the rare arm's arguments are written when they differ from what this arena holds
         struct {
@@ -2154,11 +1530,11 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
         want_cold.ix = right_index->v;
         want_cold.serial = right_index->serial;
         if (!ws.tag_matches(cold, &want_cold, sizeof want_cold)) {
-            J_LAUNCH("gpk_join_prep", join_prep_kernel, dim3(1), dim3(256), 0, s, stot, 0, cold, right->d, right_index->v);
+            GPK_LAUNCH("gpk_join_prep", join_prep_kernel, dim3(1), dim3(256), 0, s, stot, 0, cold, right->d, right_index->v);
             ws.set_tag(cold, &want_cold, sizeof want_cold);
         }
     } else if (chain) {  // totals zeroed and the rare arm's arguments written by one small launch
-        J_LAUNCH("gpk_join_prep", join_prep_kernel, dim3(1), dim3(256), 0, s, stot, n_super + 2, cold, right->d, right_index->v);
+        GPK_LAUNCH("gpk_join_prep", join_prep_kernel, dim3(1), dim3(256), 0, s, stot, n_super + 2, cold, right->d, right_index->v);
     } else {
         const hipError_t me = hipMemsetAsync(stot, 0, sizeof(unsigned long long) * (size_t)(n_super + 2), s);  // (+ grand, multi_top)
         if (me != hipSuccess) return fail(GPK_ERR_DEVICE, "spatial_join: %s", hipGetErrorString(me));
@@ -2223,30 +1599,29 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
         return GPK_OK;
     }
     if (chain)
-        J_LAUNCH("gpk_pip_tile", pip_tile_chain_kernel, dim3((unsigned)((n_blocks + PIP_BLOCK / 64 - 1) / (PIP_BLOCK / 64))), dim3(PIP_BLOCK), 0, s, hot);
+        GPK_LAUNCH("gpk_pip_tile", pip_tile_chain_kernel, dim3((unsigned)((n_blocks + PIP_BLOCK / 64 - 1) / (PIP_BLOCK / 64))), dim3(PIP_BLOCK), 0, s, hot);
     else if (lean)
-        J_LAUNCH("gpk_pip_tile", pip_tile_lean_kernel, dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d, right_index->v, pvj,
+        GPK_LAUNCH("gpk_pip_tile", pip_tile_lean_kernel, dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d, right_index->v, pvj,
                  counts_dev, code, btot, stot, stats);
     else if (right_index->pip.R > 0)
         if (right_index->pip.sub2 && one_per_lane)
-            J_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, true, 1>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
+            GPK_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, true, 1>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
                      right_index->v, pvj, counts_dev, code, btot, stot, multi_pool, multi_cap, multi_top, stats);
         else if (right_index->pip.sub2)
-            J_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, true>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
+            GPK_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, true>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
                      right_index->v, pvj, counts_dev, code, btot, stot, multi_pool, multi_cap, multi_top, stats);
         else if (one_per_lane)
-            J_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, false, 1>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
+            GPK_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, false, 1>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
                      right_index->v, pvj, counts_dev, code, btot, stot, multi_pool, multi_cap, multi_top, stats);
         else
-            J_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, false>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
+            GPK_LAUNCH("gpk_pip_tile", (pip_tile_kernel<true, false>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
                      right_index->v, pvj, counts_dev, code, btot, stot, multi_pool, multi_cap, multi_top, stats);
     else
-        J_LAUNCH("gpk_pip_tile_generic", (pip_tile_kernel<false, false>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
+        GPK_LAUNCH("gpk_pip_tile_generic", (pip_tile_kernel<false, false>), dim3((unsigned)n_blocks), dim3(PIP_BLOCK), 0, s, left->d, right->d,
                  right_index->v, pvj, counts_dev, code, btot, stot, multi_pool, multi_cap, multi_top, stats);
     // the writer also produces the grand total; in count-only mode it runs without a pair buffer
-    J_LAUNCH("gpk_pip_write", pip_write_kernel, dim3((unsigned)n_wblocks), dim3(WR_BLOCK), 0, s, left->d, right->d, right_index->v,
+    GPK_LAUNCH("gpk_pip_write", pip_write_kernel, dim3((unsigned)n_wblocks), dim3(WR_BLOCK), 0, s, left->d, right->d, right_index->v,
              code, btot, stot, (const uint32_t*)multi_pool, n_blocks, tile_points, left_row_base, (uint2*)pairs_dev, pair_capacity, grand, total_out);
-#undef J_LAUNCH
 
     *counts_dev_out = counts_dev;
     *pairs_dev_out = pairs_dev;
@@ -2292,15 +1667,7 @@ static int32_t swapped_pip_join(const gpk_geoarray* polys, const gpk_geoarray* p
     const bool want_pairs = pair_capacity > 0;
     *n_pairs = 0;
     if (n_left == 0) return GPK_OK;
-    if (n_pts == 0) {  // nothing on the right: every polygon has zero hits
-        if (out_counts) {
-            if (host_out)
-                memset(out_counts, 0, sizeof(uint32_t) * (size_t)n_left);
-            else
-                GPK_HIP(hipMemsetAsync(out_counts, 0, sizeof(uint32_t) * (size_t)n_left, s));
-        }
-        return GPK_OK;
-    }
+    if (n_pts == 0) return zero_counts(out_counts, n_left, out_space, s);  // nothing on the right: every polygon has zero hits
     gpk_index* lix = nullptr;
     GPK_TRY(gpk_index_build(polys, (void*)s, &lix));
     auto done = [&](int32_t rc) {
@@ -2340,18 +1707,12 @@ static int32_t swapped_pip_join(const gpk_geoarray* polys, const gpk_geoarray* p
         if (counts_dev && n_left > 0)
             GPK_LAUNCH("gpk_swap_counts", swap_counts_kernel, dim3((unsigned)((n_left + 255) / 256)), dim3(256), 0, s,
                        (const unsigned long long*)sorted, total, n_left, counts_dev);
-        if (host_out) {
-            if (out_counts) GPK_TRY(copy_out(out_counts, out_space, counts_dev, 4 * (size_t)n_left, s));
-            if (want_pairs) GPK_TRY(copy_out(out_pairs, out_space, pairs_dev, 8 * (size_t)(total < pair_capacity ? total : pair_capacity), s));
-        }
         GPK_HIP(hipStreamSynchronize(s));
         return GPK_OK;
     };
     rc = run();
     if (rc != GPK_OK) return done(rc);
-    if (want_pairs && total > pair_capacity)
-        return done(fail(GPK_ERR_CAPACITY, "spatial_join: %lld pairs but capacity %lld", (long long)total, (long long)pair_capacity));
-    return done(GPK_OK);
+    return done(finish_pairs("spatial_join", total, n_left, out_counts, counts_dev, out_pairs, (const uint32_t*)pairs_dev, pair_capacity, n_pairs, out_space, s));
 }
 
 }  // namespace gpk
@@ -2390,216 +1751,6 @@ int32_t gpk_join_trace(unsigned long long* out, int64_t n_words) {  // the raw s
     return GPK_OK;
 }
 
-int32_t gpk_index_query_envelope(const gpk_index* idx, const double* boxes4, int64_t n_boxes, int32_t mode, uint32_t* out_counts,
-                                 uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t space, void* stream) {
-    if (!idx || !n_pairs || (n_boxes > 0 && !boxes4)) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (mode != GPK_QUERY_CONTAINED && mode != GPK_QUERY_INTERSECTING) return fail(GPK_ERR_INVALID_ARGUMENT, "unknown envelope query mode %d", mode);
-    if (n_boxes < 0 || pair_capacity < 0 || (pair_capacity > 0 && !out_pairs)) return fail(GPK_ERR_INVALID_ARGUMENT, "bad sizes");
-    if (n_boxes > (int64_t)0x7FFFFFF0ll) return fail(GPK_ERR_INVALID_ARGUMENT, "more than 2^31 query boxes");
-    *n_pairs = 0;
-    GPK_TRY(require_device());
-    if (n_boxes == 0) return GPK_OK;
-    hipStream_t s = (hipStream_t)stream;
-    // the queries take the left rows' place in the box join, the index's own array the right rows' (the index holds the leaves: no
-    // geometry is read); null and empty rows of the indexed array have NaN boxes and are in no directory cell
-    gpk_geoarray left, right;
-    memset(&left, 0, sizeof left);
-    memset(&right, 0, sizeof right);
-    left.d.type = GPK_GEOM_POINT;
-    left.d.n_geoms = n_boxes;
-    left.device = right.device = idx->device;
-    right.d.type = idx->geom_type;
-    right.d.n_geoms = idx->n_geoms;
-    // the queries in the library's own memory, corners ordered the way `AABB::from_corners` orders them (lower = the component-wise
-    // minimum of the two corners, upper = the maximum)
-    GPK_TRY(workspace_aux(0).begin(2 * (sizeof(double4) * (size_t)n_boxes + 256)));
-    double4* boxes_dev = (double4*)workspace_aux(0).take(sizeof(double4) * (size_t)n_boxes);
-    const double4* src = reinterpret_cast<const double4*>(boxes4);
-    if (space != GPK_MEM_DEVICE) {
-        double4* up = (double4*)workspace_aux(0).take(sizeof(double4) * (size_t)n_boxes);
-        GPK_HIP(hipMemcpyAsync(up, boxes4, sizeof(double4) * (size_t)n_boxes, hipMemcpyHostToDevice, s));
-        src = up;
-    }
-    GPK_LAUNCH("gpk_query_boxes", query_boxes_kernel, dim3((unsigned)((n_boxes + 255) / 256)), dim3(256), 0, s, src, n_boxes, boxes_dev);
-    return bbox_join(&left, &right, idx, 0u, out_counts, out_pairs, pair_capacity, n_pairs, space, s,
-                     mode == GPK_QUERY_CONTAINED ? REFINE_ENVELOPE_CONTAINED : REFINE_ENVELOPE_INTERSECTS, boxes_dev);
-}
-
-int32_t gpk_index_free(gpk_index* idx) {
-    if (!idx) return GPK_OK;
-    // (hipFree's implicit wait, once: a join enqueued against this index may still be running — on the device that OWNS the tables,
-    // which need not be the calling thread's current one: the blocks go back to a process-wide cache tagged by device)
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (cur != idx->device) (void)hipSetDevice(idx->device);
-    (void)hipDeviceSynchronize();
-    for (int i = 0; i < 24; ++i)
-        if (idx->owned[i]) cached_free(idx->owned[i]);
-    if (cur >= 0 && cur != idx->device) (void)hipSetDevice(cur);
-    delete idx;
-    return GPK_OK;
-}
-
-int32_t gpk_index_describe(const gpk_index* idx, int64_t out[8]) {
-    if (!idx || !out) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    out[0] = idx->pip.R;
-    out[1] = idx->pip_lean;
-    out[2] = idx->pip.chain_xy != nullptr;
-    out[3] = idx->pip.route != nullptr;
-    out[4] = idx->pip_list_heavy;
-    return GPK_OK;
-}
-
-int32_t gpk_index_nbytes(const gpk_index* idx, int64_t* out_bytes) {
-    if (!idx || !out_bytes) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out_bytes = idx->nbytes;
-    return GPK_OK;
-}
-
-int32_t gpk_index_build(const gpk_geoarray* a, void* stream, gpk_index** out) {
-    return gpk_index_build_ex(a, GPK_INDEX_BBOX_GRID | GPK_INDEX_PIP, nullptr, stream, out);
-}
-
-int32_t gpk_index_build_ex(const gpk_geoarray* a, int32_t parts, const double* bbox4_dev, void* stream, gpk_index** out) {
-    if (!a || !out) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out = nullptr;
-    GPK_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n = a->d.n_geoms;
-
-    gpk_index* ix = new gpk_index;
-    memset(ix, 0, sizeof *ix);
-    ix->device = a->device;
-    ix->n_geoms = n;
-    ix->geom_type = a->d.type;
-    ix->n_coords = a->d.n_coords;
-    ix->n_rings = a->d.n_rings;
-    {
-        static std::atomic<uint64_t> next_serial{1};
-        ix->serial = next_serial.fetch_add(1);
-    }
-
-    // grid resolution: ~2 cells per geometry along each axis of a square layout
-    int gdim = (int)ceil(2.0 * sqrt((double)(n > 0 ? n : 1)));
-    if (gdim < 1) gdim = 1;
-    if (gdim > 2048) gdim = 2048;
-    const int64_t n_cells = (int64_t)gdim * gdim;
-
-    auto cleanup = [&](int32_t rc) {
-        gpk_index_free(ix);
-        return rc;
-    };
-#define IX_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return cleanup(fail(_e == hipErrorOutOfMemory ? GPK_ERR_OOM : GPK_ERR_DEVICE,         \
-                                "%s failed: %s", #expr, hipGetErrorString(_e)));                  \
-    } while (0)
-#define IX_TRY(expr)                             \
-    do {                                         \
-        int32_t _rc = (expr);                    \
-        if (_rc != GPK_OK) return cleanup(_rc);  \
-    } while (0)
-// a failed launch must release the half-built index too (GPK_LAUNCH returns from the enclosing function)
-#define IX_LAUNCH(...)                           \
-    do {                                         \
-        auto _f = [&]() -> int32_t {             \
-            GPK_LAUNCH(__VA_ARGS__);             \
-            return GPK_OK;                       \
-        };                                       \
-        int32_t _rc = _f();                      \
-        if (_rc != GPK_OK) return cleanup(_rc);  \
-    } while (0)
-
-    const bool dbg_time = getenv("GPK_DEBUG_INDEX") != nullptr;  // wall time of the directory phases (the stream is drained per stamp)
-    auto t_last = std::chrono::steady_clock::now();
-    auto stamp = [&](const char* what) {
-        if (!dbg_time) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[gpk] index build: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-    double4* bbox = nullptr;
-    GridParams* grid = nullptr;
-    int32_t* cell_off = nullptr;
-    IX_HIP(cached_malloc((void**)&bbox, sizeof(double4) * (size_t)(n > 0 ? n : 1)));
-    ix->owned[0] = bbox;
-    IX_HIP(cached_malloc((void**)&grid, sizeof(GridParams)));
-    ix->owned[1] = grid;
-    IX_HIP(cached_malloc((void**)&cell_off, sizeof(int32_t) * (size_t)(n_cells + 1)));
-    ix->owned[2] = cell_off;
-
-    // 1. bounding boxes (NodeEnvelope, spatial_index.rs:212-312) — or the caller's (the leaves another rank built and
-    //    sent over xGMI: dist.all_gather_leaves)
-    if (bbox4_dev)
-        IX_HIP(hipMemcpyAsync(bbox, bbox4_dev, sizeof(double4) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    else
-        IX_TRY(gpk_bounds(a, (double*)bbox, GPK_MEM_DEVICE, stream));
-
-    stamp("boxes (gpk_bounds)");
-    // 2. extent + grid parameters, all on device (two stages beyond a few thousand boxes: one work-group walked 5M of them in 4.7 ms)
-    const int64_t n_blocks = (n_cells + 255) / 256;
-    const int64_t ext_blocks = n > 65536 ? 1024 : 0;
-    IX_TRY(workspace().begin(align256(sizeof(int32_t) * (size_t)(n_cells + 1)) * 2 +
-                             align256(sizeof(unsigned long long) * (size_t)(n_blocks + 1)) + align256(sizeof(double4) * 1024) + 1024));
-    int32_t* cell_cnt = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_cells + 1));
-    int32_t* cursor = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_cells + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(n_blocks + 1));
-    double4* ext_part = (double4*)workspace().take(sizeof(double4) * 1024);
-    if (ext_blocks) {
-        IX_LAUNCH("gpk_index_extent_partial", extent_partial_kernel, dim3((unsigned)ext_blocks), dim3(256), 0, s, bbox, n, ext_part);
-        IX_LAUNCH("gpk_index_extent", extent_kernel, dim3(1), dim3(1024), 0, s, (const double4*)ext_part, ext_blocks, gdim, gdim, grid);
-    } else {
-        IX_LAUNCH("gpk_index_extent", extent_kernel, dim3(1), dim3(1024), 0, s, bbox, n, gdim, gdim, grid);
-    }
-
-    stamp("extent");
-    // 3. count, scan, fill, sort
-    IX_HIP(hipMemsetAsync(cell_cnt, 0, sizeof(int32_t) * (size_t)(n_cells + 1), s));
-    if (n > 0)
-        IX_LAUNCH("gpk_index_count", grid_register_kernel<false>, grid_for(n, 256), dim3(256), 0, s, bbox, n, grid, cell_cnt, (int32_t*)nullptr);
-    IX_TRY(exclusive_scan_i32(cell_cnt, n_cells, cell_off, cursor, btot, s));
-    unsigned long long total = 0;
-    IX_HIP(d2h_small(&total, btot + n_blocks, sizeof total, s));
-    IX_HIP(d2h_small(&ix->host_grid, grid, sizeof(GridParams), s));
-    IX_HIP(sync_small(s));
-    if (total > (unsigned long long)INT32_MAX)
-        return cleanup(fail(GPK_ERR_INVALID_OFFSETS, "spatial index directory overflows i32 (%llu entries)", total));
-    int32_t* items = nullptr;
-    IX_HIP(cached_malloc((void**)&items, sizeof(int32_t) * (size_t)(total > 0 ? total : 1)));
-    ix->owned[3] = items;
-    if (n > 0) {
-        IX_LAUNCH("gpk_index_fill", grid_register_kernel<true>, grid_for(n, 256), dim3(256), 0, s, bbox, n, grid, cursor, items);
-        IX_LAUNCH("gpk_index_sort", cell_sort_kernel, grid_for(n_cells, 256), dim3(256), 0, s, cell_off, n_cells, items);
-    }
-    IX_HIP(hipStreamSynchronize(s));  // the workspace may be recycled by the next call on another stream
-    stamp("directory");
-#undef IX_HIP
-#undef IX_TRY
-#undef IX_LAUNCH
-
-    ix->v.bbox = bbox;
-    ix->v.grid = grid;
-    ix->v.cell_off = cell_off;
-    ix->v.items = items;
-    ix->v.gx = gdim;
-    ix->v.gy = gdim;
-    ix->nbytes = (int64_t)(sizeof(double4) * (size_t)n + sizeof(GridParams) + sizeof(int32_t) * (size_t)(n_cells + 1) +
-                           sizeof(int32_t) * (size_t)total);
-    if (parts & GPK_INDEX_PIP) {
-        const int32_t rc = build_pip_index(a, ix, s, (parts & GPK_INDEX_PIP_LIGHT) ? 0 : ((parts & GPK_INDEX_PIP_FULL) ? 2 : 1));  // raster + slabs for polygonal arrays
-        if (rc != GPK_OK) {
-            gpk_index_free(ix);
-            return rc;
-        }
-    }
-    *out = ix;
-    return GPK_OK;
-}
-
 int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index,
                          int32_t predicate, uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs,
                          int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream) {
@@ -2621,15 +1772,8 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right, co
     const bool polypoly_arm = polypoly && (predicate == GPK_PRED_INTERSECTS || (predicate == GPK_PRED_CONTAINS && right->d.type == GPK_GEOM_POLYGON));
     auto lineal = [](int32_t t) { return t == GPK_GEOM_LINESTRING || t == GPK_GEOM_MULTILINESTRING; };
     const bool lineal_point = (left->d.type == GPK_GEOM_POINT && lineal(right->d.type)) || (lineal(left->d.type) && right->d.type == GPK_GEOM_POINT);
-    if (!pip && !polypoly_arm && !lineal_point) {  // `_ => false` (spatial_index.rs:136): an empty join, not an error
-        if (out_counts && left->d.n_geoms > 0) {
-            if (out_space == GPK_MEM_DEVICE)
-                GPK_HIP(hipMemsetAsync(out_counts, 0, sizeof(uint32_t) * (size_t)left->d.n_geoms, s));
-            else
-                memset(out_counts, 0, sizeof(uint32_t) * (size_t)left->d.n_geoms);
-        }
-        return GPK_OK;
-    }
+    if (!pip && !polypoly_arm && !lineal_point)  // `_ => false` (spatial_index.rs:136): an empty join, not an error
+        return zero_counts(out_counts, left->d.n_geoms, out_space, s);
 
     gpk_index* tmp_index = nullptr;
     if (!right_index) {  // built on the fly, like spatial_index.rs:60-71 — only the tables this arm reads
@@ -2664,9 +1808,8 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right, co
                 tmp_index = nullptr;  // (owned by the handle from here on)
             }
         }
-    } else if (right_index->n_geoms != right->d.n_geoms || right_index->n_coords != right->d.n_coords || right_index->n_rings != right->d.n_rings) {
-        // (an index whose slabs name coordinates by index reads THIS array's coordinates: rows alone do not identify the column)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "right_index was built over a different array");
+    } else {
+        GPK_TRY(index_matches(right_index, right));
     }
     auto done = [&](int32_t rc) {
         if (tmp_index) gpk_index_free(tmp_index);
@@ -2675,14 +1818,18 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right, co
 
     const int64_t n = left->d.n_geoms;
     if (n == 0) return done(GPK_OK);
-    if (polypoly)
-        return done(bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s,
-                              predicate == GPK_PRED_CONTAINS ? REFINE_CONTAINS : REFINE_POLYGONAL));
-    if (lineal_point)
-        return done(bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, REFINE_LINEAL_POINT));
+    if (polypoly || lineal_point) {  // the box-candidate join with this arm's refine
+        const double4* lbbox = nullptr;  // (the lineal x point refine reads no boxes: bbox_join computes the candidates' own)
+        if (polypoly) {
+            const int32_t brc = left_boxes(left, s, &lbbox);
+            if (brc != GPK_OK) return done(brc);
+        }
+        BoxRefineCtx cx = box_refine_ctx(left, right, right_index, lbbox);
+        const CandRefine refine = lineal_point ? lineal_point_refine(&cx)
+                                               : (predicate == GPK_PRED_CONTAINS ? polygonal_contains_refine(&cx) : polygonal_intersects_refine(&cx));
+        return done(bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, lbbox, refine));
+    }
     const bool host_out = out_space != GPK_MEM_DEVICE;
-    const bool want_pairs = pair_capacity > 0;
-    const size_t counts_bytes = sizeof(uint32_t) * (size_t)n;
     static thread_local unsigned long long* pinned_total = nullptr;  // device-mapped host word: no D2H copy per call
     if (!pinned_total && hipHostMalloc((void**)&pinned_total, 64, hipHostMallocMapped) != hipSuccess) pinned_total = nullptr;
     uint32_t *counts_dev = nullptr, *pairs_dev = nullptr;
@@ -2698,22 +1845,7 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right, co
     if (e != hipSuccess) return done(fail(GPK_ERR_DEVICE, "spatial_join: %s", hipGetErrorString(e)));
     if (pinned_total) total = *(volatile unsigned long long*)pinned_total;
     if (total == ~0ull) return done(fail(GPK_ERR_DEVICE, "spatial_join: the fused point join gave up waiting for one of its work-groups"));
-    *n_pairs = (int64_t)total;
-    if (host_out) {
-        if (out_counts) {
-            rc = copy_out(out_counts, out_space, counts_dev, counts_bytes, s);
-            if (rc != GPK_OK) return done(rc);
-        }
-        if (want_pairs) {
-            const int64_t w = (int64_t)total < pair_capacity ? (int64_t)total : pair_capacity;
-            rc = copy_out(out_pairs, out_space, pairs_dev, sizeof(uint32_t) * 2 * (size_t)w, s);
-            if (rc != GPK_OK) return done(rc);
-        }
-    }
-    if (want_pairs && (int64_t)total > pair_capacity)
-        return done(fail(GPK_ERR_CAPACITY, "spatial_join: %lld pairs but capacity %lld", (long long)total,
-                         (long long)pair_capacity));
-    return done(GPK_OK);
+    return done(finish_pairs("spatial_join", (int64_t)total, n, out_counts, counts_dev, out_pairs, pairs_dev, pair_capacity, n_pairs, out_space, s));
 }
 
 int32_t gpk_spatial_join_async(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
@@ -2729,8 +1861,7 @@ int32_t gpk_spatial_join_async(const gpk_geoarray* left, const gpk_geoarray* rig
         return fail(GPK_ERR_MISMATCHED_GEOMETRY,
                     "spatial_join_async: only point x polygon/multipolygon is stream-ordered (left type %d x right type %d)",
                     left->d.type, right->d.type);
-    if (right_index->n_geoms != right->d.n_geoms || right_index->n_coords != right->d.n_coords || right_index->n_rings != right->d.n_rings)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "right_index was built over a different array");
+    GPK_TRY(index_matches(right_index, right));
     hipStream_t s = (hipStream_t)stream;
     if (left->d.n_geoms == 0) {
         if (n_pairs_dev) GPK_HIP(hipMemsetAsync(n_pairs_dev, 0, sizeof(int64_t), s));

@@ -1,4 +1,4 @@
-// gpk_lineal.h — Contains<Coord> for Line / LineString / MultiLineString, shared by the join's refine (gpk_join.hip) and
+// gpk_lineal.h — Contains<Coord> for Line / LineString / MultiLineString, shared by the join's refine (gpk_bboxjoin.hip) and
 // the row-wise predicates (gpk_rowwise.hip).
 #pragma once
 

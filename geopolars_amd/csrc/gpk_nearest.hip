@@ -37,6 +37,7 @@
 
 #include "gpk_device.h"
 #include "gpk_distance.h"
+#include "gpk_candjoin.h"
 #include "gpk_index.h"
 #include "gpk_scan.h"
 
@@ -324,12 +325,7 @@ extern "C" int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray
     if (rt != GPK_GEOM_POINT && rt != GPK_GEOM_MULTIPOINT && rt != GPK_GEOM_LINESTRING && rt != GPK_GEOM_MULTILINESTRING && rt != GPK_GEOM_POLYGON &&
         rt != GPK_GEOM_MULTIPOLYGON)
         return fail(GPK_ERR_MISMATCHED_GEOMETRY, "nearest_join: unsupported right geometry type %d", rt);
-    if (right_index) {
-        if (right_index->n_geoms != right->d.n_geoms || right_index->n_coords != right->d.n_coords || right_index->n_rings != right->d.n_rings)
-            return fail(GPK_ERR_INVALID_ARGUMENT, "right_index was built over a different array");
-        if (!right_index->v.grid || !right_index->v.cell_off || !right_index->v.items || !right_index->v.bbox)
-            return fail(GPK_ERR_INVALID_ARGUMENT, "nearest_join: right_index carries no bbox grid");
-    }
+    if (right_index) GPK_TRY(index_matches_with_grid(right_index, right, "nearest_join"));
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = left->d.n_geoms;

@@ -25,6 +25,19 @@ from .geoarrow import DeviceGeoArray
 from .geoseries import GeoSeries, dwithin_distance_arg
 
 
+def _ptr(t):
+    """data_ptr() of an optional torch tensor (None stays None: the ABI's "not asked for")"""
+    return t.data_ptr() if t is not None else None
+
+
+def _index_parts(for_points: bool, full: bool, light: bool) -> int:
+    """the GPK_INDEX_* bits of gpk_index_build_ex"""
+    parts = _abi.INDEX_BBOX_GRID | (_abi.INDEX_PIP if for_points else 0) | (_abi.INDEX_PIP_FULL if for_points and full else 0)
+    if for_points and light and not full:  # an index that serves ONE join (what gpk_spatial_join builds for itself without r_index)
+        parts |= _abi.INDEX_PIP_LIGHT
+    return parts
+
+
 class SpatialIndex:
     """Device-resident bbox grid directory over one series (the R-tree's replacement)."""
 
@@ -33,9 +46,7 @@ class SpatialIndex:
         full=True builds per-entry records for every list cell (GPK_INDEX_PIP_FULL: an index that serves hundreds of joins)."""
         self.series = series
         h = C.c_void_p()
-        parts = _abi.INDEX_BBOX_GRID | (_abi.INDEX_PIP if for_points else 0) | (_abi.INDEX_PIP_FULL if for_points and full else 0)
-        if for_points and light and not full:  # an index that serves ONE join (what gpk_spatial_join builds for itself without r_index)
-            parts |= _abi.INDEX_PIP_LIGHT
+        parts = _index_parts(for_points, full, light)
         _abi.check(_abi.lib().gpk_index_build_ex(series.device().handle, parts, None, stream, C.byref(h)))
         self._h = h
 
@@ -47,10 +58,8 @@ class SpatialIndex:
         self.series = None
         self._dev = dev
         h = C.c_void_p()
-        parts = _abi.INDEX_BBOX_GRID | (_abi.INDEX_PIP if for_points else 0) | (_abi.INDEX_PIP_FULL if for_points and full else 0)
-        if for_points and light and not full:  # an index that serves ONE join (what gpk_spatial_join builds for itself without r_index)
-            parts |= _abi.INDEX_PIP_LIGHT
-        _abi.check(_abi.lib().gpk_index_build_ex(dev.handle, parts, bboxes.data_ptr() if bboxes is not None else None, stream, C.byref(h)))
+        parts = _index_parts(for_points, full, light)
+        _abi.check(_abi.lib().gpk_index_build_ex(dev.handle, parts, _ptr(bboxes), stream, C.byref(h)))
         self._h = h
         return self
 
@@ -125,6 +134,24 @@ class SpatialJoinArgs:
     r_geom_type: int = -1
 
 
+def _pairs_with_retry(n: int, call, want_dist: bool = False):
+    """The host-buffer joins' sizing loop: one call in the common case; the ABI reports the exact total when the capacity is too small.
+    call(pairs_ptr, dist_ptr or None, capacity, byref(n_pairs)) makes the C call and returns its code.  Returns the pairs and — when
+    asked for — their distances, cut to the total."""
+    n_pairs = C.c_int64(0)
+    capacity = max(1024, 4 * n)
+    while True:
+        pairs = np.empty((capacity, 2), dtype=np.uint32)
+        dist = np.empty(capacity, dtype=np.float64) if want_dist else None
+        rc = call(pairs.ctypes.data, dist.ctypes.data if want_dist else None, capacity, C.byref(n_pairs))
+        if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
+            capacity = int(n_pairs.value)
+            continue
+        _abi.check(rc)
+        h = int(n_pairs.value)
+        return pairs[:h].copy(), (dist[:h].copy() if want_dist else None)
+
+
 def join_pairs(
     left: GeoSeries,
     right: GeoSeries,
@@ -137,41 +164,20 @@ def join_pairs(
     lib = _abi.lib()
     n = len(left)
     counts = np.empty(n, dtype=np.uint32)
-    n_pairs = C.c_int64(0)
     rh = r_index.handle if r_index is not None else None
     pred = PREDICATES[predicate]
-    capacity = max(1024, 4 * n)  # one call in the common case; the ABI reports the exact total when this is too small
-    while True:
-        pairs = np.empty((capacity, 2), dtype=np.uint32)
-        rc = lib.gpk_spatial_join(
-            left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs.ctypes.data, capacity, C.byref(n_pairs), MEM_HOST, None
-        )
-        if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
-            capacity = int(n_pairs.value)
-            continue
-        _abi.check(rc)
-        return pairs[: int(n_pairs.value)].copy(), counts
+    call = lambda pairs_ptr, _dist, capacity, n_pairs: lib.gpk_spatial_join(  # noqa: E731
+        left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs_ptr, capacity, n_pairs, MEM_HOST, None)
+    return _pairs_with_retry(n, call)[0], counts
 
 
 def join_pairs_device(left: DeviceGeoArray, right: DeviceGeoArray, r_index: SpatialIndex, predicate: str, out_counts, out_pairs, left_row_base: int = 0, stream: int = 0) -> int:
     """Device-buffer variant (bench / multi-GPU path): out_counts (n,) uint32-as-int32 and out_pairs
     (cap, 2) torch CUDA tensors are filled in place on `stream`; returns the number of pairs."""
     n_pairs = C.c_int64(0)
-    _abi.check(
-        _abi.lib().gpk_spatial_join(
-            left.handle,
-            right.handle,
-            r_index.handle if r_index is not None else None,
-            PREDICATES[predicate],
-            left_row_base,
-            out_counts.data_ptr() if out_counts is not None else None,
-            out_pairs.data_ptr() if out_pairs is not None else None,
-            out_pairs.shape[0] if out_pairs is not None else 0,
-            C.byref(n_pairs),
-            MEM_DEVICE,
-            stream,
-        )
-    )
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_spatial_join(
+        left.handle, right.handle, rh, PREDICATES[predicate], left_row_base, _ptr(out_counts), _ptr(out_pairs), cap, C.byref(n_pairs), MEM_DEVICE, stream))
     return int(n_pairs.value)
 
 
@@ -179,20 +185,9 @@ def join_pairs_enqueue(left: DeviceGeoArray, right: DeviceGeoArray, r_index: Spa
     """Stream-ordered variant of join_pairs_device (gpk_spatial_join_async): the join is enqueued on `stream` and
     this returns without waiting.  n_pairs_out: a 1-element int64 CUDA tensor that receives the total (read it
     after synchronising; pairs beyond out_pairs' capacity are dropped)."""
-    _abi.check(
-        _abi.lib().gpk_spatial_join_async(
-            left.handle,
-            right.handle,
-            r_index.handle,
-            PREDICATES[predicate],
-            left_row_base,
-            out_counts.data_ptr() if out_counts is not None else None,
-            out_pairs.data_ptr() if out_pairs is not None else None,
-            out_pairs.shape[0] if out_pairs is not None else 0,
-            n_pairs_out.data_ptr() if n_pairs_out is not None else None,
-            stream,
-        )
-    )
+    cap = out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_spatial_join_async(
+        left.handle, right.handle, r_index.handle, PREDICATES[predicate], left_row_base, _ptr(out_counts), _ptr(out_pairs), cap, _ptr(n_pairs_out), stream))
 
 
 JOIN_TYPES = {"inner": 0, "left": 1}  # GPK_JOIN_*
@@ -290,14 +285,33 @@ def _as_wkb(column, geo: GeoSeries):
     return geo.device().to_arrow("wkb")  # (gpk_geoarray_to_arrow: the library's buffers, validity included, released by pyarrow)
 
 
+def _assemble(lhs, rhs, lgeo: GeoSeries, rgeo: GeoSeries, li: np.ndarray, ri: np.ndarray, l_suffix, r_suffix, distance_col=None, dist=None):
+    """The joined table of spatial_index.rs:165-199 from the i64 row indices: suffixed left columns, suffixed right columns, then —
+    for the distance joins — `distance_col` with each pair's distance (null for an unmatched left row)."""
+    import pyarrow as pa
+
+    cols, names = [], []
+    for table, geo, idx, suffix in ((lhs, lgeo, li, l_suffix), (rhs, rgeo, ri, r_suffix)):
+        for name in table.column_names:
+            cols.append(take_column(_as_wkb(table.column(name), geo) if name == "geometry" else table.column(name), idx))
+            names.append(name + (suffix or ""))
+    if distance_col is not None:
+        # join_indices keeps the pairs' order and puts an unmatched left row (r = -1) where its pairs would be: pair k of the sorted
+        # output is joined row k among the rows with r >= 0
+        matched = ri >= 0
+        d = np.zeros(len(ri), dtype=np.float64)
+        d[matched] = dist
+        cols.append(pa.array(d, type=pa.float64(), mask=~matched))
+        names.append(distance_col)
+    return pa.table(cols, names=names)
+
+
 def spatial_join(lhs, rhs, options: Optional[SpatialJoinArgs] = None):
     """spatial_join(lhs, rhs, SpatialJoinArgs) over pyarrow Tables with a `geometry` column (spatial_index.rs:44-45) — WKB binary as the
     reference holds it, or a native GeoArrow nesting.  Returns a pyarrow Table shaped like the reference's result: suffixed left columns,
     then suffixed right columns (spatial_index.rs:165-199).  The geometry columns cross into the library the way every Series crosses
     the reference's FFI — as Arrow C Data Interface structs (py-geopolars/src/ffi.rs:12-32; gpk_geoarray_from_arrow): WKB is decoded
     on the GPU, nothing is rewritten on the host."""
-    import pyarrow as pa
-
     options = options or SpatialJoinArgs()
     if options.join_type not in ("inner", "left"):
         # spatial_index.rs:200-202 rejects every other JoinType
@@ -307,14 +321,7 @@ def spatial_join(lhs, rhs, options: Optional[SpatialJoinArgs] = None):
     r_index = options.r_index or SpatialIndex(rgeo)
     pairs, counts = join_pairs(lgeo, rgeo, options.predicate, r_index)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    cols, names = [], []
-    for name in lhs.column_names:
-        cols.append(take_column(_as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
-        names.append(name + (options.l_suffix or ""))
-    for name in rhs.column_names:
-        cols.append(take_column(_as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
-        names.append(name + (options.r_suffix or ""))
-    return pa.table(cols, names=names)
+    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
 
 
 # ---- nearest-neighbour join (gpk_nearest_join) ----------------------------------------------------------------------------------
@@ -366,22 +373,11 @@ def nearest_pairs(
     lib = _abi.lib()
     n = len(left)
     counts = np.empty(n, dtype=np.uint32)
-    n_pairs = C.c_int64(0)
     rh = r_index.handle if r_index is not None else None
-    capacity = max(1024, 4 * n)
-    while True:
-        pairs = np.empty((capacity, 2), dtype=np.uint32)
-        dist = np.empty(capacity, dtype=np.float64)
-        rc = lib.gpk_nearest_join(
-            left.device().handle, right.device().handle, rh, md, left_row_base, counts.ctypes.data, pairs.ctypes.data, dist.ctypes.data, capacity,
-            C.byref(n_pairs), MEM_HOST, None
-        )
-        if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
-            capacity = int(n_pairs.value)
-            continue
-        _abi.check(rc)
-        h = int(n_pairs.value)
-        return pairs[:h].copy(), counts, dist[:h].copy()
+    call = lambda pairs_ptr, dist_ptr, capacity, n_pairs: lib.gpk_nearest_join(  # noqa: E731
+        left.device().handle, right.device().handle, rh, md, left_row_base, counts.ctypes.data, pairs_ptr, dist_ptr, capacity, n_pairs, MEM_HOST, None)
+    pairs, dist = _pairs_with_retry(n, call, want_dist=True)
+    return pairs, counts, dist
 
 
 def nearest_pairs_device(
@@ -401,22 +397,9 @@ def nearest_pairs_device(
     if left.geom_type != _abi.GEOM_POINT:
         raise _abi.MismatchedGeometry(_abi.GPK_ERR_MISMATCHED_GEOMETRY, f"nearest join: the left side must be POINT (found type {left.geom_type})")
     n_pairs = C.c_int64(0)
-    _abi.check(
-        _abi.lib().gpk_nearest_join(
-            left.handle,
-            right.handle,
-            r_index.handle if r_index is not None else None,
-            md,
-            left_row_base,
-            out_counts.data_ptr() if out_counts is not None else None,
-            out_pairs.data_ptr() if out_pairs is not None else None,
-            out_dist.data_ptr() if out_dist is not None else None,
-            out_pairs.shape[0] if out_pairs is not None else 0,
-            C.byref(n_pairs),
-            MEM_DEVICE,
-            stream,
-        )
-    )
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_nearest_join(
+        left.handle, right.handle, rh, md, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_dist), cap, C.byref(n_pairs), MEM_DEVICE, stream))
     return int(n_pairs.value)
 
 
@@ -424,8 +407,6 @@ def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = N
     """GeoPandas' sjoin_nearest over pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes them): every
     left point with every right geometry at its smallest distance (ties all kept), shaped like spatial_join's result — suffixed left
     columns, suffixed right columns, then `distance_col` when asked for.  The left geometry column must hold points."""
-    import pyarrow as pa
-
     options = options or SpatialJoinNearestArgs()
     if options.join_type not in ("inner", "left"):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"nearest join: join_type must be 'inner' or 'left', got {options.join_type!r}")
@@ -435,22 +416,7 @@ def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = N
     rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
     pairs, counts, dist = nearest_pairs(lgeo, rgeo, options.r_index, md)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    cols, names = [], []
-    for name in lhs.column_names:
-        cols.append(take_column(_as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
-        names.append(name + (options.l_suffix or ""))
-    for name in rhs.column_names:
-        cols.append(take_column(_as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
-        names.append(name + (options.r_suffix or ""))
-    if options.distance_col is not None:
-        # join_indices keeps the pairs' order and puts an unmatched left row (r = -1) where its pairs would be: pair k of the sorted
-        # output is joined row k among the rows with r >= 0
-        matched = ri >= 0
-        d = np.zeros(len(ri), dtype=np.float64)
-        d[matched] = dist
-        cols.append(pa.array(d, type=pa.float64(), mask=~matched))
-        names.append(options.distance_col)
-    return pa.table(cols, names=names)
+    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
 
 
 # ---- within-distance join (gpk_dwithin_join) ------------------------------------------------------------------------------------
@@ -484,22 +450,11 @@ def dwithin_pairs(
     lib = _abi.lib()
     n = len(left)
     counts = np.zeros(n, dtype=np.uint32)
-    n_pairs = C.c_int64(0)
     rh = r_index.handle if r_index is not None else None
-    capacity = max(1024, 4 * n)
-    while True:
-        pairs = np.empty((capacity, 2), dtype=np.uint32)
-        dist = np.empty(capacity, dtype=np.float64)
-        rc = lib.gpk_dwithin_join(
-            left.device().handle, right.device().handle, rh, d, left_row_base, counts.ctypes.data, pairs.ctypes.data, dist.ctypes.data, capacity,
-            C.byref(n_pairs), MEM_HOST, None
-        )
-        if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
-            capacity = int(n_pairs.value)
-            continue
-        _abi.check(rc)
-        h = int(n_pairs.value)
-        return pairs[:h].copy(), counts, dist[:h].copy()
+    call = lambda pairs_ptr, dist_ptr, capacity, n_pairs: lib.gpk_dwithin_join(  # noqa: E731
+        left.device().handle, right.device().handle, rh, d, left_row_base, counts.ctypes.data, pairs_ptr, dist_ptr, capacity, n_pairs, MEM_HOST, None)
+    pairs, dist = _pairs_with_retry(n, call, want_dist=True)
+    return pairs, counts, dist
 
 
 def dwithin_pairs_device(
@@ -517,22 +472,9 @@ def dwithin_pairs_device(
     may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
     d = dwithin_distance_arg(distance)
     n_pairs = C.c_int64(0)
-    _abi.check(
-        _abi.lib().gpk_dwithin_join(
-            left.handle,
-            right.handle,
-            r_index.handle if r_index is not None else None,
-            d,
-            left_row_base,
-            out_counts.data_ptr() if out_counts is not None else None,
-            out_pairs.data_ptr() if out_pairs is not None else None,
-            out_dist.data_ptr() if out_dist is not None else None,
-            out_pairs.shape[0] if out_pairs is not None else 0,
-            C.byref(n_pairs),
-            MEM_DEVICE,
-            stream,
-        )
-    )
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_dwithin_join(
+        left.handle, right.handle, rh, d, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_dist), cap, C.byref(n_pairs), MEM_DEVICE, stream))
     return int(n_pairs.value)
 
 
@@ -540,8 +482,6 @@ def spatial_join_dwithin(lhs, rhs, options: Optional[SpatialJoinDWithinArgs] = N
     """GeoPandas' sjoin(predicate="dwithin", distance=d) over pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as
     spatial_join takes them): every left row with every right row within `options.distance` of it, shaped like spatial_join's result —
     suffixed left columns, suffixed right columns, then `distance_col` when asked for.  Any two geometry families."""
-    import pyarrow as pa
-
     options = options or SpatialJoinDWithinArgs()
     if options.join_type not in ("inner", "left"):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"dwithin join: join_type must be 'inner' or 'left', got {options.join_type!r}")
@@ -550,17 +490,4 @@ def spatial_join_dwithin(lhs, rhs, options: Optional[SpatialJoinDWithinArgs] = N
     rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
     pairs, counts, dist = dwithin_pairs(lgeo, rgeo, d, options.r_index)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    cols, names = [], []
-    for name in lhs.column_names:
-        cols.append(take_column(_as_wkb(lhs.column(name), lgeo) if name == "geometry" else lhs.column(name), li))
-        names.append(name + (options.l_suffix or ""))
-    for name in rhs.column_names:
-        cols.append(take_column(_as_wkb(rhs.column(name), rgeo) if name == "geometry" else rhs.column(name), ri))
-        names.append(name + (options.r_suffix or ""))
-    if options.distance_col is not None:
-        matched = ri >= 0  # (pair k of the sorted output is joined row k among the rows with r >= 0: see spatial_join_nearest)
-        dd = np.zeros(len(ri), dtype=np.float64)
-        dd[matched] = dist
-        cols.append(pa.array(dd, type=pa.float64(), mask=~matched))
-        names.append(options.distance_col)
-    return pa.table(cols, names=names)
+    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)

@@ -286,8 +286,8 @@ def contains(pa, pb) -> bool:
 PP_SMALL = 66  # gpk_polypoly.h: single-ring POLYGON pairs of 1 .. PP_SMALL coordinates take polygon_pair_small
 PP_LIST = 32  # gpk_polypoly.h: in-window segment list of the general routine
 JOIN_GS = 16  # lanes per candidate pair of the refine
-CAND_STAGE = 16  # gpk_join.hip: rows of at most this many candidates keep a staged slice
-CAND_INLINE_SORT = 48  # gpk_join.hip: beyond it the join takes bbox_cand_kernel<true> and the segmented sort
+CAND_STAGE = 16  # gpk_bboxjoin.hip: rows of at most this many candidates keep a staged slice
+CAND_INLINE_SORT = 48  # gpk_bboxjoin.hip: beyond it the join takes bbox_cand_kernel<true> and the segmented sort
 
 
 def pick_group_rows(n_coords: int, n_geoms: int) -> int:
