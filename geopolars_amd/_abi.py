@@ -173,6 +173,9 @@ _PROTOS = {
         [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
     "gpk_dwithin_rowwise": (C.c_int32, [_VP, _VP, _VP, C.c_double, _VP, C.c_int32, _VP]),
+    "gpk_closest_point_rowwise": (C.c_int32, [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_line_locate_point": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP]),
+    "gpk_line_interpolate_point": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int32, _VP]),
     "gpk_wkb_encode": (C.c_int32, [_VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "gpk_geoarray_to_wkb": (C.c_int32, [_VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP]),
     "gpk_join_indices": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int64, C.c_uint32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP]),

@@ -35,6 +35,7 @@ SOURCES = [
     "gpk_pairdist.hip",
     "gpk_nearest.hip",
     "gpk_dwithin.hip",
+    "gpk_linref.hip",
     "gpk_hull.hip",
     "gpk_wkb.cpp",
     "gpk_arrow.cpp",

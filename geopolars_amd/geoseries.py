@@ -342,6 +342,114 @@ class GeoSeries:
         )
         return out.astype(bool)
 
+    # ---- linear referencing (gpk_linref.hip) -----------------------------------------------------
+    def _family(self) -> int:
+        return self._dev.geom_type if self._array is None else self._array.geom_type
+
+    def closest_point(self, other: "GeoSeries", other_rows=None, return_segment: bool = False):
+        """geo's ClosestPoint / shapely's nearest_points: for every point of `self` (a POINT column) the nearest point of
+        other[other_rows[i]] (any family), as a POINT series; null where there is none (a null or empty row, a NaN point).  A point
+        inside or on a polygon is its own closest point.  With `return_segment` also the int32 index, in `other`'s coordinate
+        buffer, of the start of the segment the point lies on (the lowest one among ties; -1: none, or inside a polygon)."""
+        rows = linref_args("closest_point", self, other, other_rows)
+        n = len(self)
+        xy = np.empty((n, 2), dtype=np.float64)
+        seg = np.empty(n, dtype=np.int32) if return_segment else None
+        if n:
+            _abi.check(
+                _abi.lib().gpk_closest_point_rowwise(
+                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, xy.ctypes.data,
+                    seg.ctypes.data if return_segment else None, MEM_HOST, None,
+                )
+            )
+        ok =~np.isnan(xy[:, 0])
+        out = GeoSeries(GeoArrowArray.from_points(xy, validity=None if ok.all() else np.packbits(ok, bitorder="little")))
+        return (out, seg) if return_segment else out
+
+    def shortest_line(self, other: "GeoSeries", other_rows=None) -> "GeoSeries":
+        """shapely's shortest_line: the two-coordinate LINESTRING [p, closest_point(p)] per row (assembled on the host from
+        closest_point); null where there is no closest point."""
+        q = self.closest_point(other, other_rows)
+        n = len(self)
+        xy = np.empty((2 * n, 2), dtype=np.float64)
+        xy[0::2] = self.array.xy
+        xy[1::2] = q.array.xy
+        return GeoSeries(GeoArrowArray(GEOM_LINESTRING, xy, geom_offsets=np.arange(0, 2 * n + 1, 2, dtype=np.int32), validity=q.array.validity, n_geoms=n))
+
+    def project(self, other: "GeoSeries", normalized: bool = False, rows=None) -> np.ndarray:
+        """GeoPandas' GeoSeries.project / geo's LineLocatePoint: `self` is a LINESTRING or MULTILINESTRING column, `other` a POINT
+        column; one result per point: the distance along self[rows[i]] (default: self[i]) of its point nearest to other[i], as a
+        fraction of the line's length with `normalized`.  A MULTILINESTRING's members are measured one after the other.  NaN for
+        null and empty rows and NaN points."""
+        r = linref_args("project", other, self, rows, lineal_only=True)
+        out = np.empty(len(other), dtype=np.float64)
+        if len(out):
+            _abi.check(
+                _abi.lib().gpk_line_locate_point(
+                    other.device().handle, self.device().handle, None if r is None else r.ctypes.data, int(bool(normalized)), out.ctypes.data, MEM_HOST, None
+                )
+            )
+        return out
+
+    def interpolate(self, distance, normalized: bool = False) -> "GeoSeries":
+        """GeoPandas' GeoSeries.interpolate / geo's LineInterpolatePoint: the point at `distance` (a number, or one per row) along each
+        LINESTRING or MULTILINESTRING; a negative distance is taken from the end, one beyond either end gives that end; with
+        `normalized` a fraction of the line's length.  Null for null and empty rows and NaN distances."""
+        d = interpolate_distance_arg(self, distance)
+        n = len(self)
+        xy = np.empty((n, 2), dtype=np.float64)
+        valid = np.ones(n, dtype=np.uint8)
+        if n:
+            _abi.check(
+                _abi.lib().gpk_line_interpolate_point(
+                    self.device().handle, d.ctypes.data, len(d), int(bool(normalized)), xy.ctypes.data, valid.ctypes.data, MEM_HOST, None
+                )
+            )
+        ok = valid.astype(bool)
+        return GeoSeries(GeoArrowArray.from_points(xy, validity=None if ok.all() else np.packbits(ok, bitorder="little")))
+
+
+def _mismatch(msg: str) -> "_abi.MismatchedGeometry":
+    return _abi.MismatchedGeometry(_abi.GPK_ERR_MISMATCHED_GEOMETRY, msg)
+
+
+def linref_args(op: str, points: GeoSeries, other: GeoSeries, rows, lineal_only: bool = False) -> Optional[np.ndarray]:
+    """the checks of closest_point / project, before any device call: `points` is a POINT column, `other` lineal where the operator
+    needs it, the row map (as uint32, or None) pairs every point with a row; refusals as the C ABI would make them"""
+    if points._family() != GEOM_POINT:
+        raise _mismatch(f"{op}: the point side must be POINT (found {_abi_name(points._family())})")
+    if lineal_only and other._family() not in (GEOM_LINESTRING, GEOM_MULTILINESTRING):
+        raise _mismatch(f"{op}: expected LineString or MultiLineString (found {_abi_name(other._family())})")
+    if rows is None:
+        if len(points) != len(other):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(points)} vs {len(other)})")
+        return None
+    try:
+        r = np.ascontiguousarray(rows, dtype=np.uint32)
+    except (TypeError, ValueError, OverflowError):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+    if r.ndim != 1 or len(r) != len(points):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(points)} points")
+    return r
+
+
+def interpolate_distance_arg(lines: GeoSeries, distance) -> np.ndarray:
+    """the `distance` of interpolate as a float64 array of 1 value (a scalar: it stays one value) or len(lines) values; a wrong
+    family, length or anything not convertible to float is refused here, before any device call"""
+    if lines._family() not in (GEOM_LINESTRING, GEOM_MULTILINESTRING):
+        raise _mismatch(f"interpolate: expected LineString or MultiLineString (found {_abi_name(lines._family())})")
+    try:
+        if distance is None:
+            raise TypeError("None")
+        d = np.asarray(distance, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"interpolate: distance must be a number or an array of numbers, got {distance!r}") from None
+    if d.ndim == 0:
+        return d.reshape(1)
+    if d.ndim != 1 or len(d) != len(lines):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"interpolate: {d.size} distances for {len(lines)} rows (a scalar or one per row)")
+    return np.ascontiguousarray(d)
+
 
 def dwithin_distance_arg(distance) -> float:
     """the `distance` of a dwithin call as a float; anything but a finite number >= 0 is refused here, before any device call"""

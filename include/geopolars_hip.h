@@ -498,6 +498,44 @@ int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray* right, co
 int32_t gpk_dwithin_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double distance, uint8_t* out,
                             int32_t out_space, void* stream);
 
+/* ---- linear referencing (gpk_linref.hip) ------------------------------------------------------------------------------------
+ * Where on a geometry the nearest point lies, how far along a line it is, and the point at a measure along a line (geo 0.27
+ * ClosestPoint / LineLocatePoint / LineInterpolatePoint; shapely / GeoPandas nearest_points, shortest_line, project, interpolate).
+ * Shape rules of all three: the POINT column is the first argument; `b_rows` / `line_rows` (same space as the outputs) as in
+ * gpk_distance_rowwise — NULL = identity (the row counts must then match), an entry >= n_geoms behaves like a null row; any other
+ * geometry family than the ones named gives GPK_ERR_MISMATCHED_GEOMETRY, a wrong count GPK_ERR_INVALID_ARGUMENT, both before any
+ * device work.  Outputs are stream-ordered (host outputs: the call waits for them).  Magnitude range: as gpk_distance_rowwise.
+ *
+ * Closest point: q[i] = the point of B = b[b_rows[i]] nearest to p = a[i]; a POINT, b any of the six families.
+ *   - B polygonal and p inside or on its boundary (the exact position test of `distance`, holes excluded): q = p bit for bit, seg = -1;
+ *   - otherwise the candidates are every segment of every coordinate sequence of B (all rings of all parts, all member linestrings;
+ *     a MULTIPOINT member, a POINT and a one-coordinate sequence are degenerate segments), compared as gpk_distance_rowwise compares
+ *     them (squared distances as fractions).  Ties: the winner is the minimising segment with the LOWEST start index in b's
+ *     coordinate buffer, whatever the lane-group size; out_seg[i] (may be NULL) is that coordinate index;
+ *   - with s, e the winner's ends, dot = (p - s).(e - s), d2 = |e - s|^2: q = s when dot <= 0 or d2 == 0, q = e when dot >= d2 (both
+ *     bit for bit), else s + (dot / d2)(e - s): each component within 2^-48 max(|p|, |s|, |e|) (largest coordinate magnitudes) of the
+ *     exact nearest point of that segment;
+ *   - a null or empty row on either side or a NaN point: q = (NaN, NaN), seg = -1.  out_xy[2 n] interleaved, n = n_geoms(a). */
+int32_t gpk_closest_point_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double* out_xy, int32_t* out_seg,
+                                  int32_t out_space, void* stream);
+/* Locate (project): out[i] = the measure along lines[line_rows[i]] of its point nearest to pts[i]; pts POINT, lines LINESTRING |
+ * MULTILINESTRING.  The winning segment is the closest-point winner (same scan, same tie rule); the measure is the summed length of
+ * every segment before it in storage order plus the length from its start to q.  MULTILINESTRING: members are measured consecutively
+ * in storage order (GEOS LengthIndexedLine), empty members are skipped, the gap between two members has no length.  normalized != 0
+ * divides by the total length (a line without length: 0.0).  Null or empty rows and NaN points give NaN.  Within 1e-9 x the line's
+ * length of the exact measure of the winning segment's nearest point.  out[n_geoms(pts)]. */
+int32_t gpk_line_locate_point(const gpk_geoarray* pts, const gpk_geoarray* lines, const uint32_t* line_rows, int32_t normalized, double* out,
+                              int32_t out_space, void* stream);
+/* Interpolate: the point at measure distances[i] along lines[i] (LINESTRING | MULTILINESTRING, measured as by locate).  `distances`
+ * lives in out_space; n_distances is 1 (one value for every row: it is not expanded to n values) or n_geoms(lines).  With L the
+ * line's length: a normalized distance is multiplied by L first, d < 0 is measured from the end (d += L), the result is clamped to
+ * [0, L].  The point lies on the first segment in storage order whose cumulative end measure is >= d; a measure that lands exactly on
+ * a vertex returns that vertex bit for bit (at a member boundary: the end of the earlier member); L == 0 gives the first coordinate.
+ * A NaN distance and a null or empty line give (NaN, NaN) and out_valid 0.  Within 1e-9 L of the exact point, per component.
+ * out_xy[2 n] interleaved, out_valid[n] bytes 0/1 (may be NULL). */
+int32_t gpk_line_interpolate_point(const gpk_geoarray* lines, const double* distances, int64_t n_distances, int32_t normalized,
+                                   double* out_xy, uint8_t* out_valid, int32_t out_space, void* stream);
+
 /*
  * Stream-ordered form of gpk_spatial_join for callers that keep everything in HBM (the idiom a pipeline of
  * kernels on one HIP stream wants; the reference's call is synchronous, spatial_index.rs:44-58): the join is
