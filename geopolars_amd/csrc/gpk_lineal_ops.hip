@@ -160,7 +160,9 @@ __global__ __launch_bounds__(256) void rdp_kernel(const double2* __restrict__ xy
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         int len = n, top = 0;  // simplified_len; stack depth (identical on every lane of the group)
         int ri = 0, rj = n - 1;
-        bool have = n >= 3 && eps > 0.0;  // fewer than three points, or a non-positive epsilon: unchanged (geo's rdp wrapper)
+        // fewer than three points, or epsilon <= 0: unchanged (geo's rdp wrapper tests `epsilon <= 0`, so a NaN epsilon goes on and,
+        // as no distance is `> NaN`, culls down to min_pts)
+        bool have = n >= 3 && !(eps <= 0.0);
         while (have) {
             if (rj - ri >= 2) {
                 const double2 a = v[ri], b = v[rj];

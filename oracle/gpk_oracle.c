@@ -1901,7 +1901,8 @@ int32_t gpko_simplify(const gpk_geoarrow_desc* a, double eps, double* out_xy, in
         uint8_t* keep = (uint8_t*)malloc((size_t)(n > 0 ? n : 1));
         memset(keep, 1, (size_t)(n > 0 ? n : 1));
         int64_t len = n;
-        if (n >= 3 && eps > 0.0) o_rdp(xy, 0, n - 1, eps, min_pts, &len, keep);
+        if (n >= 3 && !(eps <= 0.0)) /* upstream's wrapper returns early on `epsilon <= 0`: a NaN epsilon goes on (and culls) */
+            o_rdp(xy, 0, n - 1, eps, min_pts, &len, keep);
         for (int64_t k = 0; k < n; ++k)
             if (keep[k]) {
                 out_xy[2 * w] = xy[2 * k];

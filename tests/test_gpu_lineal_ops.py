@@ -129,3 +129,99 @@ def test_simplify_long_ring_and_degenerate_sequences(gpk, oracle):
     assert got.geom_offsets.tolist() == [0, 2, 3, 3, 7, 9]
     pts = GeoSeries(synth.uniform_points(5))
     assert np.array_equal(pts.simplify(1.0).array.xy, pts.array.xy)
+
+
+# ---- haversine and Vincenty: both kernel widths, the guards, NaN, a high-precision reference ------------------------------------
+
+
+def _close(got, exp):
+    """the 1e-9 relative tolerance of the parity tests, NaN-aware: the NaN masks must be equal"""
+    nan = np.isnan(exp)
+    return np.array_equal(np.isnan(got), nan) and bool(np.all(np.abs(got[~nan] - exp[~nan]) <= 1e-9 * np.abs(exp[~nan])))
+
+
+def _lonlat_seq(rng, n):
+    start = np.array([rng.uniform(-170, 170), rng.uniform(-80, 80)])
+    xy = start + np.cumsum(rng.normal(0, 0.05, (n, 2)), axis=0)
+    xy[:, 1] = np.clip(xy[:, 1], -89.0, 89.0)
+    return xy.tolist()
+
+
+@pytest.mark.parametrize("G", [4, 16])
+@pytest.mark.parametrize("method", ["haversine", "vincenty"])
+def test_geodesic_length_in_both_widths(gpk, oracle, method, G):
+    from tests import geodesic_ref as Gd
+    from tests import simplify_ref as R
+
+    rng = np.random.default_rng(60 + G)
+    lengths = [0, 1, 2, G, G + 1, 3 * G + 1] * 6 + [5, 9, 2 * G, 0]
+    antipodes = [(0.0, 0.0), (180.0, 0.0)]
+    for kind in (_abi.GEOM_LINESTRING, _abi.GEOM_MULTILINESTRING, _abi.GEOM_POLYGON):
+        ring = kind == _abi.GEOM_POLYGON
+        seqs = []
+        for n in lengths:
+            s = _lonlat_seq(rng, n)
+            seqs.append(s + s[:1] if ring and n > 2 else s)
+        seqs[3] = seqs[3][:2] + antipodes + seqs[3][2:]  # Vincenty fails on this segment: the NaN reaches the row total
+        if G == 16:
+            seqs += [_lonlat_seq(rng, 150) for _ in range(12)]
+        a = R.as_column(kind, seqs, null_every=6)
+        n_seq = len(R.inner_offsets(a)) - 1
+        assert Gd.geodesic_group_size(a.n_coords, n_seq) == G
+        got, exp = GeoSeries(a).geodesic_length(method), oracle.geodesic_length(a, method)
+        assert _close(got, exp), (kind, method, G)
+        valid = a.is_valid()
+        assert np.all(np.isnan(got[~valid])) and np.isnan(got[valid]).sum() == (1 if method == "vincenty" else 0)
+        assert np.any(got[valid] == 0.0) and np.nanmax(got) > 1e4  # empty rows measure 0
+
+
+def test_vincenty_guards_and_failure_to_converge(gpk, oracle):
+    from tests import geodesic_ref as Gd
+
+    def run(rows):
+        a = GeoArrowArray.from_linestrings(rows)
+        return GeoSeries(a).geodesic_length("vincenty"), oracle.geodesic_length(a, "vincenty")
+
+    got, exp = run([
+        [(0.0, 0.0), (180.0, 0.0)],  # exact antipodes on the equator: upstream's FailedToConverge
+        [(10.0, 20.0), (11.0, 21.0), (0.0, 0.0), (180.0, 0.0), (12.0, 22.0)],  # ... inside a longer line: the total is NaN
+        [(10.0, 20.0), (10.0, 20.0), (10.0, 20.0)],  # coincident vertices: 0
+        [(10.0, 20.0), (10.0, 20.0), (11.0, 21.0), (11.0, 21.0), (12.0, 20.0)],  # repeated vertices contribute 0, not NaN
+        [(0.0, 0.0), (1.0, 0.0), (90.0, 0.0), (170.0, 0.0)],  # along the equator: cos^2 alpha == 0
+        [(-30.0, 0.0), (150.0, 0.0)],  # half the equator, sigma = pi exactly? (the oracle says what upstream gives)
+        [(25.0, -80.0), (25.0, 0.0), (25.0, 89.0)],  # a meridian
+        [(25.0, 10.0), (25.0, 90.0), (-100.0, 45.0)],  # through the north pole
+        [(0.0, -90.0), (77.0, -90.0), (13.0, -20.0)],  # two names of the south pole, then away from it
+        [(0.0, 90.0), (0.0, -90.0)],  # pole to pole
+    ])
+    assert _close(got, exp)
+    assert np.isnan(got[0]) and np.isnan(got[1]) and got[2] == 0.0 and got[3] > 0.0 
+    # (on the equator the formula reduces to a * L; the iteration stops at |d lambda| <= 1e-12 rad, about 6e-6 m a segment)
+    assert abs(got[4] - 6378137.0 * np.radians(170.0)) < 1e-4
+    rng = np.random.default_rng(61)
+    m = 2000
+    l1, p1 = rng.uniform(-180, 180, m), rng.uniform(-89, 89, m)
+    for q in ((l1, np.zeros(m), l1 + rng.uniform(-170, 170, m), np.zeros(m)), (l1, p1, l1, rng.uniform(-90, 90, m)),
+              (l1, p1, rng.uniform(-180, 180, m), np.full(m, 90.0)), (l1, np.full(m, -90.0), rng.uniform(-180, 180, m), p1)):
+        a = _pairs_as_lines(*q)
+        assert _close(GeoSeries(a).geodesic_length("vincenty"), oracle.geodesic_length(a, "vincenty"))
+    # nearly antipodal pairs, only those far from the 100-iteration limit on the CPU (1533 of the 1600 drawn are kept, 688 of them
+    # fail to converge): an ulp of the GPU's sin / atan2 cannot flip these
+    l1, p1, l2, p2, is_nan, drawn = Gd.nearly_antipodal_pairs()
+    assert len(l1) >= 1400 and 500 <= is_nan.sum() <= len(l1) - 500
+    a = _pairs_as_lines(l1, p1, l2, p2)
+    got, exp = GeoSeries(a).geodesic_length("vincenty"), oracle.geodesic_length(a, "vincenty")
+    assert np.array_equal(np.isnan(exp), is_nan) and _close(got, exp)
+
+
+def test_haversine_against_a_high_precision_evaluation(gpk):
+    """the kernel against the great-circle distance at 50 digits; per regime it may be off by 4 times what the oracle's f64
+    evaluation of the same formula is off by on these pairs (tests/geodesic_ref.py HAVERSINE_ERR_M, measured on the CPU)"""
+    pytest.importorskip("mpmath")
+    from tests import geodesic_ref as Gd
+
+    for regime, q in Gd.haversine_pairs().items():
+        got = GeoSeries(_pairs_as_lines(*q)).geodesic_length("haversine")
+        err = Gd.haversine_errors_m(got, Gd.haversine_mp(*q))
+        print(f"haversine {regime}: largest error {err.max():.3e} m (allowed {Gd.GPU_FACTOR * Gd.HAVERSINE_ERR_M[regime]:.3e})")
+        assert err.max() <= Gd.GPU_FACTOR * Gd.HAVERSINE_ERR_M[regime], (regime, err.max())

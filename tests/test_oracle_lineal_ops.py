@@ -2,6 +2,7 @@
 for them: the values geo's own documentation states, Vincenty's published test line, and — for Douglas-Peucker — an
 independent pure-Python recursion on exact rationals plus hand-checked cases of the rules that are particular to geo 0.27
 (last farthest point among equals, the INITIAL_MIN floor of 4 for rings)."""
+import math
 from fractions import Fraction as F
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
+from tests import simplify_ref as R
 
 
 def _dms(d, m, s):
@@ -70,46 +72,8 @@ def test_karney_geodesic_reproduces_published_lines(oracle):
 
 
 def _rdp_rational(pts, eps, min_pts):
-    """geo 0.27 compute_rdp on exact rationals (squared distances compared, so no rounding anywhere)"""
-    n = len(pts)
-    keep = [True] * n
-    state = {"len": n}
-
-    def d2(p, s, e):
-        dx, dy = e[0] - s[0], e[1] - s[1]
-        if dx == 0 and dy == 0:
-            return (p[0] - s[0]) ** 2 + (p[1] - s[1]) ** 2
-        dd = dx * dx + dy * dy
-        r = F((p[0] - s[0]) * dx + (p[1] - s[1]) * dy, dd)
-        if r <= 0:
-            return (p[0] - s[0]) ** 2 + (p[1] - s[1]) ** 2
-        if r >= 1:
-            return (p[0] - e[0]) ** 2 + (p[1] - e[1]) ** 2
-        c = (s[1] - p[1]) * dx - (s[0] - p[0]) * dy
-        return F(c * c, dd)
-
-    def rec(i, j):
-        if j - i < 2:
-            return
-        best, at = F(0), 0
-        for k in range(i + 1, j):
-            d = d2(pts[k], pts[i], pts[j])
-            if d >= best:
-                best, at = d, k
-        if best > eps * eps:
-            rec(i, at)
-            rec(at, j)
-            return
-        culled = j - i - 1
-        if state["len"] - culled < min_pts:
-            return
-        state["len"] -= culled
-        for k in range(i + 1, j):
-            keep[k] = False
-
-    if n >= 3 and eps > 0:
-        rec(0, n - 1)
-    return [p for p, k in zip(pts, keep) if k]
+    """geo 0.27 compute_rdp on exact rationals (tests/simplify_ref.py: squared distances compared, so no rounding anywhere)"""
+    return [p for p, k in zip(pts, R.rdp_exact(pts, float(eps), min_pts).keep) if k]
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -196,3 +160,35 @@ def test_karney_restatement_against_an_independent_solver(oracle):
         p2 = np.clip(p2, -90.0, 90.0)
         got, exp = c_oracle(l1, p1, l2, p2), gq.inverse_distance(l1, p1, l2, p2)
         assert np.all(np.abs(got - exp) <= 1e-9 * exp + 2e-8)
+
+
+def _pair_lines(l1, p1, l2, p2):
+    n = len(l1)
+    xy = np.empty((2 * n, 2))
+    xy[0::2, 0], xy[0::2, 1], xy[1::2, 0], xy[1::2, 1] = l1, p1, l2, p2
+    return GeoArrowArray(_abi.GEOM_LINESTRING, xy, geom_offsets=np.arange(0, 2 * n + 1, 2, dtype=np.int32))
+
+
+def test_haversine_against_a_high_precision_evaluation(oracle):
+    """the oracle's f64 half-angle formula against the same great-circle distance at 50 digits: its error per regime is what
+    tests/geodesic_ref.py records (the GPU test allows the kernel 4 times as much)"""
+    pytest.importorskip("mpmath")
+    from tests import geodesic_ref as Gd
+
+    for regime, q in Gd.haversine_pairs().items():
+        err = Gd.haversine_errors_m(oracle.geodesic_length(_pair_lines(*q), "haversine"), Gd.haversine_mp(*q))
+        print(f"haversine {regime}: largest error {err.max():.3e} m")
+        assert err.max() <= Gd.HAVERSINE_ERR_M[regime], (regime, err.max())
+
+
+def test_vincenty_restatement_and_the_pairs_far_from_the_iteration_limit(oracle):
+    from tests import geodesic_ref as Gd
+
+    l1, p1, l2, p2, is_nan, drawn = Gd.nearly_antipodal_pairs()
+    assert len(l1) == 1533 and drawn == 1600 and is_nan.sum() == 688  # pairs kept / drawn / failing to converge
+    v = oracle.geodesic_length(_pair_lines(l1, p1, l2, p2), "vincenty")
+    assert np.array_equal(np.isnan(v), is_nan)
+    mine = np.array([Gd.vincenty_py(*(float(x) for x in q))[0] for q in zip(l1, p1, l2, p2)])
+    assert np.all(np.abs(mine[~is_nan] - v[~is_nan]) <= 1e-12 * v[~is_nan])
+    assert math.isnan(Gd.vincenty_py(0.0, 0.0, 180.0, 0.0)[0]) and Gd.vincenty_py(10.0, 20.0, 10.0, 20.0)[0] == 0.0
+    assert [Gd.geodesic_group_size(c, s) for c, s in ((0, 0), (24, 1), (25, 1), (240, 10), (241, 10))] == [0, 4, 16, 4, 16]
