@@ -44,6 +44,8 @@ INDEX_PIP_LIGHT = 4
 INDEX_PIP_FULL = 8
 QUERY_CONTAINED, QUERY_INTERSECTING = 0, 1  # gpk_index_query_envelope modes
 PREDICATES = {"intersects": PRED_INTERSECTS, "contains": PRED_CONTAINS, "within": PRED_WITHIN}
+LP_INTERIOR, LP_BOUNDARY, LP_EXTERIOR = 1, 2, 4  # GPK_LP_*: the bits of the line x polygon relation mask
+LP_PRED_INTERSECTS, LP_PRED_WITHIN, LP_PRED_COVERED_BY, LP_PRED_CROSSES, LP_PRED_TOUCHES = 0, 1, 2, 3, 4  # GPK_LP_PRED_*
 
 
 class GeopolarsHipError(RuntimeError):
@@ -173,6 +175,11 @@ _PROTOS = {
         [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
     "gpk_dwithin_rowwise": (C.c_int32, [_VP, _VP, _VP, C.c_double, _VP, C.c_int32, _VP]),
+    "gpk_line_polygon_relation": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_line_polygon_join": (
+        C.c_int32,
+        [_VP, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
+    ),
     "gpk_closest_point_rowwise": (C.c_int32, [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_line_locate_point": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP]),
     "gpk_line_interpolate_point": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int32, _VP]),

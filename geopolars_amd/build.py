@@ -36,6 +36,7 @@ SOURCES = [
     "gpk_nearest.hip",
     "gpk_dwithin.hip",
     "gpk_linref.hip",
+    "gpk_linearea.hip",
     "gpk_hull.hip",
     "gpk_wkb.cpp",
     "gpk_arrow.cpp",

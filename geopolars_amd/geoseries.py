@@ -342,6 +342,54 @@ class GeoSeries:
         )
         return out.astype(bool)
 
+    # ---- line x polygon relations (gpk_linearea.hip) ---------------------------------------------
+    def line_polygon_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """The exact relation mask (uint8) of every row's line against its polygon (gpk_line_polygon_relation): bit 1 — the line has a
+        point in the polygon's interior, 2 — on one of its rings, 4 — outside it or strictly inside a hole; 0 for a null or empty row,
+        a NaN coordinate or an invalid ring.  One side is a LINESTRING / MULTILINESTRING column and the other a POLYGON / MULTIPOLYGON
+        column, in either order; `other_rows` pairs row i with other[other_rows[i]] and needs `self` to be the lineal side."""
+        line_first = relation_sides("line_polygon_relation", self._family(), other._family())
+        rows = relation_rows_arg("line_polygon_relation", self, other, other_rows, line_first)
+        lines, polys = (self, other) if line_first else (other, self)
+        out = np.empty(len(lines), dtype=np.uint8)
+        if len(out):
+            _abi.check(
+                _abi.lib().gpk_line_polygon_relation(
+                    lines.device().handle, polys.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
+                )
+            )
+        return out
+
+    def _relation(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
+        a, b = self._family(), other._family()
+        if not ((a in LINEAL and b in POLYGONAL) or (a in POLYGONAL and b in LINEAL)):
+            raise NotImplementedError(f"{name}: defined for LineString | MultiLineString x Polygon | MultiPolygon, not for {_abi_name(a)} x {_abi_name(b)}")
+        mask = self.line_polygon_relation(other, other_rows)
+        # the asymmetric names say which side is covered: a line covers no polygon, and no polygon is covered by a line
+        if name in ("covered_by", "covers") and (a in LINEAL) != (name == "covered_by"):
+            return np.zeros(len(mask), dtype=bool)
+        return mask_predicate(mask, name)
+
+    def crosses(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """the line has a point in the polygon's interior and one in its exterior (either order of the two families)"""
+        return self._relation(other, "crosses", other_rows)
+
+    def touches(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """the line meets the polygon's boundary but not its interior (either order of the two families)"""
+        return self._relation(other, "touches", other_rows)
+
+    def covered_by(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """no point of the line `self[i]` lies outside the polygon `other[i]`; always False with the polygons in `self`"""
+        return self._relation(other, "covered_by", other_rows)
+
+    def covers(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """no point of the line `other[i]` lies outside the polygon `self[i]`; always False with the lines in `self`"""
+        return self._relation(other, "covers", other_rows)
+
+    def disjoint(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """the line and the polygon share no point (False, like every relation, for unusable rows)"""
+        return self._relation(other, "disjoint", other_rows)
+
     # ---- linear referencing (gpk_linref.hip) -----------------------------------------------------
     def _family(self) -> int:
         return self._dev.geom_type if self._array is None else self._array.geom_type
@@ -449,6 +497,57 @@ def interpolate_distance_arg(lines: GeoSeries, distance) -> np.ndarray:
     if d.ndim != 1 or len(d) != len(lines):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"interpolate: {d.size} distances for {len(lines)} rows (a scalar or one per row)")
     return np.ascontiguousarray(d)
+
+
+LINEAL = (GEOM_LINESTRING, GEOM_MULTILINESTRING)
+POLYGONAL = (GEOM_POLYGON, GEOM_MULTIPOLYGON)
+
+# the line / area predicates over the relation mask (include/geopolars_hip.h); mask 0 — an unusable row — satisfies none of them
+MASK_PREDICATES = {
+    "intersects": lambda m: (m & 3) != 0,
+    "disjoint": lambda m: m == 4,
+    "covered_by": lambda m: (m != 0) & ((m & 4) == 0),
+    "within": lambda m: ((m & 1) != 0) & ((m & 4) == 0),
+    "crosses": lambda m: ((m & 1) != 0) & ((m & 4) != 0),
+    "touches": lambda m: ((m & 2) != 0) & ((m & 1) == 0),
+}
+MASK_PREDICATES["covers"] = MASK_PREDICATES["covered_by"]  # the polygon's view of the same relation
+MASK_PREDICATES["contains"] = MASK_PREDICATES["within"]
+
+
+def mask_predicate(mask, name: str) -> np.ndarray:
+    """a named line / polygon predicate from relation masks"""
+    if name not in MASK_PREDICATES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown line / polygon predicate {name!r}: one of {sorted(MASK_PREDICATES)}")
+    return MASK_PREDICATES[name](np.asarray(mask, dtype=np.uint8))
+
+
+def relation_sides(op: str, a: int, b: int) -> bool:
+    """True when family `a` is lineal and `b` polygonal, False for the other order; any other pair is refused as the C ABI would"""
+    if a in LINEAL and b in POLYGONAL:
+        return True
+    if a in POLYGONAL and b in LINEAL:
+        return False
+    raise _mismatch(f"{op}: LineString | MultiLineString x Polygon | MultiPolygon in either order (found {_abi_name(a)} x {_abi_name(b)})")
+
+
+def relation_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows, line_first: bool) -> Optional[np.ndarray]:
+    """the checks of line_polygon_relation before any device call: without a row map the row counts match; a row map (returned as
+    uint32) has one entry per row of `a` and needs `a` to be the lineal side unless it is the identity"""
+    if rows is not None:
+        try:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+        except (TypeError, ValueError, OverflowError):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+        if r.ndim != 1 or len(r) != len(a):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
+        if line_first:
+            return r
+        if not np.array_equal(r, np.arange(len(a), dtype=np.uint32)):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: a row map needs the lineal column on the left (it maps line rows to polygon rows)")
+    if len(a) != len(b):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+    return None
 
 
 def dwithin_distance_arg(distance) -> float:

@@ -5,6 +5,8 @@
     spatial_join            spatial_index.rs:37-204
     spatial_join_nearest    GeoPandas' sjoin_nearest (not in the reference): every point with the nearest geometries of another table
     spatial_join_dwithin    GeoPandas' sjoin(predicate="dwithin", distance=d) (not in the reference): every pair within a distance
+    spatial_join_relation   GeoPandas' sjoin(predicate=...) for lines x polygons (not in the reference): intersects, within, contains,
+                            covers, covered_by, crosses, touches from the exact relation mask
 
 The candidate generation + exact refine (spatial_index.rs:74-143) run on the GPU through
 gpk_spatial_join; this module only marshals buffers and — for dataframe-shaped callers — assembles
@@ -22,7 +24,7 @@ import numpy as np
 from . import _abi
 from ._abi import MEM_DEVICE, MEM_HOST, PREDICATES
 from .geoarrow import DeviceGeoArray
-from .geoseries import GeoSeries, dwithin_distance_arg
+from .geoseries import GeoSeries, dwithin_distance_arg, relation_sides
 
 
 def _ptr(t):
@@ -134,15 +136,15 @@ class SpatialJoinArgs:
     r_geom_type: int = -1
 
 
-def _pairs_with_retry(n: int, call, want_dist: bool = False):
+def _pairs_with_retry(n: int, call, want_dist: bool = False, payload=np.float64):
     """The host-buffer joins' sizing loop: one call in the common case; the ABI reports the exact total when the capacity is too small.
     call(pairs_ptr, dist_ptr or None, capacity, byref(n_pairs)) makes the C call and returns its code.  Returns the pairs and — when
-    asked for — their distances, cut to the total."""
+    asked for — their distances (or another per-pair payload of dtype `payload`), cut to the total."""
     n_pairs = C.c_int64(0)
     capacity = max(1024, 4 * n)
     while True:
         pairs = np.empty((capacity, 2), dtype=np.uint32)
-        dist = np.empty(capacity, dtype=np.float64) if want_dist else None
+        dist = np.empty(capacity, dtype=payload) if want_dist else None
         rc = call(pairs.ctypes.data, dist.ctypes.data if want_dist else None, capacity, C.byref(n_pairs))
         if rc == _abi.GPK_ERR_CAPACITY and int(n_pairs.value) > capacity:
             capacity = int(n_pairs.value)
@@ -491,3 +493,114 @@ def spatial_join_dwithin(lhs, rhs, options: Optional[SpatialJoinDWithinArgs] = N
     pairs, counts, dist = dwithin_pairs(lgeo, rgeo, d, options.r_index)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
     return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
+
+
+# ---- line x polygon predicate join (gpk_line_polygon_join) ----------------------------------------------------------------------
+
+# GeoPandas' predicate names -> (GPK_LP_PRED_*, the side that must hold the lines: "left", "right" or None for either)
+RELATION_PREDICATES = {
+    "intersects": (_abi.LP_PRED_INTERSECTS, None),
+    "crosses": (_abi.LP_PRED_CROSSES, None),
+    "touches": (_abi.LP_PRED_TOUCHES, None),
+    "within": (_abi.LP_PRED_WITHIN, "left"),
+    "covered_by": (_abi.LP_PRED_COVERED_BY, "left"),
+    "contains": (_abi.LP_PRED_WITHIN, "right"),
+    "covers": (_abi.LP_PRED_COVERED_BY, "right"),
+}
+
+
+def relation_predicate_arg(predicate: str, left_family: int, right_family: int) -> int:
+    """The GPK_LP_PRED_* id of a GeoPandas predicate name for a join of these two families, checked before any device call: one
+    side lineal and the other polygonal, and the name must fit the side that holds the lines (`within` and `covered_by` say it of
+    the left rows, so the lines are on the left; `contains` and `covers` need the polygons there)."""
+    if predicate not in RELATION_PREDICATES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"relation join: unknown predicate {predicate!r}: one of {sorted(RELATION_PREDICATES)}")
+    line_left = relation_sides("relation join", left_family, right_family)
+    pred, side = RELATION_PREDICATES[predicate]
+    if side is not None and (side == "left") != line_left:
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT,
+            f"relation join: {predicate!r} needs the {'lines' if side == 'left' else 'polygons'} on the left (a line {'covers' if predicate in ('contains', 'covers') else 'lies within'} no polygon)",
+        )
+    return pred
+
+
+@dataclass
+class SpatialJoinRelationArgs:
+    """Options of spatial_join_relation (GeoPandas' sjoin(predicate=...) for a lines table and a polygons table)."""
+
+    predicate: str = "intersects"  # intersects | within | contains | covers | covered_by | crosses | touches
+    join_type: str = "inner"  # "inner" | "left" (unmatched left rows once, with nulls on the right)
+    relation_col: Optional[str] = None  # name of a uint8 column with each pair's relation mask (null for unmatched left rows)
+    l_suffix: Optional[str] = "_left"
+    r_suffix: Optional[str] = "_right"
+    r_index: Optional[SpatialIndex] = None
+    l_geom_type: int = -1  # as in SpatialJoinArgs
+    r_geom_type: int = -1
+
+
+def relation_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    predicate: str = "intersects",
+    r_index: Optional[SpatialIndex] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every (l, r) of a lines column and a polygons column (either order) whose exact relation satisfies `predicate`: (pairs (H, 2)
+    uint32 sorted by (l, r), counts (n_left,) uint32, masks (H,) uint8 — what GeoSeries.line_polygon_relation gives for the pairs).
+    Host-buffer variant: the pair buffer is sized like join_pairs'."""
+    pred = relation_predicate_arg(predicate, left._family(), right._family())
+    lib = _abi.lib()
+    n = len(left)
+    counts = np.zeros(n, dtype=np.uint32)
+    rh = r_index.handle if r_index is not None else None
+    call = lambda pairs_ptr, mask_ptr, capacity, n_pairs: lib.gpk_line_polygon_join(  # noqa: E731
+        left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs_ptr, mask_ptr, capacity, n_pairs, MEM_HOST, None)
+    pairs, mask = _pairs_with_retry(n, call, want_dist=True, payload=np.uint8)
+    return pairs, counts, mask
+
+
+def relation_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    predicate: str,
+    out_counts,
+    out_pairs,
+    out_mask=None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_mask (cap,) uint8 torch CUDA tensors (any may
+    be None; out_pairs None = count only; without out_mask a pair's walk ends as soon as its predicate is settled) are filled in place
+    on `stream`; returns the number of pairs."""
+    pred = relation_predicate_arg(predicate, left.geom_type, right.geom_type)
+    n_pairs = C.c_int64(0)
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_line_polygon_join(
+        left.handle, right.handle, rh, pred, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_mask), cap, C.byref(n_pairs), MEM_DEVICE, stream))
+    return int(n_pairs.value)
+
+
+def spatial_join_relation(lhs, rhs, options: Optional[SpatialJoinRelationArgs] = None):
+    """GeoPandas' sjoin(predicate=...) over two pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes
+    them), one of lines and one of polygons: every left row with every right row in the relation, shaped like spatial_join's result —
+    suffixed left columns, suffixed right columns, then `relation_col` (the pair's mask) when asked for."""
+    import pyarrow as pa
+
+    options = options or SpatialJoinRelationArgs()
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"relation join: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    if options.predicate not in RELATION_PREDICATES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"relation join: unknown predicate {options.predicate!r}: one of {sorted(RELATION_PREDICATES)}")
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, mask = relation_pairs(lgeo, rgeo, options.predicate, options.r_index)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
+    if options.relation_col is not None:
+        matched = ri >= 0
+        m = np.zeros(len(ri), dtype=np.uint8)
+        m[matched] = mask
+        table = table.append_column(options.relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
+    return table

@@ -498,6 +498,54 @@ int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray* right, co
 int32_t gpk_dwithin_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double distance, uint8_t* out,
                             int32_t out_space, void* stream);
 
+/* ---- line x polygon relations (gpk_linearea.hip) ----------------------------------------------------------------------------------
+ * Where a line runs relative to a polygonal geometry.  L = a LINESTRING or MULTILINESTRING row, taken as the closed set of all its
+ * segments and coordinates; P = a POLYGON or MULTIPOLYGON row.  The relation is a 3-bit mask: */
+#define GPK_LP_INTERIOR 1 /* L has a point in the interior of P (inside a part's shell, outside its holes, off every ring) */
+#define GPK_LP_BOUNDARY 2 /* L has a point on a ring of P */
+#define GPK_LP_EXTERIOR 4 /* L has a point outside every part of P, or strictly inside a hole */
+/* P's interior and exterior are open sets, so every named line / area predicate is a function of the mask alone:
+ *   intersects                 mask & 3                      disjoint             mask == 4
+ *   covered_by / covers        mask != 0 && !(mask & 4)      within / contains    (mask & 1) && !(mask & 4)
+ *   crosses                    (mask & 1) && (mask & 4)      touches              (mask & 2) && !(mask & 1)
+ * The mask is EXACT — the set-theoretic answer, decided with exact orientation signs only, no tolerance, the same at any placement of
+ * the same figure — for every usable L and every OGC-valid P.  Valid allows rings that touch each other at single points (hole-shell,
+ * hole-hole, part-part); a line may pass through such a point, and the side of the piece next to it is judged against the whole
+ * geometry.  Rows:
+ *   line row unusable      null, no coordinate, or a NaN coordinate: mask 0
+ *   degenerate line        a one-coordinate sequence or repeated coordinates: the point set of its coordinates
+ *   polygon row unusable   null, or no non-empty member: mask 0
+ *   invalid ring           a non-empty ring that is unclosed, has fewer than 4 coordinates, a NaN or no turning extreme vertex: mask 0
+ *                          (the rule and the decision of `contains`)
+ *   empty members of a multi-geometry are ignored
+ *   invalid polygon        (self-crossing rings, overlapping parts) the mask is unspecified; the call terminates normally
+ *
+ * Row-wise: out_mask[i] = mask(lines[i], polys[poly_rows[i]]).  `lines` is always the first argument.  `poly_rows` (same space as the
+ * output) as `b_rows` of gpk_distance_rowwise: NULL = identity (the row counts must then match), an entry >= n_geoms(polys) gives mask
+ * 0.  Any other family on either side: GPK_ERR_MISMATCHED_GEOMETRY; a wrong count: GPK_ERR_INVALID_ARGUMENT; both before any device
+ * work.  Outputs are stream-ordered (host outputs: the call waits for them).  out_mask[n_geoms(lines)] bytes. */
+int32_t gpk_line_polygon_relation(const gpk_geoarray* lines, const gpk_geoarray* polys, const uint32_t* poly_rows, uint8_t* out_mask,
+                                  int32_t out_space, void* stream);
+#define GPK_LP_PRED_INTERSECTS 0
+#define GPK_LP_PRED_WITHIN 1     /* line within polygon == polygon contains line */
+#define GPK_LP_PRED_COVERED_BY 2 /* == polygon covers line */
+#define GPK_LP_PRED_CROSSES 3
+#define GPK_LP_PRED_TOUCHES 4
+/* Line x polygon predicate join (GeoPandas sjoin(predicate=...) on roads x districts): every (l, r) whose mask satisfies `predicate`.
+ * One side is LINESTRING | MULTILINESTRING and the other POLYGON | MULTIPOLYGON, in either order (any other pair:
+ * GPK_ERR_MISMATCHED_GEOMETRY); the predicate names the line / polygon relation whichever side the line is on.  An unknown predicate
+ * id: GPK_ERR_INVALID_ARGUMENT.  Unusable rows (mask 0) never match.
+ *   out_counts[n_left]   u32 matches per left row (may be NULL)
+ *   out_pairs[2*cap]     u32 (l, r) interleaved, sorted by (l, r) (NULL with cap == 0: count-only mode)
+ *   out_mask[cap]        u8 the full mask of each pair (may be NULL: a pair's walk then ends as soon as its predicate is settled)
+ *   *n_pairs             total, always set; GPK_ERR_CAPACITY when > cap and pairs were asked for
+ * `left_row_base` is added to every emitted l.  All buffers live in `out_space`.  `right_index`: an index of `right` carrying the bbox
+ * grid (else GPK_ERR_INVALID_ARGUMENT), or NULL: a GPK_INDEX_BBOX_GRID index is built for the call and freed.  Synchronous, like
+ * gpk_dwithin_join.  gpk_spatial_join is unchanged: its lines x polygons arm still returns nothing, as the reference's does. */
+int32_t gpk_line_polygon_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
+                              uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask, int64_t pair_capacity,
+                              int64_t* n_pairs, int32_t out_space, void* stream);
+
 /* ---- linear referencing (gpk_linref.hip) ------------------------------------------------------------------------------------
  * Where on a geometry the nearest point lies, how far along a line it is, and the point at a measure along a line (geo 0.27
  * ClosestPoint / LineLocatePoint / LineInterpolatePoint; shapely / GeoPandas nearest_points, shortest_line, project, interpolate).
