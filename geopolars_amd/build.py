@@ -37,6 +37,7 @@ SOURCES = [
     "gpk_dwithin.hip",
     "gpk_linref.hip",
     "gpk_linearea.hip",
+    "gpk_polyrel.hip",
     "gpk_hull.hip",
     "gpk_wkb.cpp",
     "gpk_arrow.cpp",

@@ -233,6 +233,38 @@ __device__ __forceinline__ RowSeqs line_seqs(const DevGeo& L, int64_t i) {
     return L.type == GPK_GEOM_LINESTRING ? row_seqs<GPK_GEOM_LINESTRING>(L, i) : row_seqs<GPK_GEOM_MULTILINESTRING>(L, i);
 }
 
+// The walk itself: the mask of the coordinate sequences `l` (no NaN) against the usable polygon row `polys`[p0, p1) with the box of its
+// shells.  `settled(mask)` ends the walk early (the mask is then partial).  The sequences of a line row — or the rings of another
+// polygonal row taken as closed lines (gpk_polyrel.h).  Same value on every lane of the group.
+template <int G, class Settled>
+__device__ inline int sequences_mask_group(const RowSeqs& l, const DevGeo& polys, int p0, int p1, double4 box, int lane, Settled settled) {
+    int mask = 0;
+    for (int s = l.s0; s < l.s1; ++s) {
+        const int c0 = l.so[s], c1 = l.so[s + 1];
+        if (c1 <= c0) continue;
+        double2 p = l.xy[c0];
+        int pp = coord_bits<G>(polys, p0, p1, box, p, lane);
+        mask |= pp;
+        for (int c = c0 + 1; c < c1; ++c) {
+            if (settled(mask)) return mask;
+            const double2 q = l.xy[c];
+            if (cont::same_xy(p, q)) continue;
+            const int pq = coord_bits<G>(polys, p0, p1, box, q, lane);
+            mask |= pq;
+            if ((pp | pq) == (GPK_LP_INTERIOR | GPK_LP_EXTERIOR)) {
+                mask |= GPK_LP_BOUNDARY;  // from the interior to the exterior: the segment meets a ring on the way
+            } else if (!(fmax(p.x, q.x) < box.x || fmin(p.x, q.x) > box.z || fmax(p.y, q.y) < box.y || fmin(p.y, q.y) > box.w)) {
+                if (pp == GPK_LP_BOUNDARY) mask |= side_bits<G>(polys, p0, p1, p, q, lane);
+                if (pq == GPK_LP_BOUNDARY) mask |= side_bits<G>(polys, p0, p1, q, p, lane);
+                if (!settled(mask)) mask |= segment_events<G>(polys, p0, p1, p, q, lane);
+            }
+            p = q;
+            pp = pq;
+        }
+    }
+    return mask;
+}
+
 // The mask of row i of `lines` (LINESTRING | MULTILINESTRING) against row j of `polys` (POLYGON | MULTIPOLYGON); rows out of range
 // behave like null rows.  With `st` the walk ends as soon as the bits a caller needs are settled (the mask is then partial).
 // Same value on every lane of the group.
@@ -254,32 +286,7 @@ __device__ inline int line_polygon_mask_group(const DevGeo& lines, int64_t i, co
     dev::geom_parts(polys, j, p0, p1);
     double4 box;
     if (!polygon_row_ok<G>(polys, p0, p1, lane, box)) return 0;
-
-    int mask = 0;
-    for (int s = l.s0; s < l.s1; ++s) {
-        const int c0 = l.so[s], c1 = l.so[s + 1];
-        if (c1 <= c0) continue;
-        double2 p = l.xy[c0];
-        int pp = coord_bits<G>(polys, p0, p1, box, p, lane);
-        mask |= pp;
-        for (int c = c0 + 1; c < c1; ++c) {
-            if (done(mask, st)) return mask;
-            const double2 q = l.xy[c];
-            if (cont::same_xy(p, q)) continue;
-            const int pq = coord_bits<G>(polys, p0, p1, box, q, lane);
-            mask |= pq;
-            if ((pp | pq) == (GPK_LP_INTERIOR | GPK_LP_EXTERIOR)) {
-                mask |= GPK_LP_BOUNDARY;  // from the interior to the exterior: the segment meets a ring on the way
-            } else if (!(fmax(p.x, q.x) < box.x || fmin(p.x, q.x) > box.z || fmax(p.y, q.y) < box.y || fmin(p.y, q.y) > box.w)) {
-                if (pp == GPK_LP_BOUNDARY) mask |= side_bits<G>(polys, p0, p1, p, q, lane);
-                if (pq == GPK_LP_BOUNDARY) mask |= side_bits<G>(polys, p0, p1, q, p, lane);
-                if (!done(mask, st)) mask |= segment_events<G>(polys, p0, p1, p, q, lane);
-            }
-            p = q;
-            pp = pq;
-        }
-    }
-    return mask;
+    return sequences_mask_group<G>(l, polys, p0, p1, box, lane, [st](int m) { return done(m, st); });
 }
 
 // lanes per pair: ring edges are what the lanes stride over, so the polygon column's mean coordinate count decides — about four

@@ -362,6 +362,8 @@ class GeoSeries:
 
     def _relation(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         a, b = self._family(), other._family()
+        if a in POLYGONAL and b in POLYGONAL:
+            return polygon_mask_predicate(self.polygon_relation(other, other_rows), name)
         if not ((a in LINEAL and b in POLYGONAL) or (a in POLYGONAL and b in LINEAL)):
             raise NotImplementedError(f"{name}: defined for LineString | MultiLineString x Polygon | MultiPolygon, not for {_abi_name(a)} x {_abi_name(b)}")
         mask = self.line_polygon_relation(other, other_rows)
@@ -389,6 +391,41 @@ class GeoSeries:
     def disjoint(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
         """the line and the polygon share no point (False, like every relation, for unusable rows)"""
         return self._relation(other, "disjoint", other_rows)
+
+    # ---- polygon x polygon relations (gpk_polyrel.hip) -------------------------------------------
+    def polygon_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """The exact relation mask (uint8) of every row's polygon A against its polygon B = other[other_rows[i]]
+        (gpk_polygon_relation): bit 1 — the interiors share a point, 2 — a ring of A and a ring of B share a point, 4 — A's interior has
+        a point outside B, 8 — B's interior has a point outside A; 0 for a null or empty row or an invalid ring on either side.  Both
+        columns are POLYGON / MULTIPOLYGON.  crosses, touches, covers, covered_by and disjoint take two such columns too."""
+        rows = polygon_relation_args("polygon_relation", self, other, other_rows)
+        out = np.empty(len(self), dtype=np.uint8)
+        if len(out):
+            _abi.check(
+                _abi.lib().gpk_polygon_relation(
+                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
+                )
+            )
+        return out
+
+    def _polygon_relation(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
+        a, b = self._family(), other._family()
+        if not (a in POLYGONAL and b in POLYGONAL):
+            raise NotImplementedError(f"{name}: defined for Polygon | MultiPolygon x Polygon | MultiPolygon, not for {_abi_name(a)} x {_abi_name(b)}")
+        return polygon_mask_predicate(self.polygon_relation(other, other_rows), name)
+
+    def overlaps(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """the two polygons share area and each has area outside the other"""
+        return self._polygon_relation(other, "overlaps", other_rows)
+
+    def geom_equals(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """the two polygons are the same point set, however their rings are written (start, winding, extra collinear vertices, order
+        of the parts)"""
+        return self._polygon_relation(other, "equals", other_rows)
+
+    def contains_properly(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """the polygon `other[i]` lies in the interior of `self[i]`: contained without touching its boundary"""
+        return self._polygon_relation(other, "contains_properly", other_rows)
 
     # ---- linear referencing (gpk_linref.hip) -----------------------------------------------------
     def _family(self) -> int:
@@ -520,6 +557,50 @@ def mask_predicate(mask, name: str) -> np.ndarray:
     if name not in MASK_PREDICATES:
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown line / polygon predicate {name!r}: one of {sorted(MASK_PREDICATES)}")
     return MASK_PREDICATES[name](np.asarray(mask, dtype=np.uint8))
+
+
+# the area / area predicates over the polygon x polygon relation mask (include/geopolars_hip.h); mask 0 satisfies none of them
+POLYGON_MASK_PREDICATES = {
+    "intersects": lambda m: (m & 3) != 0,
+    "disjoint": lambda m: (m != 0) & ((m & 3) == 0),
+    "touches": lambda m: ((m & 2) != 0) & ((m & 1) == 0),
+    "overlaps": lambda m: (m & 13) == 13,
+    "within": lambda m: ((m & 1) != 0) & ((m & 4) == 0),
+    "contains": lambda m: ((m & 1) != 0) & ((m & 8) == 0),
+    "equals": lambda m: ((m & 1) != 0) & ((m & 12) == 0),
+    "contains_properly": lambda m: (m & 11) == 1,
+    "crosses": lambda m: np.zeros(m.shape, dtype=bool),  # two areas never cross
+}
+POLYGON_MASK_PREDICATES["covered_by"] = POLYGON_MASK_PREDICATES["within"]  # closed regular sets: covered means within
+POLYGON_MASK_PREDICATES["covers"] = POLYGON_MASK_PREDICATES["contains"]
+
+
+def polygon_mask_predicate(mask, name: str) -> np.ndarray:
+    """a named polygon / polygon predicate from relation masks"""
+    if name not in POLYGON_MASK_PREDICATES:
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT, f"unknown polygon / polygon predicate {name!r}: one of {sorted(POLYGON_MASK_PREDICATES)}"
+        )
+    return POLYGON_MASK_PREDICATES[name](np.asarray(mask, dtype=np.uint8))
+
+
+def polygon_relation_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
+    """the checks of polygon_relation before any device call, in the C ABI's order: both families polygonal, then the row map (returned
+    as uint32) with one entry per row of `a`, or equal row counts without one"""
+    fa, fb = a._family(), b._family()
+    if fa not in POLYGONAL or fb not in POLYGONAL:
+        raise _mismatch(f"{op}: Polygon | MultiPolygon x Polygon | MultiPolygon (found {_abi_name(fa)} x {_abi_name(fb)})")
+    if rows is not None:
+        try:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+        except (TypeError, ValueError, OverflowError):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+        if r.ndim != 1 or len(r) != len(a):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
+        return r
+    if len(a) != len(b):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+    return None
 
 
 def relation_sides(op: str, a: int, b: int) -> bool:

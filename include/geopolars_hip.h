@@ -546,6 +546,54 @@ int32_t gpk_line_polygon_join(const gpk_geoarray* left, const gpk_geoarray* righ
                               uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask, int64_t pair_capacity,
                               int64_t* n_pairs, int32_t out_space, void* stream);
 
+/* ---- polygon x polygon relations (gpk_polyrel.hip) --------------------------------------------------------------------------------
+ * How two polygonal geometries lie to each other.  A, B = POLYGON or MULTIPOLYGON rows, taken as closed regular sets: the interior
+ * (inside a part's shell, outside its holes, off every ring) and the exterior (outside every part, or strictly inside a hole) are
+ * open.  The relation is a 4-bit mask: */
+#define GPK_PP_INTERIORS 1  /* the interiors of A and B share a point */
+#define GPK_PP_BOUNDARIES 2 /* a ring of A and a ring of B share a point */
+#define GPK_PP_A_OUTSIDE 4  /* the interior of A has a point in the exterior of B (A is not a subset of B) */
+#define GPK_PP_B_OUTSIDE 8  /* the interior of B has a point in the exterior of A (B is not a subset of A) */
+/* Every named area / area predicate is a function of the mask alone:
+ *   intersects                 mask & 3                       disjoint             mask != 0 && !(mask & 3)
+ *   touches                    (mask & 2) && !(mask & 1)      overlaps             (mask & 13) == 13
+ *   within / covered_by        (mask & 1) && !(mask & 4)      contains / covers    (mask & 1) && !(mask & 8)
+ *   equals                     (mask & 1) && !(mask & 12)     contains_properly    (mask & 11) == 1
+ *   crosses                    never
+ * A usable pair never has mask 0; only the masks 3, 5, 7, 9, 11, 12, 13, 14 and 15 occur.  mask(B, A) is mask(A, B) with the bits 4
+ * and 8 swapped.  The mask is EXACT — the set-theoretic answer, decided with exact orientation signs only, no tolerance, the same at
+ * any placement of the same figures — for OGC-valid operands.  Valid allows rings of one geometry that touch each other at single
+ * points (hole-shell, hole-hole, part-part), and the other geometry may pass through such a point.  Rows, on either side:
+ *   row unusable           null, or no non-empty member: mask 0
+ *   invalid ring           a non-empty ring that is unclosed, has fewer than 4 coordinates, a NaN or no turning extreme vertex: mask 0
+ *                          (the rule and the decision of `contains`)
+ *   empty members of a multi-geometry are ignored
+ *   invalid polygon        (self-crossing rings, overlapping parts) the mask is unspecified; the call terminates normally
+ *
+ * Row-wise: out_mask[i] = mask(a[i], b[b_rows[i]]).  `b_rows` (same space as the output) as in gpk_line_polygon_relation: NULL =
+ * identity (the row counts must then match), an entry >= n_geoms(b) gives mask 0.  Any other family on either side:
+ * GPK_ERR_MISMATCHED_GEOMETRY; a wrong count: GPK_ERR_INVALID_ARGUMENT; both before any device work.  Outputs are stream-ordered (host
+ * outputs: the call waits for them).  out_mask[n_geoms(a)] bytes. */
+int32_t gpk_polygon_relation(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, uint8_t* out_mask, int32_t out_space,
+                             void* stream);
+#define GPK_PP_PRED_INTERSECTS 0
+#define GPK_PP_PRED_WITHIN 1 /* left within right (== covered_by: both sets are closed and regular) */
+#define GPK_PP_PRED_CONTAINS 2 /* left contains right (== covers) */
+#define GPK_PP_PRED_TOUCHES 3
+#define GPK_PP_PRED_OVERLAPS 4
+#define GPK_PP_PRED_EQUALS 5
+#define GPK_PP_PRED_CONTAINS_PROPERLY 6 /* right lies in the interior of left: no shared boundary point */
+/* Polygon x polygon predicate join (GeoPandas sjoin(predicate=...) on two polygon tables): every (l, r) whose mask — always A = the
+ * left row, B = the right row — satisfies `predicate`.  Both sides POLYGON | MULTIPOLYGON (else GPK_ERR_MISMATCHED_GEOMETRY); an
+ * unknown predicate id: GPK_ERR_INVALID_ARGUMENT.  Unusable rows (mask 0) never match.  `left` and `right` may be the same array (a
+ * self-join, for adjacency): pair (i, i) then appears for intersects / within / contains / equals and not for touches / overlaps.
+ * Outputs (out_counts, out_pairs, out_mask, *n_pairs), the capacity rule, count-only mode, `left_row_base`, `right_index` (NULL: a
+ * GPK_INDEX_BBOX_GRID index is built for the call and freed) and the error order are those of gpk_line_polygon_join.  Without out_mask
+ * a pair's walk ends as soon as its predicate is settled.  Synchronous.  gpk_spatial_join and gpk_predicate_rowwise are unchanged. */
+int32_t gpk_polygon_relation_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
+                                  uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask,
+                                  int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
+
 /* ---- linear referencing (gpk_linref.hip) ------------------------------------------------------------------------------------
  * Where on a geometry the nearest point lies, how far along a line it is, and the point at a measure along a line (geo 0.27
  * ClosestPoint / LineLocatePoint / LineInterpolatePoint; shapely / GeoPandas nearest_points, shortest_line, project, interpolate).
