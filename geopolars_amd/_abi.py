@@ -188,6 +188,8 @@ _PROTOS = {
         C.c_int32,
         [_VP, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
+    "gpk_validity": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_is_simple": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
     "gpk_closest_point_rowwise": (C.c_int32, [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_line_locate_point": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP]),
     "gpk_line_interpolate_point": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int32, _VP]),

@@ -427,6 +427,37 @@ class GeoSeries:
         """the polygon `other[i]` lies in the interior of `self[i]`: contained without touching its boundary"""
         return self._polygon_relation(other, "contains_properly", other_rows)
 
+    # ---- validity and simplicity (gpk_validity.hip) ----------------------------------------------
+    def _validity(self, op: str, return_where: bool):
+        validity_family_arg(op, self._family(), POLYGONAL)
+        n = len(self)
+        code = np.empty(n, dtype=np.uint8)
+        where = np.empty(n, dtype=np.int32) if return_where else None
+        if n:
+            _abi.check(_abi.lib().gpk_validity(self.device().handle, code.ctypes.data, where.ctypes.data if return_where else None, MEM_HOST, None))
+        return code, where
+
+    def is_valid_reason(self, return_where: bool = False):
+        """Why a polygon row is not OGC-valid (gpk_validity): one uint8 code per row, 0 for a valid row — VALIDITY_NAMES[code] names
+        it; the lowest code that applies.  With `return_where` also the int32 index, in the column's coordinate buffer, of the
+        coordinate, segment, ring or member at fault (-1 for valid and null rows).  A POLYGON or MULTIPOLYGON column."""
+        code, where = self._validity("is_valid_reason", return_where)
+        return (code, where) if return_where else code
+
+    def is_valid(self) -> np.ndarray:
+        """GeoPandas' GeoSeries.is_valid for a POLYGON or MULTIPOLYGON column: True where the relation masks are exact for the row
+        (is_valid_reason gives code 0; a row without a non-empty member is valid, a null row is not)"""
+        return self._validity("is_valid", False)[0] == 0
+
+    def is_simple(self) -> np.ndarray:
+        """GeoPandas' GeoSeries.is_simple for a LINESTRING or MULTILINESTRING column (gpk_is_simple): no member meets itself except a
+        closed one at its start, and two members share only common end points; False for null rows and non-finite coordinates"""
+        validity_family_arg("is_simple", self._family(), LINEAL)
+        out = np.empty(len(self), dtype=np.uint8)
+        if len(out):
+            _abi.check(_abi.lib().gpk_is_simple(self.device().handle, out.ctypes.data, MEM_HOST, None))
+        return out.astype(bool)
+
     # ---- linear referencing (gpk_linref.hip) -----------------------------------------------------
     def _family(self) -> int:
         return self._dev.geom_type if self._array is None else self._array.geom_type
@@ -573,6 +604,28 @@ POLYGON_MASK_PREDICATES = {
 }
 POLYGON_MASK_PREDICATES["covered_by"] = POLYGON_MASK_PREDICATES["within"]  # closed regular sets: covered means within
 POLYGON_MASK_PREDICATES["covers"] = POLYGON_MASK_PREDICATES["contains"]
+
+
+# the codes of gpk_validity (include/geopolars_hip.h: GPK_VALID, GPK_INVALID_*), by value
+VALIDITY_NAMES = (
+    "valid",
+    "invalid coordinate",
+    "invalid ring shape",
+    "ring self-intersection",
+    "rings cross",
+    "hole outside shell",
+    "nested holes",
+    "nested members",
+    "disconnected interior",
+    "null",
+)
+
+
+def validity_family_arg(op: str, family: int, allowed) -> None:
+    """the family check of is_valid / is_valid_reason / is_simple before any device call, refused as the C ABI would"""
+    if family not in allowed:
+        want = "Polygon | MultiPolygon" if allowed is POLYGONAL else "LineString | MultiLineString"
+        raise _mismatch(f"{op}: {want} (found {_abi_name(family)})")
 
 
 def polygon_mask_predicate(mask, name: str) -> np.ndarray:

@@ -519,6 +519,7 @@ int32_t gpk_dwithin_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const 
  *                          (the rule and the decision of `contains`)
  *   empty members of a multi-geometry are ignored
  *   invalid polygon        (self-crossing rings, overlapping parts) the mask is unspecified; the call terminates normally
+ *                          gpk_validity tells which rows are valid, and why the others are not.
  *
  * Row-wise: out_mask[i] = mask(lines[i], polys[poly_rows[i]]).  `lines` is always the first argument.  `poly_rows` (same space as the
  * output) as `b_rows` of gpk_distance_rowwise: NULL = identity (the row counts must then match), an entry >= n_geoms(polys) gives mask
@@ -569,6 +570,7 @@ int32_t gpk_line_polygon_join(const gpk_geoarray* left, const gpk_geoarray* righ
  *                          (the rule and the decision of `contains`)
  *   empty members of a multi-geometry are ignored
  *   invalid polygon        (self-crossing rings, overlapping parts) the mask is unspecified; the call terminates normally
+ *                          gpk_validity tells which rows are valid, and why the others are not.
  *
  * Row-wise: out_mask[i] = mask(a[i], b[b_rows[i]]).  `b_rows` (same space as the output) as in gpk_line_polygon_relation: NULL =
  * identity (the row counts must then match), an entry >= n_geoms(b) gives mask 0.  Any other family on either side:
@@ -593,6 +595,48 @@ int32_t gpk_polygon_relation(const gpk_geoarray* a, const gpk_geoarray* b, const
 int32_t gpk_polygon_relation_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
                                   uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask,
                                   int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
+
+/* ---- validity and simplicity (gpk_validity.hip) -------------------------------------------------------------------------------------
+ * Is a polygonal row OGC-valid — the condition under which the relation masks above are exact — and if not, why not and where.
+ * `a` is a POLYGON or MULTIPOLYGON column (any other family: GPK_ERR_MISMATCHED_GEOMETRY, before any device work).  Only the non-empty
+ * members of a row (at least one ring, a non-empty shell) and their non-empty rings count, as in the relation calls.  The code of a
+ * row is the LOWEST one that applies, so each code is stated for rows to which no lower one applies: */
+#define GPK_VALID 0                          /* none of the codes below; a row without a non-empty member is valid */
+#define GPK_INVALID_COORDINATE 1             /* a coordinate is NaN or infinite */
+#define GPK_INVALID_RING_SHAPE 2             /* a ring has fewer than 4 coordinates, or its first and last coordinates differ */
+#define GPK_INVALID_RING_SELF_INTERSECTION 3 /* within one ring, zero-length segments dropped: two consecutive segments share more than
+                                              * their common end point, or two others share any point (the closing vertex joins the last
+                                              * and the first segment); also spikes, all-collinear rings, a ring of equal coordinates */
+#define GPK_INVALID_RINGS_CROSS 4            /* two rings of the row share a piece of positive length, or one has points strictly inside
+                                              * and strictly outside the other */
+#define GPK_INVALID_HOLE_OUTSIDE_SHELL 5     /* a hole has a point strictly outside its member's shell */
+#define GPK_INVALID_NESTED_HOLES 6           /* a hole has a point strictly inside another hole of its member */
+#define GPK_INVALID_NESTED_MEMBERS 7         /* the interiors of two members share a point (a shell inside a hole of another member,
+                                              * touching it at single points at most, is valid) */
+#define GPK_INVALID_DISCONNECTED_INTERIOR 8  /* the interior of a member is not connected: the graph of its rings and of the distinct
+                                              * points where two or more of them touch has a cycle */
+#define GPK_INVALID_NULL 9                   /* the row is null */
+/* Every ring that the relation calls reject (their "invalid ring" rule) has a code from 1 to 3.  out_where[i] (may be NULL) is an index
+ * into the column's coordinate buffer, -1 for the codes 0 and 9:
+ *   1      the lowest offending coordinate             2      the first coordinate of the lowest offending ring
+ *   3, 4   the lowest i such that the segment starting at coordinate i takes part in such a fault: it shares the forbidden point or
+ *          piece with another segment of its ring (3), it shares a piece with a segment of another ring, or it passes through a point
+ *          where its ring changes sides of another ring or leaves it after running along it (4); for a ring of equal coordinates
+ *          only (3) its first coordinate
+ *   5, 6   the first coordinate of the lowest-numbered offending hole (6: the hole that lies inside another one)
+ *   7      the first coordinate of the lowest-numbered member whose interior meets the interior of a lower-numbered member
+ *   8      the first coordinate of the lowest-numbered member whose interior is not connected
+ * Every decision is an exact orientation sign or an exact coordinate comparison: no tolerance, the same answer at any placement of the
+ * same figure.  Stream-ordered (a host output: the call waits for it); nothing is done for a column without rows.
+ * out_code[n_geoms(a)] bytes, out_where[n_geoms(a)] int32. */
+int32_t gpk_validity(const gpk_geoarray* a, uint8_t* out_code, int32_t* out_where, int32_t out_space, void* stream);
+/* Is a lineal row simple.  `a` is a LINESTRING or MULTILINESTRING column (any other family: GPK_ERR_MISMATCHED_GEOMETRY).  out[i] = 1
+ * when, with zero-length segments dropped, (a) in every member consecutive segments share only their common end point and other
+ * segments share nothing, except that the first and the last segment of a closed member share its start, and (b) two members share
+ * only points that are end points of both — a closed member has no end points.  A member of one coordinate or of equal coordinates is
+ * a point: it has no segments and takes part in neither rule.  A row without coordinates is simple.  out[i] = 0 otherwise, and for a
+ * null row and a row with a NaN or infinite coordinate.  Exact, stream-ordered and sized like gpk_validity.  out[n_geoms(a)] bytes. */
+int32_t gpk_is_simple(const gpk_geoarray* a, uint8_t* out, int32_t out_space, void* stream);
 
 /* ---- linear referencing (gpk_linref.hip) ------------------------------------------------------------------------------------
  * Where on a geometry the nearest point lies, how far along a line it is, and the point at a measure along a line (geo 0.27

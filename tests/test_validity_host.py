@@ -1,0 +1,90 @@
+"""Validity and simplicity, host side: the C ABI symbols, the header's codes, the family checks that refuse a call before the library is
+opened, and the older surfaces that must not move."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from geopolars_amd import _abi
+from geopolars_amd.geoarrow import GeoArrowArray
+from geopolars_amd.geoseries import VALIDITY_NAMES, GeoSeries
+from tests import validity_ref as V
+
+
+def test_exported_symbols_name_the_validity_calls():
+    assert "gpk_validity" in _abi.EXPORTED_SYMBOLS and "gpk_is_simple" in _abi.EXPORTED_SYMBOLS
+    assert len(_abi._PROTOS["gpk_validity"][1]) == 5
+    assert len(_abi._PROTOS["gpk_is_simple"][1]) == 4
+
+
+def test_built_library_exports_the_validity_calls():
+    from geopolars_amd import build
+
+    lib = build.build()
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert {"gpk_validity", "gpk_is_simple"} <= names
+
+
+def test_header_states_the_ten_codes():
+    root = os.path.dirname(_abi.HERE)
+    text = open(os.path.join(root, "include", "geopolars_hip.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define (GPK_VALID|GPK_INVALID_\w+) (\d+)", text)}
+    assert defs == {"GPK_VALID": 0, "GPK_INVALID_COORDINATE": 1, "GPK_INVALID_RING_SHAPE": 2, "GPK_INVALID_RING_SELF_INTERSECTION": 3,
+                    "GPK_INVALID_RINGS_CROSS": 4, "GPK_INVALID_HOLE_OUTSIDE_SHELL": 5, "GPK_INVALID_NESTED_HOLES": 6,
+                    "GPK_INVALID_NESTED_MEMBERS": 7, "GPK_INVALID_DISCONNECTED_INTERIOR": 8, "GPK_INVALID_NULL": 9}
+    assert len(VALIDITY_NAMES) == 10 and VALIDITY_NAMES[0] == "valid" and VALIDITY_NAMES[9] == "null"
+    assert (V.VALID, V.COORDINATE, V.RING_SHAPE, V.SELF_INTERSECTION, V.RINGS_CROSS, V.HOLE_OUTSIDE, V.NESTED_HOLES, V.NESTED_MEMBERS,
+            V.DISCONNECTED, V.NULL) == tuple(range(10))
+    # every "invalid polygon ... unspecified" line of the relation contracts points to gpk_validity
+    lines = text.splitlines()
+    at = [i for i, line in enumerate(lines) if "invalid polygon" in line and "unspecified" in line]
+    assert len(at) >= 2 and all("gpk_validity" in lines[i + 1] for i in at)
+
+
+def test_kernel_constants_are_the_ones_the_tests_mirror():
+    text = open(os.path.join(_abi.HERE, "csrc", "gpk_validity.h")).read()
+    for name, want in (("VAL_G_SMALL", V.VAL_G_SMALL), ("VAL_G_LARGE", V.VAL_G_LARGE), ("VAL_BLOCK_COORDS", V.VAL_BLOCK_COORDS),
+                       ("VAL_SEGS_PER_STRIP", V.VAL_SEGS_PER_STRIP), ("VAL_STRIPS_MAX", V.VAL_STRIPS_MAX), ("VAL_ENTRIES", V.VAL_ENTRIES)):
+        assert re.search(rf"\b{name} = {want}\b", text), name
+    assert re.search(r"VAL_G_MEAN = 32\.0", text) and V.VAL_G_MEAN == 32.0
+
+
+@pytest.fixture
+def no_device(monkeypatch):
+    """any call into the library fails the test: the checks below must happen first"""
+
+    def boom():
+        raise AssertionError("the library was opened")
+
+    monkeypatch.setattr(_abi, "lib", boom)
+
+
+def _series():
+    pts = GeoSeries(GeoArrowArray.from_points([[0.0, 0.0], [1.0, 1.0]]))
+    lines = GeoSeries(GeoArrowArray.from_linestrings([[(0.0, 0.0), (1.0, 1.0)], [(2.0, 0.0), (3.0, 1.0)]]))
+    sq = [[(0.0, 0.0), (4.0, 0.0), (4.0, 4.0), (0.0, 4.0), (0.0, 0.0)]]
+    return pts, lines, GeoSeries(GeoArrowArray.from_polygons([sq, sq, sq]))
+
+
+def test_family_errors_come_before_the_device(no_device):
+    pts, lines, polys = _series()
+    for call in (lambda: pts.is_valid(), lambda: lines.is_valid(), lambda: lines.is_valid_reason(), lambda: pts.is_valid_reason(return_where=True),
+                 lambda: polys.is_simple(), lambda: pts.is_simple()):
+        with pytest.raises(_abi.MismatchedGeometry) as e:
+            call()
+        assert e.value.code == _abi.GPK_ERR_MISMATCHED_GEOMETRY
+    assert pts._dev is None and lines._dev is None and polys._dev is None
+
+
+def test_older_surfaces_stay_as_they_are(no_device):
+    pts, lines, polys = _series()
+    for name in ("crosses", "touches", "covered_by", "covers", "disjoint"):
+        with pytest.raises(NotImplementedError, match="Point"):
+            getattr(pts, name)(polys)
+        with pytest.raises(NotImplementedError, match="LineString x LineString"):
+            getattr(lines, name)(lines)
+    for name in ("overlaps", "geom_equals", "contains_properly"):
+        with pytest.raises(NotImplementedError, match="Point"):
+            getattr(pts, name)(polys)
