@@ -49,6 +49,9 @@ LP_PRED_INTERSECTS, LP_PRED_WITHIN, LP_PRED_COVERED_BY, LP_PRED_CROSSES, LP_PRED
 PP_INTERIORS, PP_BOUNDARIES, PP_A_OUTSIDE, PP_B_OUTSIDE = 1, 2, 4, 8  # GPK_PP_*: the bits of the polygon x polygon relation mask
 (PP_PRED_INTERSECTS, PP_PRED_WITHIN, PP_PRED_CONTAINS, PP_PRED_TOUCHES, PP_PRED_OVERLAPS, PP_PRED_EQUALS,
  PP_PRED_CONTAINS_PROPERLY) = range(7)  # GPK_PP_PRED_*
+LL_INTERIORS, LL_SHARED_PIECE, LL_INT_BND, LL_BND_INT, LL_BND_BND, LL_A_OUTSIDE, LL_B_OUTSIDE = 1, 2, 4, 8, 16, 32, 64  # GPK_LL_*: the line x line mask
+(LL_PRED_INTERSECTS, LL_PRED_WITHIN, LL_PRED_CONTAINS, LL_PRED_COVERED_BY, LL_PRED_COVERS, LL_PRED_CROSSES, LL_PRED_TOUCHES, LL_PRED_OVERLAPS,
+ LL_PRED_EQUALS) = range(9)  # GPK_LL_PRED_*
 
 
 class GeopolarsHipError(RuntimeError):
@@ -185,6 +188,11 @@ _PROTOS = {
     ),
     "gpk_polygon_relation": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_polygon_relation_join": (
+        C.c_int32,
+        [_VP, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
+    ),
+    "gpk_line_relation": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_line_relation_join": (
         C.c_int32,
         [_VP, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),

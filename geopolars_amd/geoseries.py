@@ -427,6 +427,31 @@ class GeoSeries:
         """the polygon `other[i]` lies in the interior of `self[i]`: contained without touching its boundary"""
         return self._polygon_relation(other, "contains_properly", other_rows)
 
+    # ---- line x line relations (gpk_lineline.hip) ------------------------------------------------
+    def line_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """The exact relation mask (uint8) of every row's line A against its line B = other[other_rows[i]] (gpk_line_relation), under
+        the mod-2 boundary rule: bit 1 — the interiors share a point, 2 — A and B share a piece of positive length, 4 — an interior
+        point of A is a boundary point of B, 8 — a boundary point of A is an interior point of B, 16 — the boundaries share a point,
+        32 — A has a point off B, 64 — B has a point off A; 0 for a null row, a row without coordinates or one with a NaN or infinite
+        coordinate.  Both columns are LINESTRING / MULTILINESTRING.  The named methods (crosses, touches, ...) do not take two lineal
+        columns: line_predicate does."""
+        rows = line_relation_args("line_relation", self, other, other_rows)
+        out = np.empty(len(self), dtype=np.uint8)
+        if len(out):
+            _abi.check(
+                _abi.lib().gpk_line_relation(
+                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
+                )
+            )
+        return out
+
+    def line_predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
+        """a named line / line predicate (LINE_MASK_PREDICATES: intersects, disjoint, touches, crosses, overlaps, within, contains,
+        covered_by, covers, equals) of every row against its row of `other`, as bool"""
+        if name not in LINE_MASK_PREDICATES:
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown line / line predicate {name!r}: one of {sorted(LINE_MASK_PREDICATES)}")
+        return line_mask_predicate(self.line_relation(other, other_rows), name)
+
     # ---- validity and simplicity (gpk_validity.hip) ----------------------------------------------
     def _validity(self, op: str, return_where: bool):
         validity_family_arg(op, self._family(), POLYGONAL)
@@ -604,6 +629,47 @@ POLYGON_MASK_PREDICATES = {
 }
 POLYGON_MASK_PREDICATES["covered_by"] = POLYGON_MASK_PREDICATES["within"]  # closed regular sets: covered means within
 POLYGON_MASK_PREDICATES["covers"] = POLYGON_MASK_PREDICATES["contains"]
+
+
+# the line / line predicates over the line x line relation mask (include/geopolars_hip.h); mask 0 satisfies none of them
+LINE_MASK_PREDICATES = {
+    "intersects": lambda m: (m & 31) != 0,
+    "disjoint": lambda m: (m != 0) & ((m & 31) == 0),
+    "touches": lambda m: ((m & 28) != 0) & ((m & 1) == 0),
+    "crosses": lambda m: ((m & 1) != 0) & ((m & 2) == 0),
+    "overlaps": lambda m: ((m & 2) != 0) & ((m & 32) != 0) & ((m & 64) != 0),
+    "within": lambda m: ((m & 1) != 0) & ((m & 32) == 0),
+    "contains": lambda m: ((m & 1) != 0) & ((m & 64) == 0),
+    "covered_by": lambda m: ((m & 31) != 0) & ((m & 32) == 0),
+    "covers": lambda m: ((m & 31) != 0) & ((m & 64) == 0),
+    "equals": lambda m: ((m & 1) != 0) & ((m & 96) == 0),
+}
+
+
+def line_mask_predicate(mask, name: str) -> np.ndarray:
+    """a named line / line predicate from relation masks"""
+    if name not in LINE_MASK_PREDICATES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown line / line predicate {name!r}: one of {sorted(LINE_MASK_PREDICATES)}")
+    return LINE_MASK_PREDICATES[name](np.asarray(mask, dtype=np.uint8))
+
+
+def line_relation_args(op: str, a: "GeoSeries", b: "GeoSeries", rows) -> Optional[np.ndarray]:
+    """the checks of line_relation before any device call, in the C ABI's order: both families lineal, then the row map (returned as
+    uint32) with one entry per row of `a`, or equal row counts without one"""
+    fa, fb = a._family(), b._family()
+    if fa not in LINEAL or fb not in LINEAL:
+        raise _mismatch(f"{op}: LineString | MultiLineString x LineString | MultiLineString (found {_abi_name(fa)} x {_abi_name(fb)})")
+    if rows is not None:
+        try:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+        except (TypeError, ValueError, OverflowError):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+        if r.ndim != 1 or len(r) != len(a):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
+        return r
+    if len(a) != len(b):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+    return None
 
 
 # the codes of gpk_validity (include/geopolars_hip.h: GPK_VALID, GPK_INVALID_*), by value

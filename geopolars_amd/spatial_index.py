@@ -9,6 +9,8 @@
                             covers, covered_by, crosses, touches from the exact relation mask
     spatial_join_polygon_relation   the same for polygons x polygons: intersects, within, contains, covers, covered_by, touches,
                             overlaps, contains_properly, equals
+    spatial_join_line_relation      the same for lines x lines: intersects, within, contains, covers, covered_by, crosses, touches,
+                            overlaps, equals
 
 The candidate generation + exact refine (spatial_index.rs:74-143) run on the GPU through
 gpk_spatial_join; this module only marshals buffers and — for dataframe-shaped callers — assembles
@@ -26,7 +28,7 @@ import numpy as np
 from . import _abi
 from ._abi import MEM_DEVICE, MEM_HOST, PREDICATES
 from .geoarrow import DeviceGeoArray
-from .geoseries import POLYGONAL, GeoSeries, _abi_name, _mismatch, dwithin_distance_arg, relation_sides
+from .geoseries import LINEAL, POLYGONAL, GeoSeries, _abi_name, _mismatch, dwithin_distance_arg, relation_sides
 
 
 def _ptr(t):
@@ -697,6 +699,105 @@ def spatial_join_polygon_relation(lhs, rhs, options: Optional[SpatialJoinRelatio
     lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
     rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
     pairs, counts, mask = polygon_relation_pairs(lgeo, rgeo, options.predicate, options.r_index)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
+    if options.relation_col is not None:
+        matched = ri >= 0
+        m = np.zeros(len(ri), dtype=np.uint8)
+        m[matched] = mask
+        table = table.append_column(options.relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
+    return table
+
+
+# ---- line x line predicate join (gpk_line_relation_join) ---------------------------------------------------------------------
+
+# GeoPandas' predicate names (plus `equals`) -> GPK_LL_PRED_*
+LINE_RELATION_PREDICATES = {
+    "intersects": _abi.LL_PRED_INTERSECTS,
+    "within": _abi.LL_PRED_WITHIN,
+    "contains": _abi.LL_PRED_CONTAINS,
+    "covered_by": _abi.LL_PRED_COVERED_BY,
+    "covers": _abi.LL_PRED_COVERS,
+    "crosses": _abi.LL_PRED_CROSSES,
+    "touches": _abi.LL_PRED_TOUCHES,
+    "overlaps": _abi.LL_PRED_OVERLAPS,
+    "equals": _abi.LL_PRED_EQUALS,
+}
+
+
+def line_relation_predicate_arg(predicate: str, left_family: int, right_family: int) -> int:
+    """The GPK_LL_PRED_* id of a predicate name for a join of these two families, checked before any device call: a known name and
+    both sides lineal.  The relation is always read "left row <predicate> right row"."""
+    if predicate not in LINE_RELATION_PREDICATES:
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT, f"line relation join: unknown predicate {predicate!r}: one of {sorted(LINE_RELATION_PREDICATES)}"
+        )
+    if left_family not in LINEAL or right_family not in LINEAL:
+        raise _mismatch(
+            f"line relation join: LineString | MultiLineString x LineString | MultiLineString (found {_abi_name(left_family)} x {_abi_name(right_family)})"
+        )
+    return LINE_RELATION_PREDICATES[predicate]
+
+
+def line_relation_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    predicate: str = "intersects",
+    r_index: Optional[SpatialIndex] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every (l, r) of two line columns (which may be the same column: junctions, duplicates) whose exact relation satisfies
+    `predicate`: (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32, masks (H,) uint8 — what
+    left.line_relation(right) gives for the pairs).  Host-buffer variant: the pair buffer is sized like join_pairs'."""
+    pred = line_relation_predicate_arg(predicate, left._family(), right._family())
+    lib = _abi.lib()
+    n = len(left)
+    counts = np.zeros(n, dtype=np.uint32)
+    rh = r_index.handle if r_index is not None else None
+    call = lambda pairs_ptr, mask_ptr, capacity, n_pairs: lib.gpk_line_relation_join(  # noqa: E731
+        left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs_ptr, mask_ptr, capacity, n_pairs, MEM_HOST, None)
+    pairs, mask = _pairs_with_retry(n, call, want_dist=True, payload=np.uint8)
+    return pairs, counts, mask
+
+
+def line_relation_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    predicate: str,
+    out_counts,
+    out_pairs,
+    out_mask=None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_mask (cap,) uint8 torch CUDA tensors (any may
+    be None; out_pairs None = count only; without out_mask the work on a pair ends as soon as its predicate is settled) are filled in
+    place on `stream`; returns the number of pairs."""
+    pred = line_relation_predicate_arg(predicate, left.geom_type, right.geom_type)
+    n_pairs = C.c_int64(0)
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_line_relation_join(
+        left.handle, right.handle, rh, pred, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_mask), cap, C.byref(n_pairs), MEM_DEVICE, stream))
+    return int(n_pairs.value)
+
+
+def spatial_join_line_relation(lhs, rhs, options: Optional[SpatialJoinRelationArgs] = None):
+    """GeoPandas' sjoin(predicate=...) over two pyarrow Tables of lines with a `geometry` column (WKB or native GeoArrow, as
+    spatial_join takes them): every left row with every right row in the relation, shaped like spatial_join_relation's result —
+    suffixed left columns, suffixed right columns, then `relation_col` (the pair's 7-bit mask) when asked for."""
+    import pyarrow as pa
+
+    options = options or SpatialJoinRelationArgs()
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"line relation join: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    if options.predicate not in LINE_RELATION_PREDICATES:
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT, f"line relation join: unknown predicate {options.predicate!r}: one of {sorted(LINE_RELATION_PREDICATES)}"
+        )
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, mask = line_relation_pairs(lgeo, rgeo, options.predicate, options.r_index)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
     table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
     if options.relation_col is not None:

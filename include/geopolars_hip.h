@@ -596,6 +596,61 @@ int32_t gpk_polygon_relation_join(const gpk_geoarray* left, const gpk_geoarray* 
                                   uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask,
                                   int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
 
+/* ---- line x line relations (gpk_lineline.hip) ---------------------------------------------------------------------------------------
+ * How two lineal geometries lie to each other.  A, B = LINESTRING or MULTILINESTRING rows, each the closed point set of all its
+ * segments and coordinates.  Boundary (the mod-2 rule): every non-empty member of a row counts its first and its last coordinate once
+ * each; a point counted an odd number of times over the whole row is a boundary point.  A closed member (first = last) counts twice
+ * at one point and so contributes none; a member of one coordinate, or of equal coordinates, is a point of the row whose two ends
+ * coincide: it has no boundary of its own.  The interior of a row is the row minus its boundary points.  Nothing assumes that a row is
+ * simple: the mask is the set-theoretic answer for every usable row, self-crossing ones included.  The relation is a 7-bit mask: */
+#define GPK_LL_INTERIORS 1    /* an interior point of A is an interior point of B */
+#define GPK_LL_SHARED_PIECE 2 /* A and B share a piece of positive length (always together with GPK_LL_INTERIORS) */
+#define GPK_LL_INT_BND 4      /* an interior point of A is a boundary point of B */
+#define GPK_LL_BND_INT 8      /* a boundary point of A is an interior point of B */
+#define GPK_LL_BND_BND 16     /* a boundary point of A is a boundary point of B */
+#define GPK_LL_A_OUTSIDE 32   /* A has a point that is no point of B */
+#define GPK_LL_B_OUTSIDE 64   /* B has a point that is no point of A */
+/* Every named line / line predicate (DE-9IM, dimension 1 / 1) is a function of the mask alone:
+ *   intersects     mask & 31                              disjoint       mask != 0 && !(mask & 31)
+ *   touches        (mask & 28) && !(mask & 1)             crosses        (mask & 1) && !(mask & 2)
+ *   overlaps       (mask & 2) && (mask & 32) && (mask & 64)
+ *   within         (mask & 1) && !(mask & 32)             contains       (mask & 1) && !(mask & 64)
+ *   covered_by     (mask & 31) && !(mask & 32)            covers         (mask & 31) && !(mask & 64)
+ *   equals         (mask & 1) && !(mask & 96)
+ * within and covered_by differ only when A consists of point members that sit on boundary points of B.  A usable pair never has mask
+ * 0.  mask(B, A) is mask(A, B) with the bits 4 and 8, and 32 and 64, swapped.  The mask is EXACT: decided with exact orientation signs
+ * and coordinate comparisons only, no tolerance, the same at any placement of the same figures.  Rows, on either side:
+ *   row unusable           null, no coordinate, or a NaN or infinite coordinate: mask 0, and every predicate is false
+ *   empty members are ignored
+ *
+ * Row-wise: out_mask[i] = mask(a[i], b[b_rows[i]]).  `b_rows` (same space as the output) as in gpk_polygon_relation: NULL = identity
+ * (the row counts must then match), an entry >= n_geoms(b) gives mask 0.  Both sides LINESTRING | MULTILINESTRING, any other family
+ * on either side: GPK_ERR_MISMATCHED_GEOMETRY; a wrong count: GPK_ERR_INVALID_ARGUMENT; both before any device work.  Outputs are
+ * stream-ordered (host outputs: the call waits for them).  out_mask[n_geoms(a)] bytes.  Rows of many thousand coordinates run on the
+ * same 16 lanes as any other: correct and slow. */
+int32_t gpk_line_relation(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, uint8_t* out_mask, int32_t out_space,
+                          void* stream);
+#define GPK_LL_PRED_INTERSECTS 0
+#define GPK_LL_PRED_WITHIN 1
+#define GPK_LL_PRED_CONTAINS 2
+#define GPK_LL_PRED_COVERED_BY 3
+#define GPK_LL_PRED_COVERS 4
+#define GPK_LL_PRED_CROSSES 5
+#define GPK_LL_PRED_TOUCHES 6
+#define GPK_LL_PRED_OVERLAPS 7
+#define GPK_LL_PRED_EQUALS 8
+/* Line x line predicate join (GeoPandas sjoin(predicate=...) on two line tables): every (l, r) whose mask — always A = the left row,
+ * B = the right row — satisfies `predicate`.  Both sides LINESTRING | MULTILINESTRING (else GPK_ERR_MISMATCHED_GEOMETRY); an unknown
+ * predicate id: GPK_ERR_INVALID_ARGUMENT.  Unusable rows (mask 0) never match.  `left` and `right` may be the same array (a self-join,
+ * for junctions and duplicates): pair (i, i) then appears for intersects / equals / within / contains / covered_by / covers and not
+ * for touches / crosses / overlaps.  Outputs (out_counts, out_pairs, out_mask, *n_pairs), the capacity rule, count-only mode,
+ * `left_row_base`, `right_index` (NULL: a GPK_INDEX_BBOX_GRID index is built for the call and freed) and the error order are those of
+ * gpk_polygon_relation_join.  Without out_mask a pair's work ends as soon as its predicate is settled.  Synchronous.
+ * gpk_spatial_join, gpk_line_polygon_relation / _join and gpk_predicate_rowwise are unchanged. */
+int32_t gpk_line_relation_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
+                               uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask, int64_t pair_capacity,
+                               int64_t* n_pairs, int32_t out_space, void* stream);
+
 /* ---- validity and simplicity (gpk_validity.hip) -------------------------------------------------------------------------------------
  * Is a polygonal row OGC-valid — the condition under which the relation masks above are exact — and if not, why not and where.
  * `a` is a POLYGON or MULTIPOLYGON column (any other family: GPK_ERR_MISMATCHED_GEOMETRY, before any device work).  Only the non-empty
