@@ -143,6 +143,8 @@ _PROTOS = {
     "gpk_affine_transform": (C.c_int32, [_VP, C.POINTER(C.c_double), _VP, C.c_int32, _VP]),
     "gpk_affine_transform_rows": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_affine_about_origin": (C.c_int32, [_VP, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, _VP, C.c_int32, _VP]),
+    "gpk_crs_supported": (C.c_int32, [C.c_int32]),
+    "gpk_reproject": (C.c_int32, [_VP, C.c_int32, C.c_int32, _VP, C.POINTER(C.c_int64), C.c_int32, _VP]),
     "gpk_envelope": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_exterior": (C.c_int32, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.c_int32, _VP]),
     "gpk_explode": (C.c_int32, [_VP, _VP, C.c_int32, _VP, C.POINTER(_VP)]),

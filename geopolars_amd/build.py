@@ -25,6 +25,7 @@ ARCH = "gfx950"
 SOURCES = [
     "gpk_runtime.hip",
     "gpk_unary.hip",
+    "gpk_crs.hip",
     "gpk_ringstream.hip",
     "gpk_gridindex.hip",
     "gpk_bboxjoin.hip",

@@ -33,6 +33,46 @@ from .geoarrow import DeviceGeoArray, GeoArrowArray
 
 TransformOrigin = Union[str, tuple]
 
+SUPPORTED_CRS = "EPSG:4326 (OGC:CRS84), EPSG:3857, EPSG:3395, EPSG:32601-32660, EPSG:32701-32760"
+
+
+def crs_supported(epsg: int) -> bool:
+    """mirror of gpk_crs_supported (the argument checks need no library)"""
+    return epsg in (4326, 3857, 3395) or 32601 <= epsg <= 32660 or 32701 <= epsg <= 32760
+
+
+def parse_crs(crs) -> int:
+    """ "EPSG:4326" in any letter case, "OGC:CRS84" or an int -> the EPSG code; ValueError for anything outside the analytic set"""
+    code = None
+    if isinstance(crs, (int, np.integer)) and not isinstance(crs, bool):
+        code = int(crs)
+    elif isinstance(crs, str):
+        t = crs.strip().upper()
+        if t == "OGC:CRS84":
+            code = 4326
+        elif t.startswith("EPSG:") and t[5:].isdigit():
+            code = int(t[5:])
+    if code is None or not crs_supported(code):
+        raise ValueError(
+            f"reproject: CRS {crs!r} is not in the analytic set ({SUPPORTED_CRS}); arbitrary CRS strings and datum shifts are "
+            "the reference's PROJ path (to_crs, geoseries.rs:148-151)"
+        )
+    return code
+
+
+def utm_crs_of_bounds(bounds) -> str:
+    """estimate_utm_crs from an (n, 4) minx, miny, maxx, maxy array in lon/lat degrees (NaN rows — empty geometries — are ignored)"""
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 4)
+    b = b[~np.isnan(b).any(axis=1)]
+    if len(b) == 0:
+        raise ValueError("estimate_utm_crs: the column has no coordinates")
+    lon = 0.5 * (b[:, 0].min() + b[:, 2].max())
+    lat = 0.5 * (b[:, 1].min() + b[:, 3].max())
+    if not (-180.0 <= lon <= 180.0 and -90.0 <= lat <= 90.0):
+        raise ValueError("estimate_utm_crs: the column is not in lon/lat degrees")
+    zone = min(max(int(np.floor((lon + 180.0) / 6.0)) + 1, 1), 60)
+    return f"EPSG:{(32600 if lat >= 0 else 32700) + zone}"
+
 
 class GeoSeries:
     def __init__(self, array: Optional[GeoArrowArray], name: str = "geometry", device: Optional[DeviceGeoArray] = None):
@@ -250,8 +290,36 @@ class GeoSeries:
             return GeoSeries(GeoArrowArray(a.geom_type, xy, a.geom_offsets, a.part_offsets, off, a.validity, n_geoms=a.n_geoms))
         return GeoSeries(GeoArrowArray(a.geom_type, xy, off, validity=a.validity, n_geoms=a.n_geoms))
 
+    # ---- analytic reprojection (gpk_crs.hip) ----------------------------------------------------------------------------------------
+    def reproject(self, from_crs, to_crs, errors: str = "raise") -> "GeoSeries":
+        """Reproject every coordinate between the analytic systems on the WGS84 ellipsoid: EPSG:4326 (x = lon, y = lat; also
+        "OGC:CRS84"), 3857, 3395 and the UTM zones 32601-32660 / 32701-32760.  A CRS is "EPSG:nnnn" in any letter case,
+        "OGC:CRS84" or an int.  One kernel launch (gpk_reproject); offsets and validity are carried over unchanged.
+
+        A coordinate fails when it is non-finite, a geographic latitude is beyond +-90, a UTM destination is 90 degrees or
+        more from its central meridian, or the result is non-finite (a Mercator at a pole).  errors="raise": ValueError with
+        the count (the reference fails the whole call on one ProjError); errors="nan": failed coordinates come back NaN."""
+        if errors not in ("raise", "nan"):
+            raise ValueError('errors must be "raise" or "nan"')
+        src, dst = parse_crs(from_crs), parse_crs(to_crs)
+        a = self.array
+        out = np.empty_like(a.xy)
+        n_failed = C.c_int64(0)
+        _abi.check(_abi.lib().gpk_reproject(self.device().handle, src, dst, out.ctypes.data if len(out) else None, C.byref(n_failed), MEM_HOST, None))
+        if n_failed.value and errors == "raise":
+            raise ValueError(f"reproject EPSG:{src} -> EPSG:{dst}: {n_failed.value} of {len(out)} coordinates failed (errors='nan' returns them as NaN)")
+        return GeoSeries(GeoArrowArray(a.geom_type, out, a.geom_offsets, a.part_offsets, a.ring_offsets, a.validity, n_geoms=a.n_geoms))
+
+    def estimate_utm_crs(self) -> str:
+        """GeoPandas' name: the UTM zone of the centre of the column's total bounds (lon/lat degrees), as "EPSG:326zz" (centre
+        latitude >= 0) or "EPSG:327zz".  zone = clamp(floor((lon + 180) / 6) + 1, 1, 60); the Norway and Svalbard exceptions
+        of the UTM grid are NOT applied.  The bounds come from the `bounds` kernel."""
+        return utm_crs_of_bounds(self.bounds())
+
     # ---- the one operator of the reference surface that stays off this backend (DESIGN.md section 8) ---------------------
     def to_crs(self, from_crs: str, to_crs: str) -> "GeoSeries":
+        """The general PROJ entry (arbitrary CRS strings, datum shifts, grids) stays with the reference; the analytic same-datum
+        systems — WGS84 lon/lat, both Mercators, UTM — are `reproject`."""
         raise NotImplementedError("to_crs (geoseries.rs:148-151, PROJ) is not on the accelerated path: use the reference's CPU implementation")
 
     def _about_origin(self, kind: int, p0: float, p1: float, origin: TransformOrigin) -> "GeoSeries":

@@ -263,6 +263,22 @@ int32_t gpk_affine_transform_rows(const gpk_geoarray* a, const double* matrices,
 #define GPK_ORIGIN_POINT    2
 int32_t gpk_affine_about_origin(const gpk_geoarray* a, int32_t kind, double p0, double p1, int32_t origin,
                                 double ox, double oy, double* out_xy, int32_t out_space, void* stream);
+/* reproject: analytic CRS reprojection of every coordinate (the closed-form part of geoseries.rs:148-151 `to_crs`; the general
+ * PROJ path — arbitrary CRS strings, datum shifts, grids — stays with the reference).  All systems are on the WGS84
+ * ellipsoid and are named by EPSG code:
+ *   4326          geographic, x = lon, y = lat in degrees (the order proj_known_crs hands the reference)
+ *   3857          spherical Web Mercator          3395  ellipsoidal Mercator
+ *   32601-32660   UTM north, 32701-32760 UTM south (transverse Mercator, Krueger series to n^6)
+ * Every ordered pair is one kernel launch; same -> same is a copy.  A coordinate FAILS — it is written as (NaN, NaN) and
+ * counted — when an input is non-finite, a geographic latitude is beyond +-90, a transverse-Mercator destination is 90
+ * degrees or more from its central meridian, or a result is non-finite (a Mercator at a pole).  Longitudes come out in
+ * [-180, 180].  Accuracy is pinned within 12 degrees of the central meridian (1e-7 m); beyond, the series value is returned
+ * as it is.  out_xy[2*n_coords]; offsets are unchanged and shared with the input.  n_failed (host) may be NULL: then
+ * nothing is read back and, with a device output, the call does not wait for the stream.
+ * An unsupported code: GPK_ERR_INVALID_ARGUMENT, message naming it, before any device work. */
+int32_t gpk_crs_supported(int32_t epsg); /* 1 / 0; needs no device */
+int32_t gpk_reproject(const gpk_geoarray* a, int32_t src_epsg, int32_t dst_epsg, double* out_xy, int64_t* n_failed,
+                      int32_t out_space, void* stream);
 /* envelope as a geometry (geoseries.rs:28-33; geo BoundingRect -> Rect::to_polygon): one closed 5-coordinate rectangle
  * per row (minx miny, maxx miny, maxx maxy, minx maxy, minx miny) — a POLYGON column whose ring_offsets are 5 i.
  * out_xy[10*n_geoms]; out_valid[n_geoms] bytes (0 = null or empty row: its rectangle is NaN).  The envelope of a point is
