@@ -193,6 +193,11 @@ _PROTOS = {
         C.c_int32,
         [_VP, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
+    "gpk_intersection_measure": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_intersection_measure_join": (
+        C.c_int32,
+        [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
+    ),
     "gpk_line_relation": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_line_relation_join": (
         C.c_int32,

@@ -39,6 +39,7 @@ SOURCES = [
     "gpk_linref.hip",
     "gpk_linearea.hip",
     "gpk_polyrel.hip",
+    "gpk_overlay.hip",
     "gpk_lineline.hip",
     "gpk_validity.hip",
     "gpk_hull.hip",

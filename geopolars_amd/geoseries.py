@@ -495,6 +495,31 @@ class GeoSeries:
         """the polygon `other[i]` lies in the interior of `self[i]`: contained without touching its boundary"""
         return self._polygon_relation(other, "contains_properly", other_rows)
 
+    # ---- intersection area and length (gpk_overlay.hip) ------------------------------------------
+    def _intersection_measure(self, op: str, first, other: "GeoSeries", other_rows) -> np.ndarray:
+        rows = intersection_measure_args(op, first, self, other, other_rows)
+        out = np.empty(len(self), dtype=np.float64)
+        if len(out):
+            _abi.check(
+                _abi.lib().gpk_intersection_measure(
+                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
+                )
+            )
+        return out
+
+    def intersection_area(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """The area (float64) every row's polygon shares with its polygon other[other_rows[i]] (gpk_intersection_measure), without
+        building the intersection: within 1e-9 * (d_a^2 + d_b^2) of the exact area for valid rows, d = the diagonal of a row's box.
+        NaN for a null or empty row or an invalid ring on either side.  Both columns are POLYGON / MULTIPOLYGON."""
+        return self._intersection_measure("intersection_area", POLYGONAL, other, other_rows)
+
+    def intersection_length(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """The length (float64) of every row's line inside its closed polygon other[other_rows[i]] (gpk_intersection_measure): pieces
+        along a ring count, a stretch the line runs over twice counts twice; within 1e-9 * length(line) of the exact length.  NaN for a
+        null or empty row, a NaN or infinite line coordinate or an invalid ring.  self is LINESTRING / MULTILINESTRING, other POLYGON /
+        MULTIPOLYGON."""
+        return self._intersection_measure("intersection_length", LINEAL, other, other_rows)
+
     # ---- line x line relations (gpk_lineline.hip) ------------------------------------------------
     def line_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
         """The exact relation mask (uint8) of every row's line A against its line B = other[other_rows[i]] (gpk_line_relation), under
@@ -788,6 +813,52 @@ def polygon_relation_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional
     if len(a) != len(b):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
     return None
+
+
+def intersection_measure_args(op: str, first, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
+    """the checks of intersection_area / intersection_length before any device call, in the C ABI's order: `a` of the family set
+    `first` (POLYGONAL: the area, LINEAL: the length) and `b` polygonal, then the row map (returned as uint32) with one entry per row
+    of `a`, or equal row counts without one"""
+    fa, fb = a._family(), b._family()
+    if fa not in first or fb not in POLYGONAL:
+        want = "Polygon | MultiPolygon" if first is POLYGONAL else "LineString | MultiLineString"
+        swap = ": the lines come first, swap the arguments" if first is LINEAL and fa in POLYGONAL and fb in LINEAL else ""
+        raise _mismatch(f"{op}: {want} x Polygon | MultiPolygon (found {_abi_name(fa)} x {_abi_name(fb)}){swap}")
+    if rows is not None:
+        try:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+        except (TypeError, ValueError, OverflowError):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+        if r.ndim != 1 or len(r) != len(a):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
+        return r
+    if len(a) != len(b):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+    return None
+
+
+def intersection_min_measure_arg(min_measure) -> float:
+    """the `min_measure` of an intersection measure join as a float; anything but a finite number >= 0 is refused here, before any
+    device call"""
+    try:
+        m = float(min_measure)
+    except (TypeError, ValueError):
+        m = float("nan")
+    if not (m >= 0.0) or m == float("inf"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"intersection measure join: min_measure must be a finite number >= 0, got {min_measure!r}")
+    return m
+
+
+def intersection_families_arg(op: str, left_family: int, right_family: int) -> None:
+    """the family check of the intersection measure join, refused as the C ABI would: polygons or lines on the left, polygons on the
+    right"""
+    if (left_family in POLYGONAL or left_family in LINEAL) and right_family in POLYGONAL:
+        return
+    swap = ": the lines come first, swap the sides" if left_family in POLYGONAL and right_family in LINEAL else ""
+    raise _mismatch(
+        f"{op}: Polygon | MultiPolygon (area) or LineString | MultiLineString (length) x Polygon | MultiPolygon "
+        f"(found {_abi_name(left_family)} x {_abi_name(right_family)}){swap}"
+    )
 
 
 def relation_sides(op: str, a: int, b: int) -> bool:

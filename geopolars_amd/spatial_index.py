@@ -11,6 +11,8 @@
                             overlaps, contains_properly, equals
     spatial_join_line_relation      the same for lines x lines: intersects, within, contains, covers, covered_by, crosses, touches,
                             overlaps, equals
+    spatial_join_intersection       polygons x polygons or lines x polygons (not in the reference): every pair that shares more than
+                            a threshold of area / length, with the shared amount as an f64 `measure` column
 
 The candidate generation + exact refine (spatial_index.rs:74-143) run on the GPU through
 gpk_spatial_join; this module only marshals buffers and — for dataframe-shaped callers — assembles
@@ -28,7 +30,17 @@ import numpy as np
 from . import _abi
 from ._abi import MEM_DEVICE, MEM_HOST, PREDICATES
 from .geoarrow import DeviceGeoArray
-from .geoseries import LINEAL, POLYGONAL, GeoSeries, _abi_name, _mismatch, dwithin_distance_arg, relation_sides
+from .geoseries import (
+    LINEAL,
+    POLYGONAL,
+    GeoSeries,
+    _abi_name,
+    _mismatch,
+    dwithin_distance_arg,
+    intersection_families_arg,
+    intersection_min_measure_arg,
+    relation_sides,
+)
 
 
 def _ptr(t):
@@ -707,6 +719,86 @@ def spatial_join_polygon_relation(lhs, rhs, options: Optional[SpatialJoinRelatio
         m[matched] = mask
         table = table.append_column(options.relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
     return table
+
+
+# ---- intersection measure join (gpk_intersection_measure_join) --------------------------------------------------------------------
+
+
+@dataclass
+class SpatialJoinIntersectionArgs:
+    """Options of spatial_join_intersection (an overlay's pair list with its weights: areal interpolation, IoU, length per zone)."""
+
+    min_measure: float = 0.0  # finite and >= 0; pairs that share MORE than this are joined (at 0 a touching pair may appear at rounding level)
+    join_type: str = "inner"  # "inner" | "left" (unmatched left rows once, with nulls on the right)
+    measure_col: str = "measure"  # name of the float64 column with each pair's shared area / length (null for unmatched left rows)
+    l_suffix: Optional[str] = "_left"
+    r_suffix: Optional[str] = "_right"
+    r_index: Optional[SpatialIndex] = None
+    l_geom_type: int = -1  # as in SpatialJoinArgs
+    r_geom_type: int = -1
+
+
+def intersection_measure_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    min_measure: float = 0.0,
+    r_index: Optional[SpatialIndex] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every (l, r) of a polygon column (the shared area) or a line column (the length inside) against a polygon column that share more
+    than `min_measure`: (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32, measures (H,) float64 — bit for bit what
+    left.intersection_area(right) / left.intersection_length(right) gives for the pairs).  Host-buffer variant: the pair buffer is
+    sized like join_pairs'."""
+    m = intersection_min_measure_arg(min_measure)
+    intersection_families_arg("intersection measure join", left._family(), right._family())
+    lib = _abi.lib()
+    n = len(left)
+    counts = np.zeros(n, dtype=np.uint32)
+    rh = r_index.handle if r_index is not None else None
+    call = lambda pairs_ptr, measure_ptr, capacity, n_pairs: lib.gpk_intersection_measure_join(  # noqa: E731
+        left.device().handle, right.device().handle, rh, m, left_row_base, counts.ctypes.data, pairs_ptr, measure_ptr, capacity, n_pairs, MEM_HOST, None)
+    pairs, measure = _pairs_with_retry(n, call, want_dist=True)
+    return pairs, counts, measure
+
+
+def intersection_measure_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    min_measure: float,
+    out_counts,
+    out_pairs,
+    out_measure=None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_measure (cap,) float64 torch CUDA tensors (any
+    may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
+    m = intersection_min_measure_arg(min_measure)
+    intersection_families_arg("intersection measure join", left.geom_type, right.geom_type)
+    n_pairs = C.c_int64(0)
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_intersection_measure_join(
+        left.handle, right.handle, rh, m, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_measure), cap, C.byref(n_pairs), MEM_DEVICE, stream))
+    return int(n_pairs.value)
+
+
+def spatial_join_intersection(lhs, rhs, options: Optional[SpatialJoinIntersectionArgs] = None):
+    """The pair list of an overlay with its weights, over two pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as
+    spatial_join takes them): polygons or lines on the left, polygons on the right; every left row with every right row it shares more
+    than `options.min_measure` of area (polygons) or length (lines) with, shaped like spatial_join's result — suffixed left columns,
+    suffixed right columns, then the float64 `measure_col`."""
+    options = options or SpatialJoinIntersectionArgs()
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"intersection join: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    if not isinstance(options.measure_col, str) or not options.measure_col:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"intersection join: measure_col must be a column name, got {options.measure_col!r}")
+    m = intersection_min_measure_arg(options.min_measure)
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, measure = intersection_measure_pairs(lgeo, rgeo, m, options.r_index)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.measure_col, measure)
 
 
 # ---- line x line predicate join (gpk_line_relation_join) ---------------------------------------------------------------------

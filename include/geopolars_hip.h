@@ -612,6 +612,46 @@ int32_t gpk_polygon_relation_join(const gpk_geoarray* left, const gpk_geoarray* 
                                   uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask,
                                   int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
 
+/* ---- intersection area and length (gpk_overlay.hip) ---------------------------------------------------------------------------------
+ * How MUCH two geometries share, without building the intersection geometry (csrc/gpk_overlay.h has the formulation):
+ *   a polygonal x b polygonal     out = area(a ∩ b)        (areal interpolation, IoU, overlap share)
+ *   a lineal    x b polygonal     out = length(a ∩ b)      (length of road or river inside a zone; b is closed: a piece that runs
+ *                                                           along a ring counts; a stretch the line runs over twice counts twice)
+ * Every other combination: GPK_ERR_MISMATCHED_GEOMETRY; for polygonal x lineal the message says to swap the arguments.  Each measure
+ * is a sum of independent (edge, edge) terms around a pair-local origin.  Shared boundaries (neighbours, a polygon that fills a hole,
+ * equal polygons) are decided as for one fixed infinitesimal translation of b by (+eps1, +eps2), eps1 << eps2 — the tie rule: points
+ * of a lie below a collinear edge of b and in the x-range (min, max] of an edge of b, points of b above and in [min, max).  Area is
+ * continuous under translation, so the limit is the exact area; the length adds back the pieces along ring edges that the translation
+ * left outside.  Tolerance, for OGC-valid operands (d = the diagonal of a row's box):
+ *   area      |out - exact| <= 1e-9 * (d_a^2 + d_b^2)
+ *   length    |out - exact| <= 1e-9 * length(a)
+ * at any placement of the figures, georeferenced magnitudes included.  The scale is that of the terms being summed, not of the result,
+ * which may be an arbitrarily thin sliver.  Results are >= 0; rows whose boxes are strictly apart give exactly 0.0.  Rows:
+ *   row unusable           null, no non-empty member (no coordinate), on either side: NaN
+ *   invalid ring           a non-empty ring that fails the ring rule of gpk_polygon_relation: NaN
+ *   a line with a NaN or infinite coordinate: NaN
+ *   empty members of a multi-geometry are ignored
+ *   invalid polygon        (self-crossing rings, overlapping parts) the value is unspecified; the call terminates normally
+ *                          gpk_validity tells which rows are valid, and why the others are not.
+ *
+ * Row-wise: out[i] = measure(a[i], b[b_rows[i]]).  `b_rows` (same space as the output) as in gpk_polygon_relation: NULL = identity
+ * (the row counts must then match), an entry >= n_geoms(b) gives NaN.  A wrong count: GPK_ERR_INVALID_ARGUMENT; family and count are
+ * checked before any device work.  Outputs are stream-ordered (host outputs: the call waits for them).  out[n_geoms(a)] doubles.  Rows
+ * of many thousand coordinates run on the same 16 lanes as any other: correct and slow. */
+int32_t gpk_intersection_measure(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double* out, int32_t out_space,
+                                 void* stream);
+/* Intersection measure join: every (l, r) with measure(left[l], right[r]) > min_measure — strict, on doubles, NaN never hits — and the
+ * measure of each pair in out_measure (doubles, pair order; NULL: not wanted).  The families are those of the row-wise call with a =
+ * left, b = right.  `min_measure` must be finite and >= 0: anything else is GPK_ERR_INVALID_ARGUMENT before any device work.  At
+ * min_measure == 0 a pair that only touches may appear with a value at rounding level: ask for a threshold above the tolerance of
+ * the data when touching pairs must stay out.  The measures are bit for bit what the row-wise call gives for the pair.  `left` and
+ * `right` may be the same array: pair (i, i) then carries area(i).  Outputs (out_counts, out_pairs, *n_pairs), the capacity rule,
+ * count-only mode, `left_row_base`, `right_index` (NULL: a GPK_INDEX_BBOX_GRID index is built for the call and freed) and the error
+ * order are those of gpk_polygon_relation_join.  Synchronous. */
+int32_t gpk_intersection_measure_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, double min_measure,
+                                      uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_measure,
+                                      int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
+
 /* ---- line x line relations (gpk_lineline.hip) ---------------------------------------------------------------------------------------
  * How two lineal geometries lie to each other.  A, B = LINESTRING or MULTILINESTRING rows, each the closed point set of all its
  * segments and coordinates.  Boundary (the mod-2 rule): every non-empty member of a row counts its first and its last coordinate once

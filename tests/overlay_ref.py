@@ -1,0 +1,433 @@
+"""Exact reference of the intersection measures (gpk_intersection_measure, csrc/gpk_overlay.h) and their fixture.
+
+Neither measure is computed the way the kernel computes it (signed inside fractions of edge pairs under a tie translation):
+
+area(A ∩ B): the slab decomposition of tests/polyrel_ref.area_samples.  S = the x coordinates of all vertices and of all exact edge x
+edge meets of A with B; inside an open slab between two consecutive values of S the edges that span it are ordered from bottom to top
+and cut it into trapezoids.  On the middle line the edges are evaluated exactly (Fractions) and sorted; the stretch between two
+consecutive edges lies in A when the number of A's edges below it is odd (even-odd over all rings of all members), the same for B, and
+a trapezoid inside both adds (x1 - x0) * (y_hi(xm) - y_lo(xm)), which is its exact area.
+
+length(L ∩ P): every segment is cut at its exact meets with the ring edges (relation_ref._cuts), the rational midpoint of every piece
+is classified with exact_predicates._rational_pos against every member (inside or on a ring: P is closed), and the pieces that count
+are summed with the segment's length taken in mpmath at 40 digits.
+
+All fixtures live on small integer lattices.  Rows are what tests/exact_ref.column takes."""
+from __future__ import annotations
+
+import io
+import os
+from fractions import Fraction
+from functools import lru_cache
+
+import numpy as np
+
+from geopolars_amd.geoarrow import GeoArrowArray
+from tests import exact_predicates as E
+from tests import exact_ref as X
+from tests import polyrel_ref as P
+from tests import relation_ref as R
+
+LS, MLS, PG, MPG = R.LS, R.MLS, R.PG, R.MPG
+NAMES = R.NAMES
+AREA_FAMILIES = [(PG, PG), (PG, MPG), (MPG, PG), (MPG, MPG)]
+LENGTH_FAMILIES = [(LS, PG), (LS, MPG), (MLS, PG), (MLS, MPG)]
+REL_TOL = 1e-9  # the contract of the f64 measures: |got - exact| <= REL_TOL * scale, scale = d_A^2 + d_B^2 or length(L)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "overlay_lattice.npz")
+TRANSLATION = (500000.0, 4649776.0)  # a georeferenced placement at which the lattice stays exactly representable
+sq = R.sq
+
+
+# ---- the two exact measures ------------------------------------------------------------------------------------------------------------
+
+
+def _box(polys):
+    a = np.concatenate([p[0] for p in polys])
+    return a.min(axis=0), a.max(axis=0)
+
+
+def area_of_polys(pa, pb) -> Fraction:
+    """the exact area shared by two lists of integer polygons"""
+    (alo, ahi), (blo, bhi) = _box(pa), _box(pb)
+    if (ahi < blo).any() or (bhi < alo).any():
+        return Fraction(0)
+    ea, eb = E._edges([r for p in pa for r in p]), E._edges([r for p in pb for r in p])
+    xs = {Fraction(p[0]) for e in ea + eb for p in e}
+    for p, q in ea:
+        lo, hi = (min(p[0], q[0]), min(p[1], q[1])), (max(p[0], q[0]), max(p[1], q[1]))
+        for a, b in eb:
+            if max(a[0], b[0]) < lo[0] or min(a[0], b[0]) > hi[0] or max(a[1], b[1]) < lo[1] or min(a[1], b[1]) > hi[1]:
+                continue
+            x = P._meet(p, q, a, b)
+            if x is not None and x is not True:
+                xs.add(x)
+    xs = sorted(xs)
+    total = Fraction(0)
+    for x0, x1 in zip(xs, xs[1:]):
+        xm = (x0 + x1) / 2
+        ys = []
+        for which, edges in ((0, ea), (1, eb)):
+            for p, q in edges:
+                if min(p[0], q[0]) < xm < max(p[0], q[0]):
+                    ys.append((p[1] + (q[1] - p[1]) * (xm - p[0]) / (q[0] - p[0]), which))
+        ys.sort()
+        below = [0, 0]
+        for k, (y, which) in enumerate(ys[:-1]):
+            below[which] ^= 1
+            if below[0] and below[1]:
+                total += (x1 - x0) * (ys[k + 1][0] - y)
+    return total
+
+
+def exact_area(ka, row_a, kb, row_b, a_valid=True, b_valid=True):
+    """the exact area of one pair of rows as a Fraction; None (the kernel's NaN) for an unusable row on either side"""
+    pa, pb = P.usable(ka, row_a, a_valid), P.usable(kb, row_b, b_valid)
+    if pa is None or pb is None:
+        return None
+    return area_of_polys(pa, pb)
+
+
+def _line_seqs(kl, row, valid=True):
+    """the integer sequences of a usable line row, else None"""
+    if not valid or row is None:
+        return None
+    seqs = [s for s in R.line_seqs(kl, row) if len(s)]
+    if not seqs or any(not np.isfinite(np.asarray(s, dtype=np.float64)).all() for s in seqs):
+        return None
+    return [R._int_ring(s) for s in seqs]
+
+
+def exact_length(kl, row_l, kp, row_p, l_valid=True, p_valid=True):
+    """the length of the line inside the closed polygonal row, as an mpmath number; None for an unusable row"""
+    import mpmath as mp
+
+    seqs, polys = _line_seqs(kl, row_l, l_valid), P.usable(kp, row_p, p_valid)
+    if seqs is None or polys is None:
+        return None
+    edges = E._edges([r for p in polys for r in p])
+    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
+    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
+    with mp.workdps(40):
+        total = mp.mpf(0)
+        for s in seqs:
+            c = [(int(x), int(y)) for x, y in s]
+            for p, q in zip(c, c[1:]):
+                if p == q:
+                    continue
+                ts = R._cuts(p, q, edges, elo, ehi)
+                mids = [(p[0] + (t0 + t1) / 2 * (q[0] - p[0]), p[1] + (t0 + t1) / 2 * (q[1] - p[1])) for t0, t1 in zip(ts, ts[1:])]
+                pos = R._positions(mids, polys)
+                share = sum((t1 - t0 for (t0, t1), where in zip(zip(ts, ts[1:]), pos) if where != R.EXTERIOR), Fraction(0))
+                if share:
+                    total += mp.sqrt((q[0] - p[0]) ** 2 + (q[1] - p[1]) ** 2) * share.numerator / share.denominator
+        return total
+
+
+def line_length(kl, row) -> float:
+    return float(sum(np.hypot(*(np.diff(np.asarray(s, dtype=np.float64).reshape(-1, 2), axis=0).T)).sum() for s in R.line_seqs(kl, row) if len(s)))
+
+
+def diag2(kind, row) -> float:
+    """the squared diagonal of the box of a polygonal row's shells"""
+    lo, hi = _box([[np.asarray(r, dtype=np.float64).reshape(-1, 2) for r in p] for p in R.row_polys(kind, row)])
+    return float(((hi - lo) ** 2).sum())
+
+
+# ---- hand cases ----------------------------------------------------------------------------------------------------------------------
+
+S10, DONUT = P.S10, P.DONUT
+# (name, A, B, area): A and B as lists of polygons; a one-member list is a POLYGON row as well
+AREA_CASES = [
+    ("neighbours sharing a whole vertical edge", [[S10]], [[sq(10, 0, 20, 10)]], 0),
+    ("neighbours sharing a whole horizontal edge", [[S10]], [[sq(0, 10, 10, 20)]], 0),
+    ("neighbours sharing part of an edge", [[S10]], [[sq(10, 2, 20, 8)]], 0),
+    ("B inside A, sharing a boundary piece on the same side", [[S10]], [[sq(0, 2, 5, 5)]], 15),
+    ("B inside A, sharing a whole vertical edge on the same side", [[S10]], [[sq(5, 0, 10, 10)]], 50),
+    ("equal polygons stored in opposite orders", [[S10]], [[sq(0, 0, 10, 10, cw=True)]], 100),
+    ("equal polygons, rotated start", [[S10]], [[[(10, 0), (10, 10), (0, 10), (0, 0), (10, 0)]]], 100),
+    ("equal donuts, hole rotated and reversed", [DONUT], [[sq(0, 0, 12, 12, cw=True), [(8, 8), (8, 4), (4, 4), (4, 8), (8, 8)]]], 128),
+    ("A fills B's hole exactly", [[sq(4, 4, 8, 8)]], [DONUT], 0),
+    ("B fills A's hole exactly", [DONUT], [[sq(4, 4, 8, 8, cw=True)]], 0),
+    ("hole straddled", [DONUT], [[sq(3, 3, 9, 9)]], 20),
+    ("two parts against one polygon", [[sq(1, 1, 3, 3)], [sq(20, 20, 23, 23)]], [[sq(2, 2, 22, 22)]], 5),
+    ("neighbours sharing one vertex", [[S10]], [[sq(10, 10, 20, 20)]], 0),
+    ("parts meeting in one point, complementary sectors", P.FAN_A, P.FAN_B, 0),
+    ("proper overlap", [[S10]], [[sq(5, 5, 15, 15)]], 25),
+    ("overlap, rings meet only at vertices", [[S10]], [[[(0, 0), (10, 10), (15, -5), (0, 0)]]], 50),
+    ("B strictly inside a hole of A", [DONUT], [[sq(5, 5, 7, 7)]], 0),
+    ("B strictly inside A", [[S10]], [[sq(2, 2, 5, 5)]], 9),
+    ("the filled shell against the donut", [[sq(0, 0, 12, 12)]], [DONUT], 128),
+    ("an A vertex on a B edge, from outside", [[[(10, 5), (15, 2), (15, 8), (10, 5)]]], [[S10]], 0),
+    ("an A vertex on a B edge, from inside", [[[(5, 10), (2, 5), (8, 5), (5, 10)]]], [[S10]], 15),
+    ("repeated coordinates", [[[(0, 0), (0, 0), (10, 0), (10, 10), (10, 10), (10, 10), (0, 10), (0, 0)]]], [[sq(5, 5, 15, 15)]], 25),
+    ("A1 equals B1, A2 fills B2's hole", [[sq(0, 0, 4, 4)], [sq(14, 4, 18, 8)]], P.B_TWO, 16),
+    ("pinched hole of B: A fills the hole", [[[(6, 0), (9, 4), (3, 4), (6, 0)]]], [P.PINCHED], 0),
+    ("pinched hole of B: A in the interior, at the pinch", [[[(6, 0), (2, 1), (1, 3), (6, 0)]]], [P.PINCHED], Fraction(7, 2)),  # the whole triangle: |(-4)(3) - (-5)(1)| / 2
+    ("far apart", [[S10]], [[sq(40, 40, 50, 50)]], 0),
+]
+CW10 = [sq(0, 0, 10, 10, cw=True)]  # a shell stored clockwise
+# (name, line as a list of sequences, polygonal row as a list of polygons, length)
+LENGTH_CASES = [
+    ("crossing the shell", [[(-2, 2), (2, 2)]], [DONUT], 2.0),
+    ("along a shell edge, rightward", [[(2, 0), (9, 0)]], [DONUT], 7.0),
+    ("along a shell edge, leftward", [[(9, 0), (2, 0)]], [DONUT], 7.0),
+    ("along the top shell edge", [[(2, 12), (9, 12)]], [DONUT], 7.0),
+    ("along the top shell edge, reversed", [[(9, 12), (2, 12)]], [DONUT], 7.0),
+    ("along the left shell edge, upward", [[(0, 2), (0, 9)]], [DONUT], 7.0),
+    ("along the left shell edge, downward", [[(0, 9), (0, 2)]], [DONUT], 7.0),
+    ("along the right shell edge", [[(12, 2), (12, 9)]], [DONUT], 7.0),
+    ("along a hole edge, bottom", [[(5, 4), (7, 4)]], [DONUT], 2.0),
+    ("along a hole edge, bottom, reversed", [[(7, 4), (5, 4)]], [DONUT], 2.0),
+    ("along a hole edge, top", [[(5, 8), (7, 8)]], [DONUT], 2.0),
+    ("along a hole edge, left", [[(4, 5), (4, 7)]], [DONUT], 2.0),
+    ("along a hole edge, right, downward", [[(8, 7), (8, 5)]], [DONUT], 2.0),
+    ("across the hole", [[(2, 6), (10, 6)]], [DONUT], 4.0),
+    ("inside the hole", [[(5, 5), (7, 6)]], [DONUT], 0.0),
+    ("ending on the boundary from outside", [[(-3, 5), (0, 5)]], [DONUT], 0.0),
+    ("ending on the boundary from inside", [[(2, 2), (2, 0)]], [DONUT], 2.0),
+    ("along the shell and round a corner", [[(3, 0), (12, 0), (12, 7)]], [DONUT], 16.0),
+    ("the same stretch twice counts twice", [[(2, 0), (9, 0), (2, 0)]], [DONUT], 14.0),
+    ("over an edge and beyond both ends", [[(-3, 0), (15, 0)]], [DONUT], 12.0),
+    ("a diagonal through a vertex", [[(-5, -5), (5, 5)]], [[S10]], 50.0**0.5),
+    ("repeated coordinates", [[(2, 2), (2, 2), (3, 2), (3, 2)]], [DONUT], 1.0),
+    ("parts touching at a vertex, crossed through it", [[(7, 5), (13, 5)]], R.PARTS, 6.0),
+    ("parts touching at a vertex, tangent there", [[(10, 2), (10, 8)]], R.PARTS, 6.0),
+    ("parts: along the edge over the other part's vertex", [[(2, 10), (8, 10)]], R.PARTS, 6.0),
+    ("a clockwise shell: along its bottom edge", [[(2, 0), (9, 0)]], [CW10], 7.0),
+    ("a clockwise shell: along its left edge", [[(0, 9), (0, 2)]], [CW10], 7.0),
+    ("a clockwise shell: crossing", [[(-2, 2), (12, 2)]], [CW10], 10.0),
+    ("two members, one inside, one outside", [[(1, 1), (3, 1)], [(20, 20), (21, 25)]], [DONUT], 2.0),
+    ("outside", [[(20, 20), (30, 25), (20, 30)]], [DONUT], 0.0),
+]
+
+
+def _stride_polygons(rng):
+    """rows that make the lanes' strides wrap: rings of 5 and of 33 edges, and a shell with a hole of 40 coordinates"""
+    five = [R.star(0, 0, 20, 6, rng)]
+    many = [R.star(0, 0, 30, 34, rng)]
+    holed = [sq(-32, -32, 32, 32), R.star(0, 0, 24, 40, rng, cw=True)]
+    for p in (five, many, holed):
+        assert R.polygon_valid(PG, p), p
+    return [five, many, holed]
+
+
+def _as_line(kl, seqs):
+    if kl == LS:
+        assert len(seqs) == 1
+        return seqs[0]
+    return [[]] + [list(s) for s in seqs]
+
+
+# ---- the columns of the fixture --------------------------------------------------------------------------------------------------------
+
+
+@lru_cache(maxsize=None)
+def area_rows(ka, kb, n_random=200):
+    """(rows of A, rows of B): the hand cases the two kinds can hold, the stride rows, then lattice star polygons against partners built
+    to coincide with them in many ways (the generator of polyrel_ref.random_columns)"""
+    rng = np.random.default_rng(4000 + 10 * ka + kb)
+    sel = [c for c in AREA_CASES if (ka == MPG or len(c[1]) == 1) and (kb == MPG or len(c[2]) == 1)]
+    A = [P.as_row(ka, c[1]) for c in sel]
+    B = [P.as_row(kb, c[2]) for c in sel]
+    stride = _stride_polygons(rng)
+    for k, p in enumerate(stride):
+        for partner in (P._moved(stride[(k + 1) % 3], 7, -5), P._rewritten(p, rng), [sq(-9, -40, 9, 40)]):
+            A.append(P.as_row(ka, [p]))
+            B.append(P.as_row(kb, [partner]))
+    for i in range(n_random):
+        Rad = int(rng.integers(10, 13))  # (the whole row stays within about 64 lattice units)
+        a = R._random_polygon(0, 0, Rad, int(rng.choice([4, 5, 7, 9])), int(i % 3 == 0), rng)
+        b = P._partner(a, Rad, i % 8, rng)
+        ra, rb = [a], [b]
+        extra = R._random_polygon(5 * Rad, 0, 5, int(rng.integers(4, 8)), 0, rng)
+        if ka == MPG and i % 2:
+            ra.append(extra)
+        if kb == MPG and i % 4 >= 2:
+            rb.append(P._rewritten(extra, rng) if i % 8 >= 4 else P._moved(extra, 3, 2))
+        for kind, row in ((ka, ra), (kb, rb)):
+            if kind == MPG and i % 3 == 1:
+                row.insert(int(rng.integers(0, len(row) + 1)), [])
+        A.append(a if ka == PG else ra)
+        B.append(b if kb == PG else rb)
+    return A, B
+
+
+@lru_cache(maxsize=None)
+def length_rows(kl, kp, n_random=200):
+    """(line rows, polygon rows): the hand cases, lines over the stride rows, then lattice lines against lattice star polygons (the
+    generator of relation_ref.random_columns)"""
+    rng = np.random.default_rng(5000 + 10 * kl + kp)
+    sel = [c for c in LENGTH_CASES if (kl == MLS or len(c[1]) == 1) and (kp == MPG or len(c[2]) == 1)]
+    lines = [_as_line(kl, c[1]) for c in sel]
+    polys = [P.as_row(kp, c[2]) for c in sel]
+    for p in _stride_polygons(rng):
+        shell = p[0]
+        for seq in ([(-40, -3), (40, 5)], [shell[1], shell[2], shell[3], (0, 0)], [(0, -40), (0, 40), (3, -40)]):
+            lines.append(_as_line(kl, [seq]))
+            polys.append(P.as_row(kp, [p]))
+    for i in range(n_random):
+        n = int(rng.choice([4, 5, 8, 17, 33]))
+        Rad = max(int(rng.integers(7, 16)), n // 2 + 4)
+        holes = int(rng.integers(0, 3)) if n >= 17 else 0
+        members = [R._random_polygon(0, 0, Rad, n, holes, rng)]
+        if kp == MPG:
+            if i % 2:
+                members.append(R._random_polygon(2 * Rad + 6, 0, 5, int(rng.integers(4, 8)), 0, rng))
+            if i % 3 == 0:
+                members.insert(int(rng.integers(0, len(members) + 1)), [])
+        style = i % 8
+        n_l = int(rng.choice([2, 2, 3, 5, 9, 17])) if style not in (2, 6, 7) else int(rng.integers(2, 4))
+        seq = R._random_seq(members, 0, 0, Rad, n_l, style, rng)
+        if kl == LS:
+            lines.append(seq)
+        else:
+            row = [seq]
+            if i % 2 or style == 2:
+                row.append(R._random_seq(members, 0, 0, Rad, int(rng.integers(1, 6)), 3 if style == 2 else int(rng.integers(0, 8)), rng))
+            if i % 4 == 0:
+                row.insert(int(rng.integers(0, len(row) + 1)), [])
+            lines.append(row)
+        polys.append(members[0] if kp == PG else members)
+    return lines, polys
+
+
+@lru_cache(maxsize=None)
+def join_rows(n=200):
+    """(left polygons, right polygons, lines): n small POLYGON rows a side and n LINESTRING rows over a 260 x 260 lattice; the right
+    column repeats some left rows rewritten and holds a block of square tiles that the left column holds too (shared edges and corners)"""
+    rng = np.random.default_rng(611)
+    tiles = [[sq(270 + 10 * i, 10 * j, 280 + 10 * i, 10 + 10 * j)] for i in range(4) for j in range(4)]
+
+    def column(extra):
+        rows = []
+        for j in range(n - len(tiles) - len(extra)):
+            cx, cy = int(rng.integers(20, 240)), int(rng.integers(20, 240))
+            rows.append(R._random_polygon(cx, cy, int(rng.integers(5, 22)), int(rng.choice([4, 5, 9])), int(j % 7 == 0), rng))
+        return rows + tiles + extra
+
+    left = column([])
+    right = column([P._rewritten(left[i], rng) for i in range(30, 40)])
+    lines = []
+    for j in range(n):
+        x, y = int(rng.integers(0, 260)), int(rng.integers(0, 260))
+        seq = [(x, y)]
+        for _ in range(int(rng.integers(1, 6))):
+            x, y = x + int(rng.integers(-25, 26)), y + int(rng.integers(-25, 26))
+            seq.append((x, y))
+        lines.append(seq)
+    for k in range(4):  # along tile edges
+        lines[k] = [(270, 10 * k), (310, 10 * k)]
+    return left, right, lines
+
+
+def _boxes_meet(lo_a, hi_a, lo_b, hi_b):
+    return not ((hi_a < lo_b).any() or (hi_b < lo_a).any())
+
+
+def join_table(kind_l, rows_l, rows_r, measure):
+    """(l, r, exact) of every pair whose boxes meet (every other pair shares exactly nothing)"""
+    def box(kind, row):
+        if kind == PG:
+            a = np.asarray(row[0], dtype=np.int64)
+        else:
+            a = np.asarray(row, dtype=np.int64)
+        return a.min(axis=0), a.max(axis=0)
+
+    bl, br = [box(kind_l, r) for r in rows_l], [box(PG, r) for r in rows_r]
+    out = []
+    for i, (lo, hi) in enumerate(bl):
+        for j, (lo2, hi2) in enumerate(br):
+            if _boxes_meet(lo, hi, lo2, hi2):
+                out.append((i, j, float(measure(kind_l, rows_l[i], PG, rows_r[j]))))
+    return np.array(out, dtype=np.float64).reshape(-1, 3)
+
+
+# ---- the fixture file --------------------------------------------------------------------------------------------------------------------
+
+
+def _pack(prefix, col: GeoArrowArray, out):
+    out[prefix + "xy"] = col.xy
+    for name in ("geom_offsets", "part_offsets", "ring_offsets"):
+        v = getattr(col, name)
+        out[prefix + name] = np.zeros(0, dtype=np.int32) if v is None else v
+
+
+def unpack(z, prefix, kind, offset=(0.0, 0.0)) -> GeoArrowArray:
+    """a column of the fixture, translated by `offset`"""
+    off = {name: (z[prefix + name] if len(z[prefix + name]) else None) for name in ("geom_offsets", "part_offsets", "ring_offsets")}
+    return GeoArrowArray(kind, z[prefix + "xy"] + np.asarray(offset, dtype=np.float64), **off)
+
+
+def row_parts(col: GeoArrowArray, i: int):
+    """row i of a column as a list of parts, each a list of coordinate arrays (a line row: one part holding its sequences)"""
+    g, p, r, xy = col.geom_offsets, col.part_offsets, col.ring_offsets, col.xy
+    if col.geom_type == LS:
+        return [[xy[g[i]:g[i + 1]]]]
+    rings = lambda r0, r1: [xy[r[k]:r[k + 1]] for k in range(r0, r1)]  # noqa: E731
+    if col.geom_type in (MLS, PG):
+        return [rings(g[i], g[i + 1])]
+    return [rings(p[k], p[k + 1]) for k in range(g[i], g[i + 1])]
+
+
+def driver_records(what: int, a: GeoArrowArray, b: GeoArrowArray) -> bytes:
+    """the rows of two columns, pair by pair, as input records of tests/overlay_host_driver.cpp"""
+    buf = io.BytesIO()
+    for i in range(a.n_geoms):
+        buf.write(np.int32(what).tobytes())
+        for col in (a, b):
+            parts = row_parts(col, i)
+            buf.write(np.int32(len(parts)).tobytes())
+            for rings in parts:
+                buf.write(np.int32(len(rings)).tobytes())
+                for c in rings:
+                    buf.write(np.int32(len(c)).tobytes())
+                    buf.write(np.ascontiguousarray(c, dtype=np.float64).tobytes())
+    return buf.getvalue()
+
+
+def build_arrays():
+    """every array of tests/golden/overlay_lattice.npz"""
+    out = {}
+    for ka, kb in AREA_FAMILIES:
+        A, B = area_rows(ka, kb)
+        key = f"area_{NAMES[ka]}_{NAMES[kb]}_"
+        _pack(key + "a_", X.column(ka, A), out)
+        _pack(key + "b_", X.column(kb, B), out)
+        out[key + "exact"] = np.array([float(exact_area(ka, a, kb, b)) for a, b in zip(A, B)])
+        out[key + "scale"] = np.array([diag2(ka, a) + diag2(kb, b) for a, b in zip(A, B)])
+    for kl, kp in LENGTH_FAMILIES:
+        L, Q = length_rows(kl, kp)
+        key = f"length_{NAMES[kl]}_{NAMES[kp]}_"
+        _pack(key + "a_", X.column(kl, L), out)
+        _pack(key + "b_", X.column(kp, Q), out)
+        out[key + "exact"] = np.array([float(exact_length(kl, a, kp, b)) for a, b in zip(L, Q)])
+        out[key + "scale"] = np.array([line_length(kl, a) for a in L])
+    left, right, lines = join_rows()
+    _pack("join_left_", X.column(PG, left), out)
+    _pack("join_right_", X.column(PG, right), out)
+    _pack("join_lines_", X.column(LS, lines), out)
+    out["join_area"] = join_table(PG, left, right, exact_area)
+    out["join_self"] = join_table(PG, left, left, exact_area)
+    out["join_length"] = join_table(LS, lines, right, exact_length)
+    return out
+
+
+def regenerate(path=GOLDEN):
+    arrays = build_arrays()
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    with open(path, "wb") as f:
+        f.write(buf.getvalue())
+    return arrays
+
+
+def families():
+    return [("area", ka, kb) for ka, kb in AREA_FAMILIES] + [("length", kl, kp) for kl, kp in LENGTH_FAMILIES]
+
+
+def fixture_key(what, ka, kb):
+    return f"{what}_{NAMES[ka]}_{NAMES[kb]}_"
+
+
+if __name__ == "__main__":
+    regenerate()
