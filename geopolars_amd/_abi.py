@@ -138,6 +138,7 @@ _PROTOS = {
     "gpk_area": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
     "gpk_signed_area": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
     "gpk_centroid": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_representative_point": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_bounds": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
     "gpk_euclidean_length": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
     "gpk_affine_transform": (C.c_int32, [_VP, C.POINTER(C.c_double), _VP, C.c_int32, _VP]),

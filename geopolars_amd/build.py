@@ -42,6 +42,7 @@ SOURCES = [
     "gpk_overlay.hip",
     "gpk_lineline.hip",
     "gpk_validity.hip",
+    "gpk_interior.hip",
     "gpk_hull.hip",
     "gpk_wkb.cpp",
     "gpk_arrow.cpp",

@@ -236,6 +236,28 @@ class GeoSeries:
         ok = valid.astype(bool) & self.array.is_valid()  # null in, null out; an empty geometry has no centroid
         return GeoSeries(GeoArrowArray.from_points(xy, validity=None if ok.all() else np.packbits(ok, bitorder="little")))
 
+    def representative_point(self, return_width: bool = False):
+        """GeoPandas' representative_point (shapely point_on_surface, gpk_representative_point): a POINT series with one point per row
+        that lies in the row's geometry — the midpoint of the widest section of a scan line through a polygon, the interior vertex of
+        a line nearest to its centroid, the member of a multipoint nearest to the mean — where `centroid` often falls outside.  Null
+        where there is none (a null or empty row, a non-finite coordinate).  With `return_width` also the float64 width of the chosen
+        section (0: a degenerate polygon answered its first coordinate; NaN for lines, points and null rows)."""
+        return_width = return_width_arg(return_width)
+        n = len(self)
+        xy = np.empty((n, 2), dtype=np.float64)
+        valid = np.empty(n, dtype=np.uint8)
+        width = np.empty(n, dtype=np.float64) if return_width else None
+        if n:
+            _abi.check(_abi.lib().gpk_representative_point(
+                self.device().handle, xy.ctypes.data, valid.ctypes.data, width.ctypes.data if return_width else None, MEM_HOST, None))
+        ok = valid.astype(bool)
+        pts = GeoSeries(GeoArrowArray.from_points(xy, validity=None if ok.all() else np.packbits(ok, bitorder="little")))
+        return (pts, width) if return_width else pts
+
+    def point_on_surface(self, return_width: bool = False):
+        """shapely's name of representative_point"""
+        return self.representative_point(return_width)
+
     def convex_hull(self) -> "GeoSeries":
         a = self.array
         xy = np.empty((a.n_coords + len(self), 2), dtype=np.float64)
@@ -778,6 +800,33 @@ VALIDITY_NAMES = (
     "disconnected interior",
     "null",
 )
+
+
+def return_width_arg(return_width) -> bool:
+    """the `return_width` of representative_point as a bool; anything else is refused here, before any device call"""
+    if not isinstance(return_width, (bool, np.bool_)):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"representative_point: return_width must be a bool (found {return_width!r})")
+    return bool(return_width)
+
+
+def representative_point_device(dev: DeviceGeoArray, out_xy, out_valid=None, out_width=None, stream: int = 0) -> DeviceGeoArray:
+    """Device-buffer variant of representative_point: out_xy (n, 2) float64, out_valid (n,) uint8 and out_width (n,) float64 torch
+    CUDA tensors (the last two optional) are filled in place on `stream`.  Returns a POINT DeviceGeoArray that views out_xy — rows
+    without an answer are NaN points, which every join treats as empty — so the result feeds a join without a host round trip."""
+    if not isinstance(dev, DeviceGeoArray):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "representative_point_device: a DeviceGeoArray is needed")
+    n = dev.n_geoms
+    for name, t, shape, dtype in (("out_xy", out_xy, (n, 2), "torch.float64"), ("out_valid", out_valid, (n,), "torch.uint8"),
+                                  ("out_width", out_width, (n,), "torch.float64")):
+        if t is None and name != "out_xy":
+            continue
+        if t is None or tuple(getattr(t, "shape", ())) != shape or str(getattr(t, "dtype", None)) != dtype or not t.is_cuda or not t.is_contiguous():
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"representative_point_device: {name} must be a contiguous CUDA tensor of shape {shape}, {dtype}")
+    if n:
+        _abi.check(_abi.lib().gpk_representative_point(
+            dev.handle, out_xy.data_ptr(), None if out_valid is None else out_valid.data_ptr(), None if out_width is None else out_width.data_ptr(),
+            _abi.MEM_DEVICE, stream))
+    return DeviceGeoArray.from_device_buffers(GEOM_POINT, out_xy, stream=stream)
 
 
 def validity_family_arg(op: str, family: int, allowed) -> None:

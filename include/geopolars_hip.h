@@ -231,6 +231,41 @@ int32_t gpk_signed_area(const gpk_geoarray* a, double* out, int32_t out_space, v
 /* centroid: geoseries.rs:18-21,192-194.  out_xy[2*n_geoms]; out_valid[n_geoms] bytes (0 = empty geometry -> null) */
 int32_t gpk_centroid(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, int32_t out_space,
                      void* stream);
+/* representative_point (GeoPandas representative_point, shapely point_on_surface; the rules of GEOS's InteriorPointArea /
+ * InteriorPointLine / InteriorPointPoint): one point per row that lies in the row's geometry, where the centroid of an L shape, a
+ * ring shape, a multipolygon or a polyline often does not.  out_xy[2*n_geoms]; out_valid[n_geoms] bytes (may be NULL);
+ * out_width[n_geoms] (may be NULL).  Both coordinate layouts of gpk_geoarray_upload are accepted.
+ *   POLYGON | MULTIPOLYGON, for every non-empty member (a member without rings or with an empty shell is ignored):
+ *     scan line   centreY = (miny + maxy) / 2 of the member's coordinates (all rings).  loY = miny, hiY = maxy; for every coordinate
+ *                 y of every ring: y <= centreY and y > loY sets loY = y, y > centreY and y < hiY sets hiY = y.
+ *                 scanY = (loY + hiY) / 2: comparisons and one average, bit-exact.
+ *     crossings   every ring edge (p0, p1) that is not horizontal and has min(y0, y1) <= scanY <= max(y0, y1), but not an edge
+ *                 that meets the line only at its upper end (y0 == scanY && y1 < scanY, or y1 == scanY && y0 < scanY; this can
+ *                 arise only when loY and hiY are adjacent doubles).  x = x0 when x0 == x1, else
+ *                 x0 + (scanY - y0) * ((x1 - x0) / (y1 - y0)), every operation rounded on its own (no contraction).
+ *     sections    the member's crossings in ascending order of x, ties broken by edge index, pair up: (0, 1), (2, 3), ...;
+ *                 width = x[2k + 1] - x[2k].
+ *     choice      the point is ((x[2k] + x[2k + 1]) / 2, scanY) of the widest section over all members;
+ *                 a later section only when strictly wider: the first of equal widths wins in storage order.  out_width = that width.
+ *     degenerate  a row without a section of positive width (zero area, all crossings coincident, an odd crossing count of invalid
+ *                 input) answers its first coordinate with out_width exactly 0.
+ *     invalid polygons: the value is unspecified, the call terminates
+ *                 (gpk_validity says which rows are valid).
+ *   Guarantee: the point of a valid polygon with out_width > 0 is strictly inside it as far as f64 carries: x is within
+ *   1e-9 * (row box diagonal) + 4 ulp(max |x| of the row) of the exact midpoint of a section whose exact width is within that
+ *   bound of the exact maximum, y is scanY bit for bit; a row whose widest section is at least 1e-6 * diagonal wide satisfies
+ *   gpk_predicate_rowwise(contains) with its point.
+ *   LINESTRING | MULTILINESTRING: among the interior vertices (coordinates that are neither first nor last of their member) the one
+ *     nearest to the row's centroid (length-weighted: what gpk_centroid returns); a row without an interior vertex answers the
+ *     nearest member end point.  Distance dx*dx + dy*dy in f64; a later vertex only when strictly nearer.  The answer is a
+ *     coordinate of the row, bit for bit.  The centroid of a row without a member of positive length is geo's: the mean of the
+ *     members' first coordinates, each weighted by its number of segments (a member of one coordinate: 1).
+ *   POINT | MULTIPOINT: the member nearest to the mean of the members, same tie rule.  A POINT answers itself.
+ *   Lineal and puntal rows give out_width = NaN.
+ *   A null row, a row without a coordinate and a row with a NaN or infinite coordinate give out_valid = 0, a NaN point and
+ *   out_width = NaN.  Empty members are ignored.
+ * Errors and out_space as for gpk_centroid. */
+int32_t gpk_representative_point(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, double* out_width, int32_t out_space, void* stream);
 /* bounds (north-star) / envelope (geoseries.rs:28-33,200-202): out[4*n_geoms] = minx,miny,maxx,maxy;
  * empty geometry -> NaN x4 */
 int32_t gpk_bounds(const gpk_geoarray* a, double* out4, int32_t out_space, void* stream);
