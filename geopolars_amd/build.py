@@ -34,6 +34,8 @@ SOURCES = [
     "gpk_pipindex.hip",
     "gpk_rowwise.hip",
     "gpk_pairdist.hip",
+    "gpk_hausdorff.hip",
+    "gpk_frechet.hip",
     "gpk_nearest.hip",
     "gpk_dwithin.hip",
     "gpk_linref.hip",

@@ -8,6 +8,7 @@
 #include <cfloat>
 
 #include "gpk_device.h"
+#include "gpk_frac.h"
 
 namespace gpk {
 
@@ -21,10 +22,7 @@ namespace gpk {
 // r = dot / d2 is compared with 0 and 1 through dot <= 0 and dot >= d2 (same sign; at r ~ 1 the two
 // formulas agree to O((1-r)^2)).  Fractions are compared by cross-multiplication; one divide + sqrt per
 // row at the end.  Results agree with the upstream expression to a few ulps, inside the 1e-9 contract.
-struct Frac {
-    double num, den;
-};
-__device__ __forceinline__ bool frac_less(const Frac& a, const Frac& b) { return a.num * b.den < b.num * a.den; }
+// (Frac and frac_less: gpk_frac.h, shared with the host)
 __device__ __forceinline__ double frac_sqrt(const Frac& f) { return f.num == INFINITY ? DBL_MAX : sqrt(f.num / f.den); }
 
 __device__ __forceinline__ Frac segment_dist2(double px, double py, double sx, double sy, double ex, double ey, double& cross_out,
@@ -81,6 +79,16 @@ __device__ __forceinline__ Frac gmin_frac(Frac v) {
     for (int o = G / 2; o > 0; o >>= 1) {
         const Frac w{__shfl_xor(v.num, o, 64), __shfl_xor(v.den, o, 64)};
         if (frac_less(w, v)) v = w;
+    }
+    return v;
+}
+// the group's largest fraction (gpk_hausdorff.hip: the max of the lanes' minima)
+template <int G>
+__device__ __forceinline__ Frac gmax_frac(Frac v) {
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) {
+        const Frac w{__shfl_xor(v.num, o, 64), __shfl_xor(v.den, o, 64)};
+        if (frac_less(v, w)) v = w;
     }
     return v;
 }

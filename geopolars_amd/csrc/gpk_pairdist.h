@@ -12,8 +12,7 @@
 
 namespace gpk {
 
-// rows whose n_A * n_B exceeds this go to the work-group schedule.  A first value, not swept: DESIGN.md 4.3c lists what was measured
-constexpr int64_t PD_LARGE_COST = 1 << 16;
+// (PD_LARGE_COST, the rows that go to the work-group schedule: gpk_frac.h)
 constexpr int PD_VOTE = 32;      // walked coordinates between two group votes on "an intersection was found"
 constexpr int PDL_CHUNK = 1024;  // segments of the walked side staged in LDS per round of the work-group schedule (32 KB)
 
@@ -66,21 +65,7 @@ __device__ __forceinline__ double2 seg_end(const RowSeqs& r, int s, int c, doubl
     return (r.so && c + 1 < r.so[s + 1]) ? r.xy[c + 1] : p;
 }
 
-// Squared distance from p to segment (s, e) as a fraction, as segment_dist2 (gpk_distance.h) but with the cross product
-// evaluated by Kahan's fma algorithm: within 1.5 ulp of the exact product difference, and zero only when that is zero.
-__device__ __forceinline__ Frac pair_seg_dist2(double px, double py, double sx, double sy, double ex, double ey) {
-    const double dx = ex - sx, dy = ey - sy, qx = px - sx, qy = py - sy;
-    const double d2 = dx * dx + dy * dy;
-    const double dot = qx * dx + qy * dy;
-    if (d2 == 0.0 || dot <= 0.0) return Frac{qx * qx + qy * qy, 1.0};
-    if (dot >= d2) {
-        const double rx = px - ex, ry = py - ey;
-        return Frac{rx * rx + ry * ry, 1.0};
-    }
-    const double w = qy * dx;
-    const double cross = __builtin_fma(qx, dy, -w) + __builtin_fma(-qy, dx, w);
-    return Frac{cross * cross, d2};
-}
+// (pair_seg_dist2, the squared point-segment distance as a fraction with a Kahan cross product: gpk_frac.h)
 
 // One segment pair: both point-segment distances (p0 against q, q0 against p) and, when the boxes meet, the exact crossing test.
 struct PairAcc {

@@ -399,6 +399,51 @@ class GeoSeries:
         )
         return out
 
+    def hausdorff_distance(self, other: "GeoSeries", densify=None, other_rows=None) -> np.ndarray:
+        """GeoPandas' GeoSeries.hausdorff_distance: the discrete Hausdorff distance of row i and other[other_rows[i]], between the
+        rows' boundaries (gpk_hausdorff_distance; every pair of families).  `densify` is GeoPandas' fraction in (0, 1]: every segment
+        is cut into k = round(1 / densify) equal parts whose ends are samples; None means the vertices alone.  NaN for a null or empty
+        row; identical rows give exactly 0.0; hausdorff_distance(a, b) and (b, a) are the same doubles."""
+        k = densify_arg("hausdorff_distance", densify)
+        rows = distance_rows_arg("hausdorff_distance", self, other, other_rows)
+        out = np.empty(len(self), dtype=np.float64)
+        if len(out) == 0:
+            return out
+        _abi.check(
+            _abi.lib().gpk_hausdorff_distance(
+                self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, k, out.ctypes.data, MEM_HOST, None
+            )
+        )
+        return out
+
+    def frechet_distance(self, other: "GeoSeries", densify=None, other_rows=None, errors: str = "raise") -> np.ndarray:
+        """GeoPandas' GeoSeries.frechet_distance: the discrete Frechet distance of row i and other[other_rows[i]] over the samples that
+        `densify` defines (see hausdorff_distance), LINESTRING columns only (gpk_frechet_distance).  NaN for a null or empty row.  A
+        row whose shorter side has more than GPK_FRECHET_MAX_SHORT samples is not computed: errors="raise" makes that a ValueError
+        naming the count and the cap, errors="nan" returns NaN for such rows."""
+        if errors not in ("raise", "nan"):
+            raise ValueError('errors must be "raise" or "nan"')
+        k = densify_arg("frechet_distance", densify)
+        for side in (self, other):
+            if side._family() != GEOM_LINESTRING:
+                raise _mismatch(f"frechet_distance: LineString x LineString only, the measure is defined on one ordered sequence per side (found {_abi_name(side._family())})")
+        rows = distance_rows_arg("frechet_distance", self, other, other_rows)
+        out = np.empty(len(self), dtype=np.float64)
+        if len(out) == 0:
+            return out
+        n_over = C.c_int64(0)
+        _abi.check(
+            _abi.lib().gpk_frechet_distance(
+                self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, k, out.ctypes.data, C.byref(n_over), MEM_HOST, None
+            )
+        )
+        if n_over.value and errors == "raise":
+            raise ValueError(
+                f"frechet_distance: {n_over.value} of {len(out)} rows have more than {FRECHET_MAX_SHORT} samples on their shorter side "
+                "(errors='nan' returns them as NaN)"
+            )
+        return out
+
     def _predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         out = np.empty(len(self), dtype=np.uint8)
         rows = None if other_rows is None else np.ascontiguousarray(other_rows, dtype=np.uint32)
@@ -936,6 +981,44 @@ def relation_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows, line_first: boo
     if len(a) != len(b):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
     return None
+
+
+FRECHET_MAX_SHORT = 16384  # GPK_FRECHET_MAX_SHORT of include/geopolars_hip.h
+MAX_SUBDIVISIONS = 4096  # GPK_MAX_SUBDIVISIONS
+
+
+def densify_arg(op: str, densify) -> int:
+    """GeoPandas' densify fraction as the number of parts a segment is cut into: None -> 1, else round(1 / densify) (Python's round
+    half to even, the rint of the JTS definition).  Anything but a finite number in (0, 1] whose count is at most MAX_SUBDIVISIONS is
+    refused here with ValueError, before the library is called"""
+    if densify is None:
+        return 1
+    try:
+        f = float(densify)
+    except (TypeError, ValueError):
+        raise ValueError(f"{op}: densify must be None or a fraction in (0, 1], got {densify!r}") from None
+    if isinstance(densify, (bool, np.bool_)) or not (0.0 < f <= 1.0):  # (NaN fails the comparison)
+        raise ValueError(f"{op}: densify must be None or a fraction in (0, 1], got {densify!r}")
+    k = 1.0 / f
+    if not (k <= MAX_SUBDIVISIONS + 0.5) or round(k) > MAX_SUBDIVISIONS:
+        raise ValueError(f"{op}: densify = {densify!r} cuts a segment into more than {MAX_SUBDIVISIONS} parts")
+    return int(round(k))
+
+
+def distance_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
+    """the row pairing of hausdorff_distance / frechet_distance before any device call: without a row map the row counts match; a row
+    map (returned as uint32) has one entry per row of `a`"""
+    if rows is None:
+        if len(a) != len(b):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+        return None
+    try:
+        r = np.ascontiguousarray(rows, dtype=np.uint32)
+    except (TypeError, ValueError, OverflowError):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+    if r.ndim != 1 or len(r) != len(a):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
+    return r
 
 
 def dwithin_distance_arg(distance) -> float:

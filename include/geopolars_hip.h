@@ -412,6 +412,53 @@ int32_t gpk_rowmap_nbytes(const gpk_rowmap* map, int64_t* out_bytes);
 /* out[n_geoms(a)] as gpk_distance_rowwise(a, b, b_rows, ...) would fill it; a POINT, b the LINESTRING array of the map */
 int32_t gpk_distance_rowmap(const gpk_geoarray* a, const gpk_geoarray* b, const gpk_rowmap* map, double* out,
                             int32_t out_space, void* stream);
+/* Discrete Hausdorff and discrete Frechet distance, row-wise: GeoPandas' GeoSeries.hausdorff_distance(other, densify) and
+ * GeoSeries.frechet_distance(other, densify) (GEOS DiscreteHausdorffDistance / DiscreteFrechetDistance).  `b_rows`, out[n_geoms(a)],
+ * `out_space`, stream ordering and the out-of-range rule are those of gpk_distance_rowwise (b_rows works for every pair of
+ * families here).
+ * Samples.  A row is its coordinate sequences: a LINESTRING is one sequence; every ring of a POLYGON or MULTIPOLYGON and every
+ * linestring of a MULTILINESTRING is a sequence; every MULTIPOINT member and a POINT is a sequence of one coordinate.  Polygon
+ * interiors play no part: both measures are between boundaries, as in GEOS.  With subdivisions = k >= 1 the samples of a sequence
+ * p_0 .. p_(n-1) are, for every segment (p_i, p_(i+1)) and j = 0 .. k-1, the doubles
+ *     x = p_i.x + (double)j * ((p_(i+1).x - p_i.x) / (double)k)      and the same for y,
+ * every operation rounded on its own (no contraction), followed by the last vertex as itself; k = 1 means the vertices.  These
+ * doubles are part of the contract.  Sample counts and costs are computed in 64 bits.  k outside 1 .. GPK_MAX_SUBDIVISIONS is
+ * GPK_ERR_INVALID_ARGUMENT before any device work (GeoPandas' densify fraction f maps to k = rint(1 / f)).
+ *
+ * gpk_hausdorff_distance: every pair of the six families, POINT included.  H = max(h(A->B), h(B->A)); h(A->B) is the maximum over
+ * the samples of A of the minimum over the segments of B (undensified) of the point-segment distance.  Segments as in
+ * gpk_distance_rowwise: coordinate c gives (c, c + 1) inside its sequence, else the degenerate (c, c).
+ *   - terms are squared point-segment distances kept as fractions (pair_seg_dist2, csrc/gpk_pairdist.h) and compared by
+ *     cross-multiplication; one square root is taken at the end;
+ *   - there is no substitution for a computed zero: two identical rows give exactly 0.0;
+ *   - a null side, an empty side (no member has a coordinate; a POINT with a NaN coordinate) or a b_rows entry out of range
+ *     gives NaN.
+ *   Accuracy: within 16 u (H + 2 lmax) of the exact value over the contract's samples, lmax the longest undensified segment of the
+ *   pair — the bound gpk_distance_rowwise states: every term carries it, and a max of mins moves by no more than its worst term.
+ *   hausdorff(a, b) and hausdorff(b, a) evaluate the same terms in the same order (the columns are taken in canonical order, the
+ *   final choice between the two directed values does not look at their order): they are bit-identical, as are two calls on the
+ *   same input.  Magnitude range: as gpk_distance_rowwise.
+ *
+ * gpk_frechet_distance: LINESTRING x LINESTRING only; any other pair is GPK_ERR_MISMATCHED_GEOMETRY, because the measure is defined
+ * on ONE ordered sequence per side (GEOS flattens a multi-geometry into one sequence, which measures the jumps between its members;
+ * that is not offered).  The discrete Frechet distance of the two sample sequences P (n' samples) and Q (m' samples):
+ *     c(0,0) = d(0,0);  c(i,j) = max(d(i,j), min(c(i-1,j), c(i,j-1), c(i-1,j-1))), missing neighbours left out;
+ *     result = sqrt(c(n'-1, m'-1)),
+ * on squared distances d = dx*dx + dy*dy in f64.  A one-coordinate linestring is a sequence of one sample.  A null or empty side
+ * or a b_rows entry out of range gives NaN.
+ *   Accuracy: relative error at most 4 u — each difference is correctly rounded (u), the two squares and the sum add three more
+ *   roundings, so every d is within a factor 1 +- 4u; max and min are monotone; the square root halves the error and adds u.  The
+ *   result is exactly 0 iff the exact value is 0.  frechet(a, b) and frechet(b, a) are bit-identical (max and min only select).
+ *   Rows whose SHORTER side has more than GPK_FRECHET_MAX_SHORT samples after densification are not computed: the result is NaN
+ *   and the row is counted in *n_over.  16384 samples are a boundary column of 128 KB in the 160 KB of LDS behind a row
+ *   (csrc/gpk_frechet.h).  n_over (host) may be NULL: then nothing is read back and a device output stays stream-ordered; with
+ *   n_over the call waits for the stream, as gpk_reproject does for n_failed. */
+#define GPK_FRECHET_MAX_SHORT 16384
+#define GPK_MAX_SUBDIVISIONS 4096
+int32_t gpk_hausdorff_distance(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, int32_t subdivisions,
+                               double* out, int32_t out_space, void* stream);
+int32_t gpk_frechet_distance(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, int32_t subdivisions,
+                             double* out, int64_t* n_over, int32_t out_space, void* stream);
 /* contains / within / intersects row-wise (north-star additions to the trait; semantics from the
  * dispatch table spatial_index.rs:89-137, geo 0.27 traits).  out[n] bytes 0/1.  Pairs with an answer:
  * point x polygonal (all three), polygonal x polygonal (intersects; contains / within = "the contained side
