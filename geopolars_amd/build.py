@@ -46,6 +46,7 @@ SOURCES = [
     "gpk_validity.hip",
     "gpk_interior.hip",
     "gpk_hull.hip",
+    "gpk_minbound.hip",
     "gpk_wkb.cpp",
     "gpk_arrow.cpp",
     "gpk_wkb_device.hip",

@@ -9,6 +9,7 @@
 // size -> scan -> compact.
 // This is the lowest-traffic operator of the surface; the sort's working set sits in LDS.
 #include "gpk_device.h"
+#include "gpk_hull.h"
 #include "gpk_scan.h"
 
 namespace gpk {
@@ -73,30 +74,6 @@ __device__ __forceinline__ int chain_of(LD ld, int n, PUT put, GET get, double2*
     for (int j = 0; j < k; ++j) h[j] = ld(get(j));
     h[k] = h[0];  // close the ring
     return k + 1;
-}
-
-__device__ __forceinline__ void geom_coord_range(const DevGeo& a, int64_t g, int& c0, int& c1) {
-    switch (a.type) {
-    case GPK_GEOM_POINT: {
-        const double2 p = a.xy[g];
-        c0 = (int)g;
-        c1 = (isnan(p.x) || isnan(p.y)) ? (int)g : (int)g + 1;
-        break;
-    }
-    case GPK_GEOM_LINESTRING:
-    case GPK_GEOM_MULTIPOINT:
-        c0 = a.geom_off[g];
-        c1 = a.geom_off[g + 1];
-        break;
-    case GPK_GEOM_POLYGON:
-    case GPK_GEOM_MULTILINESTRING:
-        c0 = a.ring_off[a.geom_off[g]];
-        c1 = a.ring_off[a.geom_off[g + 1]];
-        break;
-    default:
-        c0 = a.ring_off[a.part_off[a.geom_off[g]]];
-        c1 = a.ring_off[a.part_off[a.geom_off[g + 1]]];
-    }
 }
 
 // scratch layout per geometry g with coordinate range [c0, c1): sorted copy at sorted[c0..c0 + n_pts[g]), chain stack at
@@ -330,40 +307,26 @@ __global__ __launch_bounds__(256) void hull_compact_kernel(DevGeo a, const doubl
     for (int i = lane; i < n; i += HULL_GS) out[o + i] = h[i];
 }
 
-}  // namespace gpk
-
-using namespace gpk;
-
-extern "C" int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_t* out_ring_offsets, int32_t out_space,
-                                   void* stream) {
-    if (!a || !out_xy || !out_ring_offsets) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    GPK_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n = a->d.n_geoms, nc = a->d.n_coords;
-    const size_t cap_coords = (size_t)(nc + n);
+// ---- the hull stage (gpk_hull.h): everything up to the scratch hulls -------------------------------------------------------------------
+size_t hull_stage_bytes(int64_t n, int64_t nc) {
     const size_t off_bytes = sizeof(int32_t) * (size_t)(n + 1);
-    const int64_t nb = (n + 255) / 256;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    size_t need = align256(sizeof(double2) * (size_t)(nc + 1)) + align256(sizeof(double2) * (2 * (size_t)nc + 2 * (size_t)n + 2)) +
-                  2 * align256(off_bytes) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) +
-                  align256(sizeof(int32_t) * (2 * (size_t)nc + 2 * (size_t)n + 2)) + 2 * align256(off_bytes) + 1024;
-    if (host_out) need += align256(sizeof(double2) * cap_coords) + align256(off_bytes);
-    GPK_TRY(workspace().begin(need));
+    return align256(sizeof(double2) * (size_t)(nc + 1)) + align256(sizeof(double2) * (2 * (size_t)nc + 2 * (size_t)n + 2)) + 4 * align256(off_bytes) +
+           align256(sizeof(int32_t) * (2 * (size_t)nc + 2 * (size_t)n + 2));
+}
+
+int32_t hull_stage(const gpk_geoarray* a, HullStage* out, hipStream_t s) {
+    const int64_t n = a->d.n_geoms, nc = a->d.n_coords;
+    const size_t off_bytes = sizeof(int32_t) * (size_t)(n + 1);
     double2* sorted = (double2*)workspace().take(sizeof(double2) * (size_t)(nc + 1));
     double2* stack = (double2*)workspace().take(sizeof(double2) * (2 * (size_t)nc + 2 * (size_t)n + 2));
     int32_t* sizes = (int32_t*)workspace().take(off_bytes);
     int32_t* n_pts = (int32_t*)workspace().take(off_bytes);
     int32_t* idx_scratch = (int32_t*)workspace().take(sizeof(int32_t) * (2 * (size_t)nc + 2 * (size_t)n + 2));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
     int32_t* big_list = (int32_t*)workspace().take(off_bytes);  // [0, n): ids of the geometries beyond HULL_CAP points, [n]: their number
     int32_t* mid_list = (int32_t*)workspace().take(off_bytes);  // the same for 65 .. HULL_CAP points
-    double2* out_dev = host_out ? (double2*)workspace().take(sizeof(double2) * cap_coords) : (double2*)out_xy;
-    int32_t* off_dev = host_out ? (int32_t*)workspace().take(off_bytes) : out_ring_offsets;
-    if (n == 0) {
-        GPK_HIP(hipMemsetAsync(off_dev, 0, sizeof(int32_t), s));
-        return copy_out(out_ring_offsets, out_space, off_dev, sizeof(int32_t), s);
-    }
-    const dim3 grid((unsigned)nb), block(256);
+    *out = HullStage{stack, sizes, n_pts};
+    if (n == 0) return GPK_OK;
+    const dim3 block(256);
     GPK_HIP(hipMemsetAsync(big_list + n, 0, sizeof(int32_t), s));
     GPK_HIP(hipMemsetAsync(mid_list + n, 0, sizeof(int32_t), s));
     const dim3 ggrid((unsigned)((n * HULL_GS + 255) / 256));
@@ -382,8 +345,38 @@ extern "C" int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_
         GPK_LAUNCH("gpk_hull_chain_big", hull_chain_big_kernel, dim3((unsigned)chain_blocks), dim3(64), 0, s, a->d, (const double2*)sorted,
                    (const int32_t*)n_pts, (const int32_t*)big_list, (const int32_t*)(big_list + n), stack, idx_scratch, sizes);
     }
-    GPK_TRY(exclusive_scan_i32(sizes, n, off_dev, nullptr, btot, s));
-    GPK_LAUNCH("gpk_hull_compact", hull_compact_kernel, ggrid, block, 0, s, a->d, stack, off_dev, out_dev);
+    return GPK_OK;
+}
+
+}  // namespace gpk
+
+using namespace gpk;
+
+extern "C" int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_t* out_ring_offsets, int32_t out_space,
+                                   void* stream) {
+    if (!a || !out_xy || !out_ring_offsets) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
+    GPK_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = a->d.n_geoms, nc = a->d.n_coords;
+    const size_t cap_coords = (size_t)(nc + n);
+    const size_t off_bytes = sizeof(int32_t) * (size_t)(n + 1);
+    const int64_t nb = (n + 255) / 256;
+    const bool host_out = out_space != GPK_MEM_DEVICE;
+    size_t need = hull_stage_bytes(n, nc) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + 1024;
+    if (host_out) need += align256(sizeof(double2) * cap_coords) + align256(off_bytes);
+    GPK_TRY(workspace().begin(need));
+    HullStage h;
+    GPK_TRY(hull_stage(a, &h, s));
+    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
+    double2* out_dev = host_out ? (double2*)workspace().take(sizeof(double2) * cap_coords) : (double2*)out_xy;
+    int32_t* off_dev = host_out ? (int32_t*)workspace().take(off_bytes) : out_ring_offsets;
+    if (n == 0) {
+        GPK_HIP(hipMemsetAsync(off_dev, 0, sizeof(int32_t), s));
+        return copy_out(out_ring_offsets, out_space, off_dev, sizeof(int32_t), s);
+    }
+    const dim3 ggrid((unsigned)((n * HULL_GS + 255) / 256)), block(256);
+    GPK_TRY(exclusive_scan_i32(h.sizes, n, off_dev, nullptr, btot, s));
+    GPK_LAUNCH("gpk_hull_compact", hull_compact_kernel, ggrid, block, 0, s, a->d, h.stack, off_dev, out_dev);
     if (host_out) {
         GPK_TRY(copy_out(out_ring_offsets, out_space, off_dev, off_bytes, s));
         const int32_t total = out_ring_offsets[n];

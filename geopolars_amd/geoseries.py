@@ -268,6 +268,52 @@ class GeoSeries:
             GeoArrowArray(GEOM_POLYGON, xy, geom_offsets=np.arange(len(self) + 1, dtype=np.int32), ring_offsets=ring_off, validity=a.validity)
         )
 
+    def minimum_rotated_rectangle(self) -> "GeoSeries":
+        """GeoPandas' minimum_rotated_rectangle (shapely oriented_envelope, gpk_minimum_rotated_rectangle): a POLYGON series with the
+        least-area rectangle on an edge of the row's convex hull as one closed 5-coordinate ring per row (a single point: the point five
+        times; collinear coordinates p .. q: p q q p p).  A row without an answer (no coordinate, a non-finite coordinate) becomes an
+        empty polygon; a null row stays null."""
+        n = len(self)
+        xy = np.empty((5 * n, 2), dtype=np.float64)
+        valid = np.empty(n, dtype=np.uint8)
+        if n:
+            _abi.check(_abi.lib().gpk_minimum_rotated_rectangle(self.device().handle, xy.ctypes.data, valid.ctypes.data, MEM_HOST, None))
+        return _ring_series(xy, valid.astype(bool), 5, self.array.validity)
+
+    def oriented_envelope(self) -> "GeoSeries":
+        """shapely's name of minimum_rotated_rectangle"""
+        return self.minimum_rotated_rectangle()
+
+    def _bounding_circle(self, want_centre: bool):
+        n = len(self)
+        centre = np.empty((n, 2), dtype=np.float64) if want_centre else None
+        radius = np.empty(n, dtype=np.float64)
+        valid = np.empty(n, dtype=np.uint8)
+        if n:
+            _abi.check(_abi.lib().gpk_minimum_bounding_circle(
+                self.device().handle, centre.ctypes.data if want_centre else None, radius.ctypes.data, valid.ctypes.data, MEM_HOST, None))
+        return centre, radius, valid.astype(bool)
+
+    def minimum_bounding_radius(self) -> np.ndarray:
+        """GeoPandas' minimum_bounding_radius (gpk_minimum_bounding_circle): the float64 radius of the smallest circle that contains the
+        row's coordinates; NaN where there is none (a null or empty row, a non-finite coordinate)."""
+        return self._bounding_circle(False)[1]
+
+    def minimum_bounding_circle_parts(self):
+        """(POINT series of the centres, float64 radii) of the smallest circle that contains each row's coordinates; a row without an
+        answer is a null point and a NaN radius."""
+        centre, radius, ok = self._bounding_circle(True)
+        return GeoSeries(GeoArrowArray.from_points(centre, validity=None if ok.all() else np.packbits(ok, bitorder="little"))), radius
+
+    def minimum_bounding_circle(self, quad_segs: int = 8) -> "GeoSeries":
+        """GeoPandas' minimum_bounding_circle: a POLYGON series, the smallest circle that contains each row's coordinates as a ring of
+        4 * quad_segs + 1 coordinates centre + r (cos t, sin t), counter-clockwise from t = 0, the last coordinate the first bit for
+        bit.  Centre and radius come from the GPU (gpk_minimum_bounding_circle); the ring is laid out here.  A radius-0 row gives the
+        point repeated; a row without an answer an empty polygon; a null row stays null."""
+        quad_segs = quad_segs_arg(quad_segs)
+        centre, radius, ok = self._bounding_circle(True)
+        return _ring_series(circle_rings(centre, radius, quad_segs), ok, 4 * quad_segs + 1, self.array.validity)
+
     def affine_transform(self, matrix: Sequence[float]) -> "GeoSeries":
         """matrix = [a, b, xoff, d, e, yoff] — the order `AffineTransform::from([f64; 6])` takes and
         py-geopolars/src/geo.rs:10-16 forwards (NOT the [a,b,d,e,xoff,yoff] of the Python docstring,
@@ -872,6 +918,68 @@ def representative_point_device(dev: DeviceGeoArray, out_xy, out_valid=None, out
             dev.handle, out_xy.data_ptr(), None if out_valid is None else out_valid.data_ptr(), None if out_width is None else out_width.data_ptr(),
             _abi.MEM_DEVICE, stream))
     return DeviceGeoArray.from_device_buffers(GEOM_POINT, out_xy, stream=stream)
+
+
+def _ring_series(xy: np.ndarray, ok: np.ndarray, k: int, validity) -> GeoSeries:
+    """a POLYGON series of one k-coordinate ring per row with ok, an empty polygon (no ring) per row without; `validity` is the input's"""
+    n = len(ok)
+    xy = np.ascontiguousarray(xy.reshape(n, k, 2)[ok].reshape(-1, 2))
+    geom_off = np.concatenate(([0], np.cumsum(ok, dtype=np.int64))).astype(np.int32)
+    ring_off = np.arange(0, k * int(ok.sum()) + 1, k, dtype=np.int32)
+    return GeoSeries(GeoArrowArray(GEOM_POLYGON, xy, geom_offsets=geom_off, ring_offsets=ring_off, validity=validity, n_geoms=n))
+
+
+def quad_segs_arg(quad_segs) -> int:
+    """the `quad_segs` of minimum_bounding_circle as an int in 1 .. 256; anything else is refused here, before any device call"""
+    if isinstance(quad_segs, (bool, np.bool_)) or not isinstance(quad_segs, (int, np.integer)) or not 1 <= int(quad_segs) <= 256:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"minimum_bounding_circle: quad_segs must be an integer in 1 .. 256 (found {quad_segs!r})")
+    return int(quad_segs)
+
+
+def circle_rings(centre: np.ndarray, radius: np.ndarray, quad_segs: int) -> np.ndarray:
+    """(n * (4 quad_segs + 1), 2): per row centre + r (cos t, sin t) for t = 0, pi / (2 quad_segs), ... counter-clockwise, closed by a copy
+    of the first coordinate"""
+    m = 4 * quad_segs
+    t = np.arange(m, dtype=np.float64) * (np.pi / (2 * quad_segs))
+    ring = np.empty((len(radius), m + 1, 2), dtype=np.float64)
+    ring[:, :m, 0] = centre[:, 0:1] + radius[:, None] * np.cos(t)[None, :]
+    ring[:, :m, 1] = centre[:, 1:2] + radius[:, None] * np.sin(t)[None, :]
+    ring[:, m] = ring[:, 0]
+    return ring.reshape(-1, 2)
+
+
+def _device_out_args(op: str, dev, outs):
+    """the checks of the device-buffer forms before any device call: a DeviceGeoArray, and every given buffer a contiguous CUDA tensor of
+    its shape and dtype (`outs`: (name, tensor, shape, dtype, required))"""
+    if not isinstance(dev, DeviceGeoArray):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: a DeviceGeoArray is needed")
+    for name, t, shape, dtype, required in outs(dev.n_geoms):
+        if t is None and not required:
+            continue
+        if t is None or tuple(getattr(t, "shape", ())) != shape or str(getattr(t, "dtype", None)) != dtype or not t.is_cuda or not t.is_contiguous():
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {name} must be a contiguous CUDA tensor of shape {shape}, {dtype}")
+
+
+def minimum_rotated_rectangle_device(dev: DeviceGeoArray, out_xy, out_valid=None, stream: int = 0) -> None:
+    """Device-buffer variant of minimum_rotated_rectangle: out_xy (n, 5, 2) float64 and out_valid (n,) uint8 (optional) torch CUDA tensors
+    are filled in place on `stream`; rows without an answer are NaN."""
+    _device_out_args("minimum_rotated_rectangle_device", dev,
+                     lambda n: (("out_xy", out_xy, (n, 5, 2), "torch.float64", True), ("out_valid", out_valid, (n,), "torch.uint8", False)))
+    if dev.n_geoms:
+        _abi.check(_abi.lib().gpk_minimum_rotated_rectangle(
+            dev.handle, out_xy.data_ptr(), None if out_valid is None else out_valid.data_ptr(), _abi.MEM_DEVICE, stream))
+
+
+def minimum_bounding_circle_device(dev: DeviceGeoArray, out_radius, out_center=None, out_valid=None, stream: int = 0) -> None:
+    """Device-buffer variant of minimum_bounding_circle_parts: out_radius (n,) float64, out_center (n, 2) float64 and out_valid (n,) uint8
+    torch CUDA tensors (the last two optional) are filled in place on `stream`; rows without an answer are NaN."""
+    _device_out_args("minimum_bounding_circle_device", dev,
+                     lambda n: (("out_radius", out_radius, (n,), "torch.float64", True), ("out_center", out_center, (n, 2), "torch.float64", False),
+                                ("out_valid", out_valid, (n,), "torch.uint8", False)))
+    if dev.n_geoms:
+        _abi.check(_abi.lib().gpk_minimum_bounding_circle(
+            dev.handle, None if out_center is None else out_center.data_ptr(), out_radius.data_ptr(),
+            None if out_valid is None else out_valid.data_ptr(), _abi.MEM_DEVICE, stream))
 
 
 def validity_family_arg(op: str, family: int, allowed) -> None:

@@ -367,6 +367,41 @@ int32_t gpk_simplify(const gpk_geoarray* a, double epsilon, double* out_xy, int3
  * out_ring_offsets[n_geoms+1]; out_xy capacity must be >= 2*(n_coords + n_geoms) doubles. */
 int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_t* out_ring_offsets,
                         int32_t out_space, void* stream);
+/* minimum_rotated_rectangle (GeoPandas minimum_rotated_rectangle, shapely oriented_envelope) and minimum_bounding_circle /
+ * minimum_bounding_radius: the two bounding shapes of a row's convex hull.  All six geometry families; a row is its set of
+ * coordinates (holes and members only contribute points, as in gpk_convex_hull).  Both coordinate layouts of gpk_geoarray_upload are
+ * accepted.  Both outputs have a fixed size per row:
+ *   gpk_minimum_rotated_rectangle   out_xy[n_geoms * 5 * 2]: the closed ring c0 c1 c2 c3 c0; out_valid[n_geoms] bytes (may be NULL)
+ *   gpk_minimum_bounding_circle     out_center_xy[n_geoms * 2] (may be NULL), out_radius[n_geoms], out_valid[n_geoms] (may be NULL)
+ * A null row, a row without a coordinate and a row with a NaN or infinite coordinate give out_valid = 0 and NaN in every output slot
+ * (the rule of gpk_representative_point).
+ * Let v_0 .. v_{h-1} be the hull ring exactly as gpk_convex_hull writes it: counter-clockwise, starting at the lexicographically
+ * smallest vertex, no collinear vertices, closing vertex dropped.
+ *   Rectangle.  For edge i, with a = v_i and d = v_{i+1} - a: L2 = d . d; for every hull vertex w, with u = w - a taken first,
+ *     s = u . d and t = d x u; smin, smax and tmax are taken over the hull (smin <= 0 <= smax and tmax >= 0 because a is among the
+ *     vertices); A_i = (smax - smin) * tmax.  The rectangle on edge i has area A_i / L2_i.
+ *     choice      the edge of least area, areas compared by cross-multiplication: A_i * L2_j < A_j * L2_i.  A later edge wins only when
+ *                 strictly smaller: equal areas on exactly representable data go to the lowest edge index.
+ *     corners     c0 = a + (smin / L2) d, c1 = a + (smax / L2) d, c2 = c1 + (tmax / L2) (-d_y, d_x), c3 = c0 + (tmax / L2) (-d_y, d_x).
+ *                 The output is c0 c1 c2 c3 c0: counter-clockwise, the fifth coordinate is the first bit for bit.
+ *     degenerate  one distinct point: that point five times.  All coordinates collinear (hull ring p q p): p q q p p.  Both are valid rows.
+ *     Every operation is rounded on its own (no contraction).  Guarantee: the corners are within 1e-9 * (row box diagonal) +
+ *     4 ulp(max |coordinate| of the row) of the exact rectangle on some edge whose exact area is within that bound (times the
+ *     perimeter) of the exact minimum.
+ *   Circle.  The unique smallest circle that contains the row's coordinates, computed in row-local coordinates with origin v_0.
+ *     A two-point support has its midpoint as centre; a three-point support uses the circumcentre formula on differences from the
+ *     first support point; the radius is the square root of the squared distance from the centre to a support point.  One distinct
+ *     point gives radius exactly 0 and centre = the point.  Method: farthest-point iteration from v_0 and the vertex farthest from it
+ *     (csrc/gpk_minbound.h states every step); it runs at most MBG_CIRCLE_ITERS times, and if it ever stops there the answer is the
+ *     current centre with the distance to the farthest vertex as radius: a circle that still contains the row.  Guarantee: centre and
+ *     radius within the bound above of the exact ones.
+ * Every data-dependent loop carries a bound derived from h: no input can keep a wave spinning.
+ * Errors: GPK_ERR_INVALID_ARGUMENT ("NULL argument") for a NULL a, out_xy or out_radius, before any device work; out_space as for
+ * gpk_centroid. */
+#define MBG_CIRCLE_ITERS 64
+int32_t gpk_minimum_rotated_rectangle(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, int32_t out_space, void* stream);
+int32_t gpk_minimum_bounding_circle(const gpk_geoarray* a, double* out_center_xy, double* out_radius, uint8_t* out_valid, int32_t out_space,
+                                    void* stream);
 
 /* ---- row-wise binary operators ------------------------------------------------------------ */
 /* distance: geoseries.rs:141-146,248-251 ("1-to-1 row-wise").  `b_rows` (optional, same space as
