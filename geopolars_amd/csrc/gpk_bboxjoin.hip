@@ -1,5 +1,6 @@
 // gpk_bboxjoin.hip — the staged box-candidate join: candidates per left box from the right side's grid directory, the caller's refine
-// (CandRefine, gpk_candjoin.h), then count / scan / emit of the hits sorted by (l, r).
+// (CandRefine, gpk_candjoin.h), then count / scan / emit of the hits sorted by (l, r); and payload_join, the driver of the joins that
+// return a value per pair over it (temporary index, boxes, payload staging and the one gather kernel).
 //
 //   candidates  == intersection_candidates_with_other_tree            spatial_index.rs:74-76
 //   the refines of gpk_spatial_join's polygonal and lineal arms       spatial_index.rs:83-143
@@ -305,6 +306,23 @@ __global__ __launch_bounds__(256) void pair_emit_kernel(int64_t n_rows, const in
     if (!WRITE) counts[i] = cnt;
 }
 
+// payload_join: the per-candidate elements of row i's hits, in candidate order, at the row's offset of the output
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void payload_gather_kernel(int64_t n_rows, const int32_t* __restrict__ cand_off, const uint8_t* __restrict__ hit,
+                                                             const int32_t* __restrict__ offsets, const T* __restrict__ payload,
+                                                             T* __restrict__ out, int64_t capacity) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    int64_t o = offsets[i];
+    for (int c = cand_off[i]; c < cand_off[i + 1]; ++c) {
+        if (!hit[c]) continue;
+        if (o < capacity) out[o] = payload[c];
+        ++o;
+    }
+}
+}  // namespace
+
 __global__ void i32_to_u32_copy_kernel(const int32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (uint32_t)in[i];
@@ -487,6 +505,77 @@ int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(GPK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
     return finish_pairs(what, (int64_t)total, n, out_counts, counts_out, out_pairs, pairs_dev, pair_capacity, n_pairs, out_space, s);
+}
+
+// ---- bbox_join with a value per pair (gpk_candjoin.h) ----------------------------------------------------------------------------
+static int32_t payload_emitted(void* ctx, int64_t n_rows, const int32_t* cand_off, const uint8_t* hit, const int32_t* offsets, void* scratch,
+                               int64_t pair_capacity, hipStream_t s) {
+    const PayloadCtx& cx = *(const PayloadCtx*)ctx;
+    if (!cx.payload_out) return GPK_OK;
+    const dim3 grid((unsigned)((n_rows + 255) / 256));
+    const void* payload = (const char*)scratch + 256;
+    if (cx.payload_elem == sizeof(uint8_t))
+        GPK_LAUNCH(cx.gather_label, (payload_gather_kernel<uint8_t>), grid, dim3(256), 0, s, n_rows, cand_off, hit, offsets, (const uint8_t*)payload,
+                   (uint8_t*)cx.payload_out, pair_capacity);
+    else
+        GPK_LAUNCH(cx.gather_label, (payload_gather_kernel<double>), grid, dim3(256), 0, s, n_rows, cand_off, hit, offsets, (const double*)payload,
+                   (double*)cx.payload_out, pair_capacity);
+    return GPK_OK;
+}
+
+int32_t payload_join(const PayloadJoin& join, const gpk_index* right_index, uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs,
+                     void* out_payload, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream) {
+    PayloadCtx& cx = *join.ctx;
+    const gpk_geoarray *left = cx.left, *right = cx.right;
+    GPK_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = left->d.n_geoms;
+    if (n == 0) return GPK_OK;
+    if (n > (int64_t)INT32_MAX) return fail(GPK_ERR_INVALID_ARGUMENT, "%s: more than 2^31 - 1 left rows: shard the left side", join.who);
+    const bool host_out = out_space != GPK_MEM_DEVICE;
+    if (right->d.n_geoms == 0) {  // nothing to meet: every count is zero
+        GPK_TRY(zero_counts(out_counts, n, out_space, s));
+        if (out_counts && !host_out) GPK_HIP(hipStreamSynchronize(s));
+        return GPK_OK;
+    }
+
+    gpk_index* tmp_index = nullptr;  // (built before the arenas are carved: the build uses them itself)
+    if (!right_index) {
+        GPK_TRY(gpk_index_build_ex(right, GPK_INDEX_BBOX_GRID, nullptr, stream, &tmp_index));
+        right_index = tmp_index;
+    }
+    auto finish = [&](int32_t rc) {
+        if (tmp_index) {
+            (void)hipStreamSynchronize(s);
+            gpk_index_free(tmp_index);
+        }
+        return rc;
+    };
+    const bool want_payload = out_payload && pair_capacity > 0;
+    const size_t box_bytes = sizeof(double4) * (size_t)n, payload_bytes = cx.payload_elem * (size_t)pair_capacity;
+    int32_t rc = workspace_aux(0).begin((join.boxes ? 2 : 1) * align256(box_bytes) + (want_payload && host_out ? align256(payload_bytes) : 0) + 512);
+    if (rc != GPK_OK) return finish(rc);
+    double4* lbox = (double4*)workspace_aux(0).take(box_bytes);
+    double4* other = join.boxes ? (double4*)workspace_aux(0).take(box_bytes) : nullptr;
+    cx.payload_out = want_payload ? (host_out ? workspace_aux(0).take(payload_bytes) : out_payload) : nullptr;
+    rc = gpk_bounds(left, (double*)lbox, GPK_MEM_DEVICE, stream);
+    if (rc == GPK_OK && join.boxes) rc = join.boxes(&cx, right_index, lbox, other, n, s);
+    if (rc != GPK_OK) return finish(rc);
+
+    CandRefine hook;
+    hook.name = join.who;
+    hook.ctx = &cx;
+    hook.scratch_fixed = 512;
+    hook.scratch_per_cand = (cx.payload_out ? cx.payload_elem : 0) + join.extra_per_cand;
+    hook.refine = join.refine;
+    hook.emitted = payload_emitted;
+    rc = bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, other ? other : lbox, hook);
+    if (rc != GPK_OK) return finish(rc);
+    if (want_payload && host_out && *n_pairs > 0) {
+        const int64_t got = *n_pairs < pair_capacity ? *n_pairs : pair_capacity;
+        rc = copy_out(out_payload, out_space, cx.payload_out, cx.payload_elem * (size_t)got, s);
+    }
+    return finish(rc);
 }
 
 }  // namespace gpk

@@ -1,8 +1,9 @@
 // gpk_candjoin.h — what the joins share: the staged bbox candidate generator of gpk_bboxjoin.hip (bbox_join: candidates per left box from
 // the right side's grid directory, a per-candidate refine, then count / scan / emit of the hits sorted by (l, r)) with its one refine
-// interface, and the host steps every pairs join repeats.  The predicates of gpk_spatial_join refine with the kernels of
-// gpk_bboxjoin.hip; the within-distance join (gpk_dwithin.hip) hands over left boxes grown by its distance and refines every candidate
-// with the library's distance routines.
+// interface, the driver of the joins that return a value per pair (payload_join, gpk_bboxjoin.hip), the host steps every pairs join
+// repeats and those of the row-wise relation calls (rowwise_pairs).  The predicates of gpk_spatial_join refine with the kernels of
+// gpk_bboxjoin.hip; the relation, measure and within-distance joins bring their own refine to payload_join, the last with left boxes
+// grown by its distance.
 #pragma once
 
 #include "gpk_index.h"
@@ -46,6 +47,31 @@ CandRefine polygonal_intersects_refine(BoxRefineCtx* cx);
 CandRefine polygonal_contains_refine(BoxRefineCtx* cx);
 CandRefine lineal_point_refine(BoxRefineCtx* cx);
 
+// ---- joins that return a value per pair -----------------------------------------------------------------------------------------
+// The relation joins (gpk_polyrel.hip, gpk_lineline.hip, gpk_linearea.hip: a uint8 mask), the measure join (gpk_overlay.hip: a double)
+// and the within-distance join (gpk_dwithin.hip: a double) are bbox_join with a payload: the refine leaves one element per CANDIDATE
+// in its scratch — 256 bytes it may use as it likes, then payload[n_cand] — and after the emit the hits' elements are gathered into
+// the caller's buffer, in pair order.  A family's refine context begins with this:
+struct PayloadCtx {
+    const gpk_geoarray *left, *right;
+    const char* gather_label;  // the profile stage of the gather ("gpk_polygon_relation_gather")
+    size_t payload_elem;       // bytes per element: 1 or 8
+    void* payload_out;         // set by payload_join — device: the caller's buffer or its staging; nullptr: no payload asked for
+};
+struct PayloadJoin {
+    const char* who;  // the calling entry point, for error messages
+    PayloadCtx* ctx;  // what the refine and the hook below get as `ctx`
+    decltype(CandRefine::refine) refine;
+    size_t extra_per_cand;  // scratch per candidate behind the payload
+    // nullptr: candidates from the left rows' own boxes.  Otherwise called once `own` (those boxes) is enqueued and the right side's
+    // index exists: it fills `other` (n boxes), which take the left boxes' place in the candidate search.
+    int32_t (*boxes)(PayloadCtx* ctx, const gpk_index* right_index, const double4* own, double4* other, int64_t n, hipStream_t s);
+};
+// Everything such a join does once its arguments are validated: the empty cases, a temporary GPK_INDEX_BBOX_GRID index when the caller
+// has none (freed on every path, after a sync), boxes and payload staging in workspace_aux(0), bbox_join, the payload of a host caller.
+int32_t payload_join(const PayloadJoin& join, const gpk_index* right_index, uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs,
+                     void* out_payload, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
+
 // gpk_join.hip: the join statistics words, or nullptr unless gpk_join_stats_enable(1)
 unsigned long long* join_stats_buffer();
 
@@ -86,6 +112,36 @@ inline int32_t finish_pairs(const char* who, int64_t total, int64_t n, uint32_t*
     if (pair_capacity > 0 && total > pair_capacity)
         return fail(GPK_ERR_CAPACITY, "%s: %lld pairs but capacity %lld", who, (long long)total, (long long)pair_capacity);
     return GPK_OK;
+}
+
+// ---- host steps of a row-wise call over two columns -----------------------------------------------------------------------------
+// What gpk_polygon_relation, gpk_line_relation, gpk_line_polygon_relation and gpk_intersection_measure do after their family check:
+// out[i] (`elem` bytes) for row i of a against row b_rows[i] (or i) of b.  A host caller's `out` and `b_rows` are staged in
+// workspace(); `launch(rows_dev, out_dev, n, s)` enqueues the family's kernel on device pointers.
+template <typename Launch>
+inline int32_t rowwise_pairs(const char* who, const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, void* out, size_t elem,
+                             int32_t out_space, void* stream, Launch launch) {
+    const int64_t n = a->d.n_geoms;
+    if (!b_rows && n != b->d.n_geoms)
+        return fail(GPK_ERR_INVALID_ARGUMENT, "%s: row counts differ (%lld vs %lld)", who, (long long)n, (long long)b->d.n_geoms);
+    GPK_TRY(require_device());
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) return GPK_OK;
+    const uint32_t* rows_dev = b_rows;
+    void* out_dev = out;
+    const size_t ob = elem * (size_t)n;
+    if (out_space != GPK_MEM_DEVICE) {
+        const size_t rb = sizeof(uint32_t) * (size_t)n;
+        GPK_TRY(workspace().begin(align256(ob) + (b_rows ? align256(rb) : 0) + 512));
+        out_dev = workspace().take(ob);
+        if (b_rows) {
+            uint32_t* r = (uint32_t*)workspace().take(rb);
+            GPK_HIP(hipMemcpyAsync(r, b_rows, rb, hipMemcpyHostToDevice, s));
+            rows_dev = r;
+        }
+    }
+    GPK_TRY(launch(rows_dev, out_dev, n, s));
+    return copy_out(out, out_space, out_dev, ob, s);
 }
 
 }  // namespace gpk

@@ -176,10 +176,20 @@ bool debug_sync();  // GPK_DEBUG_SYNC=1: name every launch on stderr and wait fo
 
 int32_t require_device();  // GPK_ERR_DEVICE unless the current device is a gfx950
 int cu_count();
+// The grid of a kernel that gives G lanes of a 256-lane block to a unit (a row, a candidate pair, a sequence) and loops: one block per
+// 256 / G units, capped at 32 blocks a compute unit, at least one.
+inline dim3 group_grid(int64_t n_units, int G) {
+    const int64_t per_block = 256 / G;
+    int64_t blocks = (n_units + per_block - 1) / per_block;
+    const int64_t cap = (int64_t)cu_count() * 32;
+    if (blocks > cap) blocks = cap;
+    return dim3((unsigned)(blocks > 0 ? blocks : 1));
+}
 
 // copy helpers honouring the ABI's memory-space tags
 int32_t copy_out(void* dst, int32_t dst_space, const void* src_dev, size_t bytes, hipStream_t s);
 
 __host__ __device__ inline bool is_polygonal(int32_t t) { return t == GPK_GEOM_POLYGON || t == GPK_GEOM_MULTIPOLYGON; }
+__host__ __device__ inline bool is_lineal(int32_t t) { return t == GPK_GEOM_LINESTRING || t == GPK_GEOM_MULTILINESTRING; }
 
 }  // namespace gpk

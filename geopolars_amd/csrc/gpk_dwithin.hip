@@ -16,6 +16,8 @@
 //      These are the routines, group sizes and lane orders of gpk_distance_rowwise's per-row kernels, so d is bit for bit the double
 //      that call returns for the pair, and the pair test is a comparison of that double with `distance`.
 //   4. emit: the generator's count / scan / emit of the hits, plus a gather of the hits' distances for out_dist.
+// Steps 2 and 4 and the host work around them (temporary index, arenas, copies) are payload_join (gpk_candjoin.h); this file brings the
+// grown boxes (dwithin_boxes) and the refine.
 //
 // Margin.  The candidate set must contain every pair whose COMPUTED distance is <= distance although boxes, cell function and distances
 // are rounded.  Let D be the exact distance of a pair and d the computed one: |d - D| <= 16 u (D + 2 lmax) (the distance routines'
@@ -176,20 +178,6 @@ __global__ __launch_bounds__(256) void dwithin_pair_large_kernel(DevGeo ga, DevG
     }
 }
 
-// out_dist: the distances of row i's hits, in candidate order, at the row's offset of the output
-__global__ __launch_bounds__(256) void dwithin_gather_kernel(int64_t n_rows, const int32_t* __restrict__ cand_off, const uint8_t* __restrict__ hit,
-                                                             const int32_t* __restrict__ offsets, const double* __restrict__ dist,
-                                                             double* __restrict__ out, int64_t capacity) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    int64_t o = offsets[i];
-    for (int c = cand_off[i]; c < cand_off[i + 1]; ++c) {
-        if (!hit[c]) continue;
-        if (o < capacity) out[o] = dist[c];
-        ++o;
-    }
-}
-
 // row-wise: the distance kernels' answer against the threshold; null, out-of-range, empty and NaN-point rows never match
 __global__ __launch_bounds__(256) void dwithin_threshold_kernel(DevGeo a, DevGeo b, const uint32_t* __restrict__ rows, const double* __restrict__ d,
                                                                 double t, int64_t n, uint8_t* __restrict__ out) {
@@ -201,11 +189,10 @@ __global__ __launch_bounds__(256) void dwithin_threshold_kernel(DevGeo a, DevGeo
 }
 
 struct DwCtx {
-    const gpk_geoarray *left, *right;
-    const double4 *lbox, *rbox;
+    PayloadCtx p;  // (p.payload_out: the distances were asked for)
     double t;
-    double* dist_out;  // device: out_dist itself or its staging; nullptr: no distances asked for
     bool pair_kernels;
+    const double4 *lbox, *rbox;  // set by dwithin_boxes
 };
 // scratch of a call: 256 bytes of counters (word 0: listed candidates), then dist[n_cand] (when asked for), then the list [n_cand]
 struct DwScratch {
@@ -218,23 +205,15 @@ DwScratch carve(const DwCtx& cx, void* scratch, int64_t n_cand) {
     DwScratch sc;
     sc.n_large = (uint32_t*)p;
     p += 256;
-    sc.dist = cx.dist_out ? (double*)p : nullptr;
-    if (cx.dist_out) p += sizeof(double) * (size_t)n_cand;
+    sc.dist = cx.p.payload_out ? (double*)p : nullptr;
+    if (cx.p.payload_out) p += sizeof(double) * (size_t)n_cand;
     sc.large = cx.pair_kernels ? (uint32_t*)p : nullptr;
     return sc;
 }
 
-dim3 refine_grid(int64_t n_cand, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n_cand + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
-
 template <int KIND>
 int32_t launch_point_refine(int G, const DevGeo& pts, const DevGeo& other, bool point_left, const Cands& cs, hipStream_t s) {
-    const dim3 grid = refine_grid(cs.n, G);
+    const dim3 grid = group_grid(cs.n, G);
     if (G == 1)
         GPK_LAUNCH("gpk_dwithin_refine", (dwithin_point_refine_kernel<1, KIND>), grid, dim3(256), 0, s, pts, other, point_left, cs);
     else if (G == 8)
@@ -247,7 +226,7 @@ int32_t launch_point_refine(int G, const DevGeo& pts, const DevGeo& other, bool 
 template <int KA, int KB>
 int32_t launch_pair_refine(const DevGeo& ga, const DevGeo& gb, bool swapped, const Cands& cs, uint32_t* large, uint32_t* n_large, hipStream_t s) {
     const int G = pairdist_group_size(ga, gb);
-    const dim3 grid = refine_grid(cs.n, G);
+    const dim3 grid = group_grid(cs.n, G);
     if (G == 8)
         GPK_LAUNCH("gpk_dwithin_refine", (dwithin_pair_refine_kernel<8, KA, KB>), grid, dim3(256), 0, s, ga, gb, swapped, cs, large, n_large);
     else
@@ -264,7 +243,7 @@ int32_t dwithin_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r
     const DwCtx& cx = *(const DwCtx*)ctx;
     const DwScratch sc = carve(cx, scratch, n_cand);
     const Cands cs{cand_l, cand_r, (int64_t)n_cand, cx.lbox, cx.rbox, cx.t, hit, sc.dist, stats};
-    const DevGeo &L = cx.left->d, &R = cx.right->d;
+    const DevGeo &L = cx.p.left->d, &R = cx.p.right->d;
     if (L.type == GPK_GEOM_POINT || R.type == GPK_GEOM_POINT) {
         // the POINT column takes the point's place (the left one when both are), as in gpk_distance_rowwise
         const bool point_left = L.type == GPK_GEOM_POINT;
@@ -296,13 +275,15 @@ int32_t dwithin_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r
     return fail(GPK_ERR_MISMATCHED_GEOMETRY, "dwithin_join: no kernel for geometry types %d, %d", L.type, R.type);
 }
 
-int32_t dwithin_emitted(void* ctx, int64_t n_rows, const int32_t* cand_off, const uint8_t* hit, const int32_t* offsets, void* scratch,
-                        int64_t pair_capacity, hipStream_t s) {
-    const DwCtx& cx = *(const DwCtx*)ctx;
-    if (!cx.dist_out) return GPK_OK;
-    const double* dist = (const double*)((const char*)scratch + 256);
-    GPK_LAUNCH("gpk_dwithin_gather", dwithin_gather_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, n_rows, cand_off, hit, offsets,
-               dist, cx.dist_out, pair_capacity);
+// the left boxes of the candidate search: the rows' own boxes grown by the distance and the margin (see the top of the file)
+int32_t dwithin_boxes(PayloadCtx* ctx, const gpk_index* right_index, const double4* own, double4* grown, int64_t n, hipStream_t s) {
+    DwCtx& cx = *(DwCtx*)ctx;
+    cx.lbox = own;
+    cx.rbox = right_index->v.bbox;
+    // the magnitude the margin scales with: the directory's origin and extent (an axis of zero extent has inv = 0: one column / row)
+    const GridParams& h = right_index->host_grid;
+    const double scale = fabs(h.x0) + fabs(h.y0) + (h.inv_w > 0.0 ? (double)h.gx / h.inv_w : 0.0) + (h.inv_h > 0.0 ? (double)h.gy / h.inv_h : 0.0);
+    GPK_LAUNCH("gpk_dwithin_grow", dwithin_grow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, own, n, cx.t, scale, grown);
     return GPK_OK;
 }
 
@@ -328,57 +309,10 @@ extern "C" int32_t gpk_dwithin_join(const gpk_geoarray* left, const gpk_geoarray
     if (!dwithin_family(left->d.type) || !dwithin_family(right->d.type))
         return fail(GPK_ERR_MISMATCHED_GEOMETRY, "dwithin_join: unsupported geometry types %d, %d", left->d.type, right->d.type);
     if (right_index) GPK_TRY(index_matches_with_grid(right_index, right, "dwithin_join"));
-    GPK_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n = left->d.n_geoms;
-    if (n == 0) return GPK_OK;
-    if (n > (int64_t)INT32_MAX) return fail(GPK_ERR_INVALID_ARGUMENT, "dwithin_join: more than 2^31 - 1 left rows: shard the left side");
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    if (right->d.n_geoms == 0) {  // nothing to meet: every count is zero
-        GPK_TRY(zero_counts(out_counts, n, out_space, s));
-        if (out_counts && !host_out) GPK_HIP(hipStreamSynchronize(s));
-        return GPK_OK;
-    }
-
-    gpk_index* tmp_index = nullptr;  // (built before the arenas are carved: the build uses them itself)
-    if (!right_index) {
-        GPK_TRY(gpk_index_build_ex(right, GPK_INDEX_BBOX_GRID, nullptr, stream, &tmp_index));
-        right_index = tmp_index;
-    }
-    auto done = [&](int32_t rc) {
-        if (tmp_index) {
-            (void)hipStreamSynchronize(s);
-            gpk_index_free(tmp_index);
-        }
-        return rc;
-    };
-    const bool want_dist = out_dist && pair_capacity > 0;
-    const size_t box_bytes = sizeof(double4) * (size_t)n, dist_bytes = sizeof(double) * (size_t)pair_capacity;
-    int32_t rc = workspace_aux(0).begin(2 * align256(box_bytes) + (want_dist && host_out ? align256(dist_bytes) : 0) + 512);
-    if (rc != GPK_OK) return done(rc);
-    double4* lbox = (double4*)workspace_aux(0).take(box_bytes);
-    double4* grown = (double4*)workspace_aux(0).take(box_bytes);
-    double* dist_dev = want_dist ? (host_out ? (double*)workspace_aux(0).take(dist_bytes) : out_dist) : nullptr;
-    rc = gpk_bounds(left, (double*)lbox, GPK_MEM_DEVICE, stream);
-    if (rc != GPK_OK) return done(rc);
-    // the magnitude the margin scales with: the directory's origin and extent (an axis of zero extent has inv = 0: one column / row)
-    const GridParams& h = right_index->host_grid;
-    const double scale = fabs(h.x0) + fabs(h.y0) + (h.inv_w > 0.0 ? (double)h.gx / h.inv_w : 0.0) + (h.inv_h > 0.0 ? (double)h.gy / h.inv_h : 0.0);
-    GPK_LAUNCH_OR(done, "gpk_dwithin_grow", dwithin_grow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double4*)lbox, n, distance,
-                  scale, grown);
-
-    DwCtx cx{left, right, lbox, right_index->v.bbox, distance, dist_dev, left->d.type != GPK_GEOM_POINT && right->d.type != GPK_GEOM_POINT};
-    CandRefine hook;
-    hook.name = "dwithin_join";
-    hook.ctx = &cx;
-    hook.scratch_fixed = 512;
-    hook.scratch_per_cand = (dist_dev ? sizeof(double) : 0) + (cx.pair_kernels ? sizeof(uint32_t) : 0);
-    hook.refine = dwithin_refine;
-    hook.emitted = dwithin_emitted;
-    rc = bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, grown, hook);
-    if (rc != GPK_OK) return done(rc);
-    if (want_dist && host_out && *n_pairs > 0) rc = copy_out(out_dist, out_space, dist_dev, sizeof(double) * (size_t)*n_pairs, s);
-    return done(rc);
+    DwCtx cx{{left, right, "gpk_dwithin_gather", sizeof(double), nullptr}, distance,
+             left->d.type != GPK_GEOM_POINT && right->d.type != GPK_GEOM_POINT, nullptr, nullptr};
+    const PayloadJoin join{"dwithin_join", &cx.p, dwithin_refine, cx.pair_kernels ? sizeof(uint32_t) : 0, dwithin_boxes};
+    return payload_join(join, right_index, left_row_base, out_counts, out_pairs, out_dist, pair_capacity, n_pairs, out_space, stream);
 }
 
 extern "C" int32_t gpk_dwithin_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double distance, uint8_t* out,

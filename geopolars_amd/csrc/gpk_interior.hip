@@ -426,13 +426,6 @@ int group_size(const DevGeo& a) {
     const double m = a.n_geoms > 0 ? (double)a.n_coords / (double)a.n_geoms : 0.0;
     return m >= ip::INT_G_MEAN ? ip::INT_G_LARGE : ip::INT_G_SMALL;
 }
-dim3 group_grid(int64_t n, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
 
 int32_t run(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, double* out_width, int32_t out_space, hipStream_t s) {
     const DevGeo& g = a->d;

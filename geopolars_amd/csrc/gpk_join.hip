@@ -1770,8 +1770,7 @@ int32_t gpk_spatial_join(const gpk_geoarray* left, const gpk_geoarray* right, co
         return swapped_pip_join(left, right, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s);
     // polygonal pairs: `intersects` (:102-104,112-123) and `contains` with a POLYGON on the right (:99-101,107-111) have arms
     const bool polypoly_arm = polypoly && (predicate == GPK_PRED_INTERSECTS || (predicate == GPK_PRED_CONTAINS && right->d.type == GPK_GEOM_POLYGON));
-    auto lineal = [](int32_t t) { return t == GPK_GEOM_LINESTRING || t == GPK_GEOM_MULTILINESTRING; };
-    const bool lineal_point = (left->d.type == GPK_GEOM_POINT && lineal(right->d.type)) || (lineal(left->d.type) && right->d.type == GPK_GEOM_POINT);
+    const bool lineal_point = (left->d.type == GPK_GEOM_POINT && is_lineal(right->d.type)) || (is_lineal(left->d.type) && right->d.type == GPK_GEOM_POINT);
     if (!pip && !polypoly_arm && !lineal_point)  // `_ => false` (spatial_index.rs:136): an empty join, not an error
         return zero_counts(out_counts, left->d.n_geoms, out_space, s);
 

@@ -229,14 +229,6 @@ __global__ __launch_bounds__(256) void rdp_compact_kernel(const double2* __restr
     }
 }
 
-static inline dim3 group_grid(int64_t n_items, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n_items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
-
 }  // namespace gpk
 
 using namespace gpk;

@@ -169,8 +169,6 @@ __global__ __launch_bounds__(256) void interpolate_point_kernel(DevGeo lines, co
     }
 }
 
-bool is_lineal(int t) { return t == GPK_GEOM_LINESTRING || t == GPK_GEOM_MULTILINESTRING; }
-
 dim3 tile_grid(int64_t n) {
     int64_t n_tiles = (n + LINREF_TILE - 1) / LINREF_TILE;
     if (n_tiles > (int64_t)cu_count() * 16) n_tiles = (int64_t)cu_count() * 16;
@@ -308,9 +306,7 @@ int32_t gpk_line_interpolate_point(const gpk_geoarray* lines, const double* dist
     }
     const int64_t stride = broadcast ? 0 : 1;
     const int G = distance_group_size(lines->d);
-    int64_t blocks = (n + 256 / G - 1) / (256 / G);
-    if (blocks > (int64_t)cu_count() * 32) blocks = (int64_t)cu_count() * 32;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid = group_grid(n, G), block(256);  // (n > 0 here: the helper never gives an empty grid)
 #define LI_LAUNCH(GG, KK) \
     GPK_LAUNCH("gpk_line_interpolate_point", (interpolate_point_kernel<GG>), grid, block, 0, s, lines->d, dist_dev, stride, scalar, (int)normalized, xy_dev, valid_dev)
     LINREF_BY_G(LI_LAUNCH, 0);

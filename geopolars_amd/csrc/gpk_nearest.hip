@@ -276,18 +276,10 @@ static NearGrid near_grid_of(const gpk_index* ix) {
     return g;
 }
 
-static dim3 nearest_grid_dim(int64_t n, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
-
 template <int KIND>
 static int32_t launch_best(int G, const NearPts& pts, const DevGeo& right, const NearDir& ix, const NearGrid& g, double max_d, double* best_d,
                            uint32_t* best_r, int32_t* cnt, hipStream_t s) {
-    const dim3 grid = nearest_grid_dim(pts.n, G);
+    const dim3 grid = group_grid(pts.n, G);
     if (G == 1)
         GPK_LAUNCH("gpk_nearest_best", (nearest_best_kernel<1, KIND>), grid, dim3(256), 0, s, pts, right, ix, g, max_d, best_d, best_r, cnt);
     else if (G == 8)
@@ -299,7 +291,7 @@ static int32_t launch_best(int G, const NearPts& pts, const DevGeo& right, const
 template <int KIND>
 static int32_t launch_emit(int G, const NearPts& pts, const DevGeo& right, const NearDir& ix, const NearGrid& g, const double* best_d,
                            const uint32_t* best_r, const int32_t* cnt, const int32_t* off, uint32_t base, uint32_t* pairs, double* dist, hipStream_t s) {
-    const dim3 grid = nearest_grid_dim(pts.n, G);
+    const dim3 grid = group_grid(pts.n, G);
     if (G == 1)
         GPK_LAUNCH("gpk_nearest_emit", (nearest_emit_kernel<1, KIND>), grid, dim3(256), 0, s, pts, right, ix, g, best_d, best_r, cnt, off, base, pairs, dist);
     else if (G == 8)

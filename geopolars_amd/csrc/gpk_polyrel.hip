@@ -9,6 +9,9 @@
 // lanes per CANDIDATE, A = the left row and B = the right row, and writes hit = predicate(mask).  When the caller asks for the per-pair
 // masks the full mask is computed and gathered after the emit; otherwise the work on a pair ends as soon as its predicate is settled
 // (pp::stop_of).  `left` and `right` may be one array: a pair (i, i) is a candidate like any other.
+//
+// The host steps around the kernels are shared (gpk_candjoin.h): rowwise_pairs stages a host caller's buffers for the row-wise call,
+// payload_join runs the join (temporary index, boxes, bbox_join, the gather of the per-pair values) around this file's refine.
 #include "gpk_candjoin.h"
 #include "gpk_device.h"
 #include "gpk_polyrel.h"
@@ -30,9 +33,8 @@ __global__ __launch_bounds__(256) void polygon_relation_rowwise_kernel(DevGeo a,
 }
 
 struct PpCtx {
-    const gpk_geoarray *left, *right;
+    PayloadCtx p;  // (p.payload_out: the masks were asked for)
     int32_t predicate;
-    uint8_t* mask_out;  // device: out_mask itself or its staging; nullptr: no masks asked for
 };
 
 // G lanes per candidate
@@ -51,35 +53,13 @@ __global__ __launch_bounds__(256) void polygon_relation_refine_kernel(DevGeo lef
     }
 }
 
-// out_mask: the masks of row i's hits, in candidate order, at the row's offset of the output
-__global__ __launch_bounds__(256) void polygon_relation_gather_kernel(int64_t n_rows, const int32_t* __restrict__ cand_off,
-                                                                      const uint8_t* __restrict__ hit, const int32_t* __restrict__ offsets,
-                                                                      const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, int64_t capacity) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    int64_t o = offsets[i];
-    for (int c = cand_off[i]; c < cand_off[i + 1]; ++c) {
-        if (!hit[c]) continue;
-        if (o < capacity) out[o] = mask[c];
-        ++o;
-    }
-}
-
-dim3 group_grid(int64_t n, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
-
 // scratch of a call: 256 bytes unused, then mask[n_cand] when the masks were asked for
 int32_t pp_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r, int32_t n_cand, void* scratch, uint8_t* hit, unsigned long long* stats,
                   hipStream_t s) {
     (void)stats;
     const PpCtx& cx = *(const PpCtx*)ctx;
-    const DevGeo &left = cx.left->d, &right = cx.right->d;
-    uint8_t* mask = cx.mask_out ? (uint8_t*)scratch + 256 : nullptr;
+    const DevGeo &left = cx.p.left->d, &right = cx.p.right->d;
+    uint8_t* mask = cx.p.payload_out ? (uint8_t*)scratch + 256 : nullptr;
     const pp::Stop st = mask ? pp::Stop{0, pp::PP_ALL} : pp::stop_of(cx.predicate);
     const int G = pp::relation_group_size(left, right);
     const dim3 grid = group_grid(n_cand, G);
@@ -89,15 +69,6 @@ int32_t pp_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r, int
     else
         GPK_LAUNCH("gpk_polygon_relation_refine", (polygon_relation_refine_kernel<lp::LP_G_LARGE>), grid, dim3(256), 0, s, left, right, cand_l, cand_r,
                    (int64_t)n_cand, (int)cx.predicate, st, hit, mask);
-    return GPK_OK;
-}
-
-int32_t pp_emitted(void* ctx, int64_t n_rows, const int32_t* cand_off, const uint8_t* hit, const int32_t* offsets, void* scratch,
-                   int64_t pair_capacity, hipStream_t s) {
-    const PpCtx& cx = *(const PpCtx*)ctx;
-    if (!cx.mask_out) return GPK_OK;
-    GPK_LAUNCH("gpk_polygon_relation_gather", polygon_relation_gather_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, n_rows, cand_off,
-               hit, offsets, (const uint8_t*)scratch + 256, cx.mask_out, pair_capacity);
     return GPK_OK;
 }
 
@@ -113,31 +84,18 @@ extern "C" int32_t gpk_polygon_relation(const gpk_geoarray* a, const gpk_geoarra
     if (!is_polygonal(a->d.type) || !is_polygonal(b->d.type))
         return fail(GPK_ERR_MISMATCHED_GEOMETRY, "polygon_relation: POLYGON | MULTIPOLYGON x POLYGON | MULTIPOLYGON (found types %d, %d)", a->d.type,
                     b->d.type);
-    const int64_t n = a->d.n_geoms;
-    if (!b_rows && n != b->d.n_geoms)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "polygon_relation: row counts differ (%lld vs %lld)", (long long)n, (long long)b->d.n_geoms);
-    GPK_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) return GPK_OK;
-    const uint32_t* rows_dev = b_rows;
-    uint8_t* out_dev = out_mask;
-    if (out_space != GPK_MEM_DEVICE) {
-        const size_t rb = sizeof(uint32_t) * (size_t)n;
-        GPK_TRY(workspace().begin(align256((size_t)n) + (b_rows ? align256(rb) : 0) + 512));
-        out_dev = (uint8_t*)workspace().take((size_t)n);
-        if (b_rows) {
-            uint32_t* r = (uint32_t*)workspace().take(rb);
-            GPK_HIP(hipMemcpyAsync(r, b_rows, rb, hipMemcpyHostToDevice, s));
-            rows_dev = r;
-        }
-    }
-    const int G = pp::relation_group_size(a->d, b->d);
-    const dim3 grid = group_grid(n, G);
-    if (G == lp::LP_G_SMALL)
-        GPK_LAUNCH("gpk_polygon_relation", (polygon_relation_rowwise_kernel<lp::LP_G_SMALL>), grid, dim3(256), 0, s, a->d, b->d, rows_dev, n, out_dev);
-    else
-        GPK_LAUNCH("gpk_polygon_relation", (polygon_relation_rowwise_kernel<lp::LP_G_LARGE>), grid, dim3(256), 0, s, a->d, b->d, rows_dev, n, out_dev);
-    return copy_out(out_mask, out_space, out_dev, (size_t)n, s);
+    auto launch = [&](const uint32_t* rows_dev, void* out_dev, int64_t n, hipStream_t s) -> int32_t {
+        const int G = pp::relation_group_size(a->d, b->d);
+        const dim3 grid = group_grid(n, G);
+        if (G == lp::LP_G_SMALL)
+            GPK_LAUNCH("gpk_polygon_relation", (polygon_relation_rowwise_kernel<lp::LP_G_SMALL>), grid, dim3(256), 0, s, a->d, b->d, rows_dev, n,
+                       (uint8_t*)out_dev);
+        else
+            GPK_LAUNCH("gpk_polygon_relation", (polygon_relation_rowwise_kernel<lp::LP_G_LARGE>), grid, dim3(256), 0, s, a->d, b->d, rows_dev, n,
+                       (uint8_t*)out_dev);
+        return GPK_OK;
+    };
+    return rowwise_pairs("polygon_relation", a, b, b_rows, out_mask, 1, out_space, stream, launch);
 }
 
 extern "C" int32_t gpk_polygon_relation_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
@@ -152,49 +110,7 @@ extern "C" int32_t gpk_polygon_relation_join(const gpk_geoarray* left, const gpk
         return fail(GPK_ERR_MISMATCHED_GEOMETRY, "polygon_relation_join: both sides POLYGON | MULTIPOLYGON (found types %d, %d)", left->d.type,
                     right->d.type);
     if (right_index) GPK_TRY(index_matches_with_grid(right_index, right, "polygon_relation_join"));
-    GPK_TRY(require_device());
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n = left->d.n_geoms;
-    if (n == 0) return GPK_OK;
-    if (n > (int64_t)INT32_MAX) return fail(GPK_ERR_INVALID_ARGUMENT, "polygon_relation_join: more than 2^31 - 1 left rows: shard the left side");
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    if (right->d.n_geoms == 0) {  // nothing to meet: every count is zero
-        GPK_TRY(zero_counts(out_counts, n, out_space, s));
-        if (out_counts && !host_out) GPK_HIP(hipStreamSynchronize(s));
-        return GPK_OK;
-    }
-
-    gpk_index* tmp_index = nullptr;  // (built before the arenas are carved: the build uses them itself)
-    if (!right_index) {
-        GPK_TRY(gpk_index_build_ex(right, GPK_INDEX_BBOX_GRID, nullptr, stream, &tmp_index));
-        right_index = tmp_index;
-    }
-    auto finish = [&](int32_t rc) {
-        if (tmp_index) {
-            (void)hipStreamSynchronize(s);
-            gpk_index_free(tmp_index);
-        }
-        return rc;
-    };
-    const bool want_mask = out_mask && pair_capacity > 0;
-    const size_t box_bytes = sizeof(double4) * (size_t)n, mask_bytes = (size_t)pair_capacity;
-    int32_t rc = workspace_aux(0).begin(align256(box_bytes) + (want_mask && host_out ? align256(mask_bytes) : 0) + 512);
-    if (rc != GPK_OK) return finish(rc);
-    double4* lbox = (double4*)workspace_aux(0).take(box_bytes);
-    uint8_t* mask_dev = want_mask ? (host_out ? (uint8_t*)workspace_aux(0).take(mask_bytes) : out_mask) : nullptr;
-    rc = gpk_bounds(left, (double*)lbox, GPK_MEM_DEVICE, stream);
-    if (rc != GPK_OK) return finish(rc);
-
-    PpCtx cx{left, right, predicate, mask_dev};
-    CandRefine hook;
-    hook.name = "polygon_relation_join";
-    hook.ctx = &cx;
-    hook.scratch_fixed = 512;
-    hook.scratch_per_cand = mask_dev ? 1 : 0;
-    hook.refine = pp_refine;
-    hook.emitted = pp_emitted;
-    rc = bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, lbox, hook);
-    if (rc != GPK_OK) return finish(rc);
-    if (want_mask && host_out && *n_pairs > 0) rc = copy_out(out_mask, out_space, mask_dev, (size_t)*n_pairs, s);
-    return finish(rc);
+    PpCtx cx{{left, right, "gpk_polygon_relation_gather", sizeof(uint8_t), nullptr}, predicate};
+    return payload_join(PayloadJoin{"polygon_relation_join", &cx.p, pp_refine, 0, nullptr}, right_index, left_row_base, out_counts, out_pairs, out_mask,
+                        pair_capacity, n_pairs, out_space, stream);
 }

@@ -523,16 +523,6 @@ __global__ void fill_u8_kernel(uint8_t* out, int64_t n, uint8_t v) {
     if (i < n) out[i] = v;
 }
 
-// ---- host side -----------------------------------------------------------------------------------
-static dim3 coop_grid(int64_t n_rows, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n_rows + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
-
-
 // ---- row map: the rows of a point column ordered for the grouped distance kernel ---------------------------------------
 }  // namespace gpk
 struct gpk_rowmap {
@@ -864,7 +854,6 @@ int32_t gpk_predicate_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, cons
 
     // contains(a, b): a polygonal, b point -> Inside.  within(a, b) == contains(b, a): a point, b polygonal.
     // intersects: either order, boundary counts.
-    auto is_lineal = [](int t) { return t == GPK_GEOM_LINESTRING || t == GPK_GEOM_MULTILINESTRING; };
     const bool a_poly_b_pt = is_polygonal(ta) && tb == GPK_GEOM_POINT;
     const bool a_pt_b_poly = ta == GPK_GEOM_POINT && is_polygonal(tb);
     bool run_pp = false, boundary = false, rows_index_polys = false;
@@ -882,7 +871,7 @@ int32_t gpk_predicate_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, cons
         polys = a_pt_b_poly ? b : a;
         rows_index_polys = a_pt_b_poly;  // b_rows indexes b; b is the polygon side when a is the point side
         const int G = pick_group_rows(polys->d);
-        const dim3 grid = coop_grid(n, G);
+        const dim3 grid = group_grid(n, G);
 #define PP(GG)                                                                                                       \
     GPK_LAUNCH("gpk_point_poly_predicate", point_poly_predicate_kernel<GG>, grid, block, 0, s, pts->d, polys->d,    \
                rows_dev, rows_index_polys, boundary, out_dev, n)
@@ -897,11 +886,11 @@ int32_t gpk_predicate_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, cons
         }
 #undef PP
     } else if (predicate == GPK_PRED_INTERSECTS && is_polygonal(ta) && is_polygonal(tb)) {
-        GPK_LAUNCH("gpk_poly_poly_intersects", poly_poly_intersects_kernel, coop_grid(n, PP_GS), block, 0, s, a->d, b->d, rows_dev, out_dev);
+        GPK_LAUNCH("gpk_poly_poly_intersects", poly_poly_intersects_kernel, group_grid(n, PP_GS), block, 0, s, a->d, b->d, rows_dev, out_dev);
     } else if (ta == GPK_GEOM_POINT && tb == GPK_GEOM_POINT) {
         GPK_LAUNCH("gpk_point_point_equal", point_point_equal_kernel, flat, block, 0, s, a->d, b->d, rows_dev, out_dev);
     } else if (is_polygonal(ta) && is_polygonal(tb)) {  // contains / within
-        GPK_LAUNCH("gpk_poly_poly_contains", poly_poly_contains_kernel, coop_grid(n, PP_GS), block, 0, s, a->d, b->d, rows_dev,
+        GPK_LAUNCH("gpk_poly_poly_contains", poly_poly_contains_kernel, group_grid(n, PP_GS), block, 0, s, a->d, b->d, rows_dev,
                    predicate == GPK_PRED_WITHIN, out_dev);
     } else if ((predicate == GPK_PRED_CONTAINS && is_lineal(ta) && tb == GPK_GEOM_POINT) ||
                (predicate == GPK_PRED_WITHIN && ta == GPK_GEOM_POINT && is_lineal(tb))) {

@@ -635,7 +635,7 @@ __global__ void length_combine_kernel(DevGeo a, const double* __restrict__ stats
             dev::part_rings(a, p, r0, r1);
             if (r1 > r0) v += stats[ST_LEN * n_seq + r0];
         }
-    } else if (a.type == GPK_GEOM_LINESTRING || a.type == GPK_GEOM_MULTILINESTRING) {
+    } else if (is_lineal(a.type)) {
         int s0, s1;
         geom_seq_range(a, g, s0, s1);
         for (int s = s0; s < s1; ++s) v += stats[ST_LEN * n_seq + s];

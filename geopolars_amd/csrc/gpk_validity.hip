@@ -190,14 +190,6 @@ __global__ __launch_bounds__(val::VAL_BLOCK_THREADS) void validity_big_kernel(De
     }
 }
 
-dim3 group_grid(int64_t n, int G) {
-    const int64_t per_block = 256 / G;
-    int64_t blocks = (n + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count() * 32;
-    if (blocks > cap) blocks = cap;
-    return dim3((unsigned)(blocks > 0 ? blocks : 1));
-}
-
 template <bool POLY>
 int32_t run(const gpk_geoarray* a, uint8_t* out_code, int32_t* out_where, int32_t out_space, hipStream_t s) {
     const DevGeo& g = a->d;

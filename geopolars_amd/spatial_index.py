@@ -437,6 +437,61 @@ def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = N
     return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
 
 
+# ---- what the joins with a value per pair share (dwithin, the three relation joins, the intersection measure) --------------------------
+# Their ABI calls have one shape: (left, right, index, <one family argument>, left_row_base, counts, pairs, payload, capacity, n_pairs,
+# space, stream).  The public functions below validate their own argument, then go through these.
+
+
+def _payload_pairs(abi_name: str, left: GeoSeries, right: GeoSeries, r_index: Optional[SpatialIndex], arg, left_row_base: int, payload=np.float64):
+    """host buffers: (pairs, counts, per-pair payload of dtype `payload`), the pair buffer sized like join_pairs'"""
+    fn = getattr(_abi.lib(), abi_name)
+    n = len(left)
+    counts = np.zeros(n, dtype=np.uint32)
+    rh = r_index.handle if r_index is not None else None
+    call = lambda pairs_ptr, payload_ptr, capacity, n_pairs: fn(  # noqa: E731
+        left.device().handle, right.device().handle, rh, arg, left_row_base, counts.ctypes.data, pairs_ptr, payload_ptr, capacity, n_pairs, MEM_HOST, None)
+    pairs, values = _pairs_with_retry(n, call, want_dist=True, payload=payload)
+    return pairs, counts, values
+
+
+def _payload_pairs_device(abi_name: str, left: DeviceGeoArray, right: DeviceGeoArray, r_index: Optional[SpatialIndex], arg, out_counts, out_pairs,
+                          out_payload, left_row_base: int, stream: int) -> int:
+    """device buffers, filled in place on `stream`: the number of pairs"""
+    n_pairs = C.c_int64(0)
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(getattr(_abi.lib(), abi_name)(
+        left.handle, right.handle, rh, arg, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_payload), cap, C.byref(n_pairs), MEM_DEVICE, stream))
+    return int(n_pairs.value)
+
+
+def _payload_table_join(what: str, lhs, rhs, options, family_arg, pairs_fn, value_col: Optional[str] = None, relation_col: Optional[str] = None):
+    """The table joins over `pairs_fn(left, right, arg, r_index)`: `what` prefixes the join_type message, `family_arg()` checks the
+    family's own options (before a geometry column is decoded) and returns the argument.  The payload becomes the float64 `value_col`
+    or the nullable uint8 `relation_col` (null for an unmatched left row)."""
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{what}: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    arg = family_arg()
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, values = pairs_fn(lgeo, rgeo, arg, options.r_index)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, value_col, values)
+    if relation_col is not None:
+        import pyarrow as pa
+
+        matched = ri >= 0
+        m = np.zeros(len(ri), dtype=np.uint8)
+        m[matched] = values
+        table = table.append_column(relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
+    return table
+
+
+def _known_predicate(what: str, predicate: str, table: dict) -> str:
+    if predicate not in table:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{what}: unknown predicate {predicate!r}: one of {sorted(table)}")
+    return predicate
+
+
 # ---- within-distance join (gpk_dwithin_join) ------------------------------------------------------------------------------------
 
 
@@ -465,14 +520,7 @@ def dwithin_pairs(
     counts (n_left,) uint32, distances (H,) float64 — the doubles GeoSeries.distance returns for the pairs).  Host-buffer variant: the
     pair buffer is sized like join_pairs'."""
     d = dwithin_distance_arg(distance)
-    lib = _abi.lib()
-    n = len(left)
-    counts = np.zeros(n, dtype=np.uint32)
-    rh = r_index.handle if r_index is not None else None
-    call = lambda pairs_ptr, dist_ptr, capacity, n_pairs: lib.gpk_dwithin_join(  # noqa: E731
-        left.device().handle, right.device().handle, rh, d, left_row_base, counts.ctypes.data, pairs_ptr, dist_ptr, capacity, n_pairs, MEM_HOST, None)
-    pairs, dist = _pairs_with_retry(n, call, want_dist=True)
-    return pairs, counts, dist
+    return _payload_pairs("gpk_dwithin_join", left, right, r_index, d, left_row_base)
 
 
 def dwithin_pairs_device(
@@ -489,11 +537,7 @@ def dwithin_pairs_device(
     """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_dist (cap,) float64 torch CUDA tensors (any
     may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
     d = dwithin_distance_arg(distance)
-    n_pairs = C.c_int64(0)
-    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
-    _abi.check(_abi.lib().gpk_dwithin_join(
-        left.handle, right.handle, rh, d, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_dist), cap, C.byref(n_pairs), MEM_DEVICE, stream))
-    return int(n_pairs.value)
+    return _payload_pairs_device("gpk_dwithin_join", left, right, r_index, d, out_counts, out_pairs, out_dist, left_row_base, stream)
 
 
 def spatial_join_dwithin(lhs, rhs, options: Optional[SpatialJoinDWithinArgs] = None):
@@ -501,14 +545,7 @@ def spatial_join_dwithin(lhs, rhs, options: Optional[SpatialJoinDWithinArgs] = N
     spatial_join takes them): every left row with every right row within `options.distance` of it, shaped like spatial_join's result —
     suffixed left columns, suffixed right columns, then `distance_col` when asked for.  Any two geometry families."""
     options = options or SpatialJoinDWithinArgs()
-    if options.join_type not in ("inner", "left"):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"dwithin join: join_type must be 'inner' or 'left', got {options.join_type!r}")
-    d = dwithin_distance_arg(options.distance)
-    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
-    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
-    pairs, counts, dist = dwithin_pairs(lgeo, rgeo, d, options.r_index)
-    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
+    return _payload_table_join("dwithin join", lhs, rhs, options, lambda: dwithin_distance_arg(options.distance), dwithin_pairs, value_col=options.distance_col)
 
 
 # ---- line x polygon predicate join (gpk_line_polygon_join) ----------------------------------------------------------------------
@@ -566,14 +603,7 @@ def relation_pairs(
     uint32 sorted by (l, r), counts (n_left,) uint32, masks (H,) uint8 — what GeoSeries.line_polygon_relation gives for the pairs).
     Host-buffer variant: the pair buffer is sized like join_pairs'."""
     pred = relation_predicate_arg(predicate, left._family(), right._family())
-    lib = _abi.lib()
-    n = len(left)
-    counts = np.zeros(n, dtype=np.uint32)
-    rh = r_index.handle if r_index is not None else None
-    call = lambda pairs_ptr, mask_ptr, capacity, n_pairs: lib.gpk_line_polygon_join(  # noqa: E731
-        left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs_ptr, mask_ptr, capacity, n_pairs, MEM_HOST, None)
-    pairs, mask = _pairs_with_retry(n, call, want_dist=True, payload=np.uint8)
-    return pairs, counts, mask
+    return _payload_pairs("gpk_line_polygon_join", left, right, r_index, pred, left_row_base, payload=np.uint8)
 
 
 def relation_pairs_device(
@@ -591,35 +621,16 @@ def relation_pairs_device(
     be None; out_pairs None = count only; without out_mask a pair's walk ends as soon as its predicate is settled) are filled in place
     on `stream`; returns the number of pairs."""
     pred = relation_predicate_arg(predicate, left.geom_type, right.geom_type)
-    n_pairs = C.c_int64(0)
-    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
-    _abi.check(_abi.lib().gpk_line_polygon_join(
-        left.handle, right.handle, rh, pred, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_mask), cap, C.byref(n_pairs), MEM_DEVICE, stream))
-    return int(n_pairs.value)
+    return _payload_pairs_device("gpk_line_polygon_join", left, right, r_index, pred, out_counts, out_pairs, out_mask, left_row_base, stream)
 
 
 def spatial_join_relation(lhs, rhs, options: Optional[SpatialJoinRelationArgs] = None):
     """GeoPandas' sjoin(predicate=...) over two pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes
     them), one of lines and one of polygons: every left row with every right row in the relation, shaped like spatial_join's result —
     suffixed left columns, suffixed right columns, then `relation_col` (the pair's mask) when asked for."""
-    import pyarrow as pa
-
     options = options or SpatialJoinRelationArgs()
-    if options.join_type not in ("inner", "left"):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"relation join: join_type must be 'inner' or 'left', got {options.join_type!r}")
-    if options.predicate not in RELATION_PREDICATES:
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"relation join: unknown predicate {options.predicate!r}: one of {sorted(RELATION_PREDICATES)}")
-    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
-    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
-    pairs, counts, mask = relation_pairs(lgeo, rgeo, options.predicate, options.r_index)
-    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
-    if options.relation_col is not None:
-        matched = ri >= 0
-        m = np.zeros(len(ri), dtype=np.uint8)
-        m[matched] = mask
-        table = table.append_column(options.relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
-    return table
+    return _payload_table_join("relation join", lhs, rhs, options, lambda: _known_predicate("relation join", options.predicate, RELATION_PREDICATES), relation_pairs,
+                               relation_col=options.relation_col)
 
 
 # ---- polygon x polygon predicate join (gpk_polygon_relation_join) ---------------------------------------------------------------
@@ -663,14 +674,7 @@ def polygon_relation_pairs(
     `predicate`: (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32, masks (H,) uint8 — what
     left.polygon_relation(right) gives for the pairs).  Host-buffer variant: the pair buffer is sized like join_pairs'."""
     pred = polygon_relation_predicate_arg(predicate, left._family(), right._family())
-    lib = _abi.lib()
-    n = len(left)
-    counts = np.zeros(n, dtype=np.uint32)
-    rh = r_index.handle if r_index is not None else None
-    call = lambda pairs_ptr, mask_ptr, capacity, n_pairs: lib.gpk_polygon_relation_join(  # noqa: E731
-        left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs_ptr, mask_ptr, capacity, n_pairs, MEM_HOST, None)
-    pairs, mask = _pairs_with_retry(n, call, want_dist=True, payload=np.uint8)
-    return pairs, counts, mask
+    return _payload_pairs("gpk_polygon_relation_join", left, right, r_index, pred, left_row_base, payload=np.uint8)
 
 
 def polygon_relation_pairs_device(
@@ -688,37 +692,16 @@ def polygon_relation_pairs_device(
     be None; out_pairs None = count only; without out_mask the work on a pair ends as soon as its predicate is settled) are filled in
     place on `stream`; returns the number of pairs."""
     pred = polygon_relation_predicate_arg(predicate, left.geom_type, right.geom_type)
-    n_pairs = C.c_int64(0)
-    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
-    _abi.check(_abi.lib().gpk_polygon_relation_join(
-        left.handle, right.handle, rh, pred, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_mask), cap, C.byref(n_pairs), MEM_DEVICE, stream))
-    return int(n_pairs.value)
+    return _payload_pairs_device("gpk_polygon_relation_join", left, right, r_index, pred, out_counts, out_pairs, out_mask, left_row_base, stream)
 
 
 def spatial_join_polygon_relation(lhs, rhs, options: Optional[SpatialJoinRelationArgs] = None):
     """GeoPandas' sjoin(predicate=...) over two pyarrow Tables of polygons with a `geometry` column (WKB or native GeoArrow, as
     spatial_join takes them): every left row with every right row in the relation, shaped like spatial_join_relation's result —
     suffixed left columns, suffixed right columns, then `relation_col` (the pair's 4-bit mask) when asked for."""
-    import pyarrow as pa
-
     options = options or SpatialJoinRelationArgs()
-    if options.join_type not in ("inner", "left"):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"polygon relation join: join_type must be 'inner' or 'left', got {options.join_type!r}")
-    if options.predicate not in POLYGON_RELATION_PREDICATES:
-        raise _abi.GeopolarsHipError(
-            _abi.GPK_ERR_INVALID_ARGUMENT, f"polygon relation join: unknown predicate {options.predicate!r}: one of {sorted(POLYGON_RELATION_PREDICATES)}"
-        )
-    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
-    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
-    pairs, counts, mask = polygon_relation_pairs(lgeo, rgeo, options.predicate, options.r_index)
-    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
-    if options.relation_col is not None:
-        matched = ri >= 0
-        m = np.zeros(len(ri), dtype=np.uint8)
-        m[matched] = mask
-        table = table.append_column(options.relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
-    return table
+    return _payload_table_join("polygon relation join", lhs, rhs, options, lambda: _known_predicate("polygon relation join", options.predicate, POLYGON_RELATION_PREDICATES), polygon_relation_pairs,
+                               relation_col=options.relation_col)
 
 
 # ---- intersection measure join (gpk_intersection_measure_join) --------------------------------------------------------------------
@@ -751,14 +734,7 @@ def intersection_measure_pairs(
     sized like join_pairs'."""
     m = intersection_min_measure_arg(min_measure)
     intersection_families_arg("intersection measure join", left._family(), right._family())
-    lib = _abi.lib()
-    n = len(left)
-    counts = np.zeros(n, dtype=np.uint32)
-    rh = r_index.handle if r_index is not None else None
-    call = lambda pairs_ptr, measure_ptr, capacity, n_pairs: lib.gpk_intersection_measure_join(  # noqa: E731
-        left.device().handle, right.device().handle, rh, m, left_row_base, counts.ctypes.data, pairs_ptr, measure_ptr, capacity, n_pairs, MEM_HOST, None)
-    pairs, measure = _pairs_with_retry(n, call, want_dist=True)
-    return pairs, counts, measure
+    return _payload_pairs("gpk_intersection_measure_join", left, right, r_index, m, left_row_base)
 
 
 def intersection_measure_pairs_device(
@@ -776,11 +752,7 @@ def intersection_measure_pairs_device(
     may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
     m = intersection_min_measure_arg(min_measure)
     intersection_families_arg("intersection measure join", left.geom_type, right.geom_type)
-    n_pairs = C.c_int64(0)
-    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
-    _abi.check(_abi.lib().gpk_intersection_measure_join(
-        left.handle, right.handle, rh, m, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_measure), cap, C.byref(n_pairs), MEM_DEVICE, stream))
-    return int(n_pairs.value)
+    return _payload_pairs_device("gpk_intersection_measure_join", left, right, r_index, m, out_counts, out_pairs, out_measure, left_row_base, stream)
 
 
 def spatial_join_intersection(lhs, rhs, options: Optional[SpatialJoinIntersectionArgs] = None):
@@ -789,16 +761,13 @@ def spatial_join_intersection(lhs, rhs, options: Optional[SpatialJoinIntersectio
     than `options.min_measure` of area (polygons) or length (lines) with, shaped like spatial_join's result — suffixed left columns,
     suffixed right columns, then the float64 `measure_col`."""
     options = options or SpatialJoinIntersectionArgs()
-    if options.join_type not in ("inner", "left"):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"intersection join: join_type must be 'inner' or 'left', got {options.join_type!r}")
-    if not isinstance(options.measure_col, str) or not options.measure_col:
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"intersection join: measure_col must be a column name, got {options.measure_col!r}")
-    m = intersection_min_measure_arg(options.min_measure)
-    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
-    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
-    pairs, counts, measure = intersection_measure_pairs(lgeo, rgeo, m, options.r_index)
-    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.measure_col, measure)
+
+    def family_arg() -> float:
+        if not isinstance(options.measure_col, str) or not options.measure_col:
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"intersection join: measure_col must be a column name, got {options.measure_col!r}")
+        return intersection_min_measure_arg(options.min_measure)
+
+    return _payload_table_join("intersection join", lhs, rhs, options, family_arg, intersection_measure_pairs, value_col=options.measure_col)
 
 
 # ---- line x line predicate join (gpk_line_relation_join) ---------------------------------------------------------------------
@@ -842,14 +811,7 @@ def line_relation_pairs(
     `predicate`: (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32, masks (H,) uint8 — what
     left.line_relation(right) gives for the pairs).  Host-buffer variant: the pair buffer is sized like join_pairs'."""
     pred = line_relation_predicate_arg(predicate, left._family(), right._family())
-    lib = _abi.lib()
-    n = len(left)
-    counts = np.zeros(n, dtype=np.uint32)
-    rh = r_index.handle if r_index is not None else None
-    call = lambda pairs_ptr, mask_ptr, capacity, n_pairs: lib.gpk_line_relation_join(  # noqa: E731
-        left.device().handle, right.device().handle, rh, pred, left_row_base, counts.ctypes.data, pairs_ptr, mask_ptr, capacity, n_pairs, MEM_HOST, None)
-    pairs, mask = _pairs_with_retry(n, call, want_dist=True, payload=np.uint8)
-    return pairs, counts, mask
+    return _payload_pairs("gpk_line_relation_join", left, right, r_index, pred, left_row_base, payload=np.uint8)
 
 
 def line_relation_pairs_device(
@@ -867,34 +829,13 @@ def line_relation_pairs_device(
     be None; out_pairs None = count only; without out_mask the work on a pair ends as soon as its predicate is settled) are filled in
     place on `stream`; returns the number of pairs."""
     pred = line_relation_predicate_arg(predicate, left.geom_type, right.geom_type)
-    n_pairs = C.c_int64(0)
-    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
-    _abi.check(_abi.lib().gpk_line_relation_join(
-        left.handle, right.handle, rh, pred, left_row_base, _ptr(out_counts), _ptr(out_pairs), _ptr(out_mask), cap, C.byref(n_pairs), MEM_DEVICE, stream))
-    return int(n_pairs.value)
+    return _payload_pairs_device("gpk_line_relation_join", left, right, r_index, pred, out_counts, out_pairs, out_mask, left_row_base, stream)
 
 
 def spatial_join_line_relation(lhs, rhs, options: Optional[SpatialJoinRelationArgs] = None):
     """GeoPandas' sjoin(predicate=...) over two pyarrow Tables of lines with a `geometry` column (WKB or native GeoArrow, as
     spatial_join takes them): every left row with every right row in the relation, shaped like spatial_join_relation's result —
     suffixed left columns, suffixed right columns, then `relation_col` (the pair's 7-bit mask) when asked for."""
-    import pyarrow as pa
-
     options = options or SpatialJoinRelationArgs()
-    if options.join_type not in ("inner", "left"):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"line relation join: join_type must be 'inner' or 'left', got {options.join_type!r}")
-    if options.predicate not in LINE_RELATION_PREDICATES:
-        raise _abi.GeopolarsHipError(
-            _abi.GPK_ERR_INVALID_ARGUMENT, f"line relation join: unknown predicate {options.predicate!r}: one of {sorted(LINE_RELATION_PREDICATES)}"
-        )
-    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
-    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
-    pairs, counts, mask = line_relation_pairs(lgeo, rgeo, options.predicate, options.r_index)
-    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
-    if options.relation_col is not None:
-        matched = ri >= 0
-        m = np.zeros(len(ri), dtype=np.uint8)
-        m[matched] = mask
-        table = table.append_column(options.relation_col, pa.array(m, type=pa.uint8(), mask=~matched))
-    return table
+    return _payload_table_join("line relation join", lhs, rhs, options, lambda: _known_predicate("line relation join", options.predicate, LINE_RELATION_PREDICATES), line_relation_pairs,
+                               relation_col=options.relation_col)

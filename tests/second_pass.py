@@ -5,7 +5,8 @@ Small fixtures give every group exactly one unit, so the loop's stride, the stat
 lists, registers) and the barriers that make the reuse safe never run.  The helpers here size a column past the cap from the
 device's CU count and fill it with a shuffled tiling of a small base column whose answers an exact reference gives.
 
-INVENTORY lists every `cu_count()` launch site of geopolars_amd/csrc with the test that takes it past its cap;
+INVENTORY lists every capped launch site of geopolars_amd/csrc — a `cu_count()` written at the launch, or a call of the shared
+`group_grid` helper (gpk_common.h: 256 / G units a block, cu_count() * 32 blocks) — with the test that takes it past its cap;
 tests/test_second_pass_inventory.py (no GPU) fails when a source file gains or loses a site without the list following."""
 from __future__ import annotations
 
@@ -75,7 +76,7 @@ class Site(NamedTuple):
     unit: str  # what one trip of the loop processes
     units_per_block: str
     cap_mult: Optional[int]  # blocks are capped at cu_count() * cap_mult
-    occurrences: int  # how often `cu_count()` is written at this site
+    occurrences: int  # how often `cu_count()` or a `group_grid` call is written at this site
     test: Optional[str]  # the test that runs the loop past its first trip; None only for an exempt site (then `note` says why)
     note: str = ""
     exempt: bool = False
@@ -84,6 +85,8 @@ class Site(NamedTuple):
 INVENTORY = [
     Site("gpk_runtime.hip", "-", "-", "-", None, 1, None, "the definition of cu_count()", exempt=True),
     Site("gpk_common.h", "-", "-", "-", None, 1, None, "the declaration of cu_count()", exempt=True),
+    Site("gpk_common.h", "-", "-", "-", 32, 2, None, "the definition of the shared group_grid (its name and the cu_count() it caps with): the "
+         "sites that launch on it are listed below, each with its file's calls", exempt=True),
     Site("gpk_join.hip", "pip_flow (persistent point join)", "tile of points", "1", 1, 2, None,
          "one persistent work-group per CU; its tile loop is the benchmark path and runs in every point join of the suite", exempt=True),
     # ---- validity ----
@@ -97,16 +100,16 @@ INVENTORY = [
     Site("gpk_interior.hip", "interior_poly_big_kernel / interior_vertex_big_kernel", "listed row (> 512 coordinates)", "1", 8, 2,
          f"{NEW}::test_representative_point_large_rows"),
     # ---- relations: one group_grid serves the row-wise call and the join's refine ----
-    Site("gpk_polyrel.hip", "polygon_relation_rowwise_kernel, pp refine", "row / candidate pair", "256/G", 32, 1, f"{NEW}::test_polygon_relation_rows",
+    Site("gpk_polyrel.hip", "polygon_relation_rowwise_kernel, pp refine", "row / candidate pair", "256/G", 32, 2, f"{NEW}::test_polygon_relation_rows",
          "refine: test_polygon_relation_join"),
-    Site("gpk_linearea.hip", "line_polygon_relation kernels, lp refine", "row / candidate pair", "256/G", 32, 1, f"{NEW}::test_line_polygon_relation_rows",
+    Site("gpk_linearea.hip", "line_polygon_relation kernels, lp refine", "row / candidate pair", "256/G", 32, 2, f"{NEW}::test_line_polygon_relation_rows",
          "refine: test_line_polygon_join"),
-    Site("gpk_lineline.hip", "line_relation kernels, ll refine", "row / candidate pair", "256/G", 32, 1, f"{NEW}::test_line_relation_rows",
+    Site("gpk_lineline.hip", "line_relation kernels, ll refine", "row / candidate pair", "256/G", 32, 2, f"{NEW}::test_line_relation_rows",
          "refine: test_line_relation_join"),
-    Site("gpk_overlay.hip", "intersection_measure kernels, ov refine", "row / candidate pair", "256/G", 32, 1,
+    Site("gpk_overlay.hip", "intersection_measure kernels, ov refine", "row / candidate pair", "256/G", 32, 2,
          f"{NEW}::test_intersection_measure_join", "the refine; row-wise: tests/test_gpu_overlay.py::test_a_million_rectangle_pairs (2^20 rows at G = 4)"),
     # ---- dwithin ----
-    Site("gpk_dwithin.hip", "dwithin point / pair refine kernels (the join's refines)", "row / candidate pair", "256/G", 32, 1,
+    Site("gpk_dwithin.hip", "dwithin point / pair refine kernels (the join's refines)", "row / candidate pair", "256/G", 32, 2,
          f"{NEW}::test_dwithin_join_pair_refine", "the point refine: test_dwithin_join_point_refine (gpk_dwithin_rowwise does not launch these: it "
          "thresholds gpk_distance_rowwise)"),
     Site("gpk_dwithin.hip", "dwithin_pair_large_kernel", "listed candidate (n_A * n_B > PD_LARGE_COST)", "1", 4, 2, f"{NEW}::test_dwithin_join_large_list"),
@@ -118,9 +121,9 @@ INVENTORY = [
     # ---- linear referencing ----
     Site("gpk_linref.hip", "locate_point / closest_point kernels", "tile of LINREF_TILE = 2048 points", "1 tile", 16, 2,
          f"{NEW}::test_locate_and_closest_point_tiles"),
-    Site("gpk_linref.hip", "interpolate_point_kernel<1|8|32>", "row", "256/G", 32, 2, f"{NEW}::test_interpolate_rows"),
+    Site("gpk_linref.hip", "interpolate_point_kernel<1|8|32>", "row", "256/G", 32, 1, f"{NEW}::test_interpolate_rows"),
     # ---- point distance ----
-    Site("gpk_rowwise.hip", "point_poly_predicate / poly_poly_intersects / poly_poly_contains (coop_grid)", "row", "256/G", 32, 1,
+    Site("gpk_rowwise.hip", "point_poly_predicate / poly_poly_intersects / poly_poly_contains (group_grid)", "row", "256/G", 32, 3,
          f"{NEW}::test_polygon_predicate_rows", "points against polygons: test_point_polygon_predicate_rows"),
     Site("gpk_rowwise.hip", "distance_grouped_kernel", "128 ordered rows a wave, 4 waves", "512", 16, 1,
          f"{NEW}::test_point_distance_grouped_chunks", "also tests/test_gpu_configs.py::test_c3_full_size_every_row (a fixed 10M rows)"),
@@ -133,7 +136,7 @@ INVENTORY = [
     Site("gpk_unary.hip", "affine_kernel", "coordinate", "256", 8, 1, f"{NEW}::test_affine_coordinates"),
     Site("gpk_unary.hip", "affine_rows_kernel<G>", "row", "256/G", 16, 1, f"{NEW}::test_affine_rows"),
     Site("gpk_crs.hip", "reproject kernels", "coordinate", "256", 8, 1, "tests/test_gpu_crs.py::test_grid_stride_path_is_bit_identical_per_tile"),
-    Site("gpk_lineal_ops.hip", "geodesic_seq_kernel<4|16>, rdp_kernel<8|64>, rdp_compact_kernel", "sequence", "256/G", 32, 1,
+    Site("gpk_lineal_ops.hip", "geodesic_seq_kernel<4|16>, rdp_kernel<8|64>, rdp_compact_kernel", "sequence", "256/G", 32, 9,
          f"{NEW}::test_geodesic_length_rows", "simplify: tests/test_gpu_simplify.py::test_deep_stacks_and_a_wrapping_grid"),
     Site("gpk_wkb_device.hip", "wkb_copy_long_kernel", "listed sequence (> WKB_LONG coordinates)", "256 coordinates of one sequence", 8, 1, None,
          "cannot run at all: sequences above WKB_LONG = 4096 coordinates are listed only in the short-sequence form of the copy, which is "
@@ -141,7 +144,7 @@ INVENTORY = [
     # ---- joins ----
     Site("gpk_bboxjoin.hip", "pair_refine_kernel / pair_contains_kernel", "candidate pair", "16", 64, 1,
          "tests/test_gpu_predicate_instances.py::test_intersects_join_at_scale", "sized from the CU count (refine_per >= 4)"),
-    Site("gpk_nearest.hip", "nearest_best_kernel / nearest_emit_kernel <1|8|32>", "left point", "256/G", 32, 1,
+    Site("gpk_nearest.hip", "nearest_best_kernel / nearest_emit_kernel <1|8|32>", "left point", "256/G", 32, 2,
          f"{NEW}::test_nearest_join_rows", "also tests/test_gpu_nearest.py::test_full_size_c3_data (a fixed 10M points)"),
     # ---- convex hull ----
     Site("gpk_hull.hip", "hull_small_kernel<128, LISTED>", "listed row of 65 .. 128 points", "16", 8, 2, f"{NEW}::test_hull_mid_list"),
@@ -153,12 +156,12 @@ INVENTORY = [
 
 
 def counted_sites() -> dict:
-    """{source file: number of `cu_count()` occurrences} over geopolars_amd/csrc"""
+    """{source file: number of `cu_count()` occurrences and `group_grid` calls} over geopolars_amd/csrc"""
     out = {}
     for fn in sorted(os.listdir(CSRC)):
         if fn.endswith((".hip", ".h", ".cpp")):
             with open(os.path.join(CSRC, fn)) as f:
-                k = len(re.findall(r"\bcu_count\(\)", f.read()))
+                k = len(re.findall(r"\bcu_count\(\)|\bgroup_grid\(", f.read()))
             if k:
                 out[fn] = k
     return out

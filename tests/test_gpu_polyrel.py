@@ -4,7 +4,7 @@ against the exact rational reference (tests/polyrel_ref.py; tests/test_polyrel_r
   1. known answers and ties in the four family combinations, as-is and padded with collinear vertices (both lane-group sizes);
   2. placements; 3. random lattice columns, argument swap; 4. agreement with intersects / contains, dwithin at 0 and gpk_spatial_join;
   5. unusable rows and refused calls; 6. the join: seven predicates, count-only, pairs, masks, prebuilt and NULL index, left_row_base,
-  capacity, device buffers, self-join; 7. the table join; 8. gpk_spatial_join's polygon arms are unchanged."""
+  capacity (also with a payload buffer, for all five payload joins), device buffers, self-join; 7. the table join; 8. gpk_spatial_join's polygon arms are unchanged."""
 import ctypes as C
 
 import numpy as np
@@ -259,6 +259,66 @@ def _check_join(sl, sr, table):
 def test_join_against_the_brute_force_table(gpk, ka, kb):
     left, lv, right, rv, table, _ = P.join_fixture(ka, kb)
     _check_join(series(ka, left, lv), series(kb, right, rv), table)
+
+
+def _payload_join_case(family):
+    """(ABI function, left, right, the family's argument, reference pairs, counts and per-pair payload) on the family's join fixture"""
+    lib = _abi.lib()
+    if family == "polygon_relation":
+        left, lv, right, rv, table, _ = P.join_fixture(PG, PG)
+        return (lib.gpk_polygon_relation_join, series(PG, left, lv), series(PG, right, rv), P.PRED_IDS["intersects"]) + P.expected_pairs(table, "intersects")
+    if family == "line_relation":
+        from tests import linerel_ref as L
+
+        left, lv, right, rv, table, _ = L.join_fixture(L.LS, L.LS)
+        return (lib.gpk_line_relation_join, series(L.LS, left, lv), series(L.LS, right, rv), L.PRED_IDS["intersects"]) + L.expected_pairs(table, "intersects")
+    if family == "line_polygon":
+        lines, lnv, polys, pv, table = R.join_fixture(R.LS, R.PG)
+        return (lib.gpk_line_polygon_join, series(R.LS, lines, lnv), series(R.PG, polys, pv), R.PRED_IDS["intersects"]) + R.expected_pairs(table, "intersects")
+    if family == "intersection_measure":  # the reference of the doubles: the row-wise call, which the join repeats bit for bit
+        from tests import overlay_ref as O
+        from tests import test_gpu_overlay as OV
+
+        golden = np.load(O.GOLDEN)
+        left, right = GeoSeries(O.unpack(golden, "join_left_", PG)), GeoSeries(O.unpack(golden, "join_right_", PG))
+        p0, c0, _ = OV.expected(golden["join_area"], len(left), OV.THETA, OV.JOIN_TOL_AREA)
+        return lib.gpk_intersection_measure_join, left, right, OV.THETA, p0, c0, OV.rowwise_of_pairs(left, right, PG, p0)
+    from tests import dwithin_ref as W  # two non-point columns: the refine that keeps a list behind the distances
+    from tests import test_gpu_dwithin as DW
+
+    left, right = W.pair_fixture(*W.PAIR_INSTANCES[0])
+    sl, sr = DW.series(left), DW.series(right)
+    D = DW.distance_matrix(left, right, sl, sr)
+    t = DW.quantile_thresholds(D)[2]
+    return (lib.gpk_dwithin_join, sl, sr, t) + DW.expected(D, t)
+
+
+@pytest.mark.parametrize("family", ["polygon_relation", "line_relation", "line_polygon", "intersection_measure", "dwithin"])
+def test_payload_buffer_with_too_small_a_capacity(gpk, family):
+    """every join that returns a value per pair, handed a pair buffer AND a payload buffer one element short: the capacity error, the
+    exact total and the counts, from host and from device buffers; with the exact capacity the pairs and the payload, bit for bit"""
+    fn, sl, sr, arg, p0, c0, v0 = _payload_join_case(family)
+    total = len(p0)
+    assert total > 1 and v0.dtype in (np.uint8, np.float64)
+    lh, rh = sl.device().handle, sr.device().handle
+    n = C.c_int64(-1)
+    counts = np.full(len(c0), 0xFFFFFFFF, dtype=np.uint32)
+    pairs, values = np.zeros((total - 1, 2), dtype=np.uint32), np.zeros(total - 1, dtype=v0.dtype)
+    rc = fn(lh, rh, None, arg, 0, counts.ctypes.data, pairs.ctypes.data, values.ctypes.data, total - 1, C.byref(n), _abi.MEM_HOST, None)
+    assert rc == _abi.GPK_ERR_CAPACITY and n.value == total
+    assert np.array_equal(counts, c0)
+    d_counts = torch.full((len(c0),), -1, dtype=torch.int32, device="cuda:0")
+    d_pairs = torch.zeros((total - 1, 2), dtype=torch.int32, device="cuda:0")
+    d_values = torch.zeros(total - 1, dtype=torch.uint8 if v0.dtype == np.uint8 else torch.float64, device="cuda:0")
+    n = C.c_int64(-1)
+    rc = fn(lh, rh, None, arg, 0, d_counts.data_ptr(), d_pairs.data_ptr(), d_values.data_ptr(), total - 1, C.byref(n), _abi.MEM_DEVICE, None)
+    torch.cuda.synchronize()
+    assert rc == _abi.GPK_ERR_CAPACITY and n.value == total
+    pairs, values = np.zeros((total, 2), dtype=np.uint32), np.zeros(total, dtype=v0.dtype)
+    rc = fn(lh, rh, None, arg, 0, counts.ctypes.data, pairs.ctypes.data, values.ctypes.data, total, C.byref(n), _abi.MEM_HOST, None)
+    assert rc == _abi.GPK_OK and n.value == total
+    assert np.array_equal(pairs, p0) and np.array_equal(counts, c0)
+    assert values.dtype == v0.dtype and values.tobytes() == np.ascontiguousarray(v0).tobytes()
 
 
 @pytest.mark.parametrize("ka", [PG, MPG], ids=["pg", "mpg"])

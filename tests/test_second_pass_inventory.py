@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_every_capped_launch_site_is_registered():
-    """a new `cu_count()` launch fails here until it is entered in second_pass.INVENTORY with the test that takes it past its cap"""
+    """a new `cu_count()` launch or `group_grid` call fails here until it is entered in second_pass.INVENTORY with the test that takes
+    it past its cap"""
     assert SP.counted_sites() == SP.inventory_counts()
 
 
