@@ -38,6 +38,7 @@ SOURCES = [
     "gpk_frechet.hip",
     "gpk_nearest.hip",
     "gpk_dwithin.hip",
+    "gpk_nearest_any.hip",
     "gpk_linref.hip",
     "gpk_linearea.hip",
     "gpk_polyrel.hip",

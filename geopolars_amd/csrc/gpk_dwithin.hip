@@ -36,6 +36,7 @@
 #include "gpk_candjoin.h"
 #include "gpk_device.h"
 #include "gpk_distance.h"
+#include "gpk_dwithin_refine.h"
 #include "gpk_pairdist.h"
 
 namespace gpk {
@@ -94,23 +95,30 @@ struct Cands {
     unsigned long long* stats;   // join statistics words or nullptr: [2] += candidates, [3] += candidates the box test rejected
 };
 
-__device__ __forceinline__ void count_stats(const Cands& cs, unsigned long long rejected, int lane) {
+// The refine kernels take the candidates as `Cands` (one threshold: gpk_dwithin_join, whose kernels read it as the scalar it always was)
+// or as `RowCands` (gpk_dwithin_refine.h: a threshold per LEFT row, gpk_nearest_join_any's search radius).
+__device__ __forceinline__ double threshold_of(const Cands& cs, int64_t) { return cs.t; }
+__device__ __forceinline__ double threshold_of(const RowCands& cs, int64_t l) { return cs.t[l]; }
+
+template <class CS>
+__device__ __forceinline__ void count_stats(const CS& cs, unsigned long long rejected, int lane) {
     if (!cs.stats) return;
     if (lane == 0 && rejected) atomicAdd(cs.stats + 3, rejected);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(cs.stats + 2, (unsigned long long)cs.n);
 }
 
 // A POINT column on one side (both: KIND == POINT, G == 1): G lanes per candidate.  `point_left`: pts is the caller's left column.
-template <int G, int KIND>
-__global__ __launch_bounds__(256) void dwithin_point_refine_kernel(DevGeo pts, DevGeo other, bool point_left, Cands cs) {
+template <int G, int KIND, class CS>
+__global__ __launch_bounds__(256) void dwithin_point_refine_kernel(DevGeo pts, DevGeo other, bool point_left, CS cs) {
     const int lane = threadIdx.x & (G - 1);
     const int64_t groups = (int64_t)gridDim.x * (256 / G);
     unsigned long long rejected = 0;
     for (int64_t c = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G; c < cs.n; c += groups) {
         const int64_t l = cs.l[c], r = cs.r[c];
         const int64_t ip = point_left ? l : r, jo = point_left ? r : l;
+        const double t = threshold_of(cs, l);
         double d = NAN;
-        if (!boxes_within(cs.lbox[l], cs.rbox[r], cs.t)) {
+        if (!boxes_within(cs.lbox[l], cs.rbox[r], t)) {
             ++rejected;
         } else {
             const double2 p = pts.xy[ip];
@@ -121,7 +129,7 @@ __global__ __launch_bounds__(256) void dwithin_point_refine_kernel(DevGeo pts, D
             if (ok) d = point_geom_distance<G, KIND>(other, jo, p.x, p.y, lane);
         }
         if (lane == 0) {
-            cs.hit[c] = d <= cs.t ? 1 : 0;
+            cs.hit[c] = d <= t ? 1 : 0;
             if (cs.dist) cs.dist[c] = d;
         }
     }
@@ -130,8 +138,8 @@ __global__ __launch_bounds__(256) void dwithin_point_refine_kernel(DevGeo pts, D
 
 // Two non-point columns in canonical order (KA <= KB); `swapped`: gb is the caller's left column.  G lanes per candidate; candidates
 // above PD_LARGE_COST are listed for dwithin_pair_large_kernel.
-template <int G, int KA, int KB>
-__global__ __launch_bounds__(256) void dwithin_pair_refine_kernel(DevGeo ga, DevGeo gb, bool swapped, Cands cs, uint32_t* __restrict__ large,
+template <int G, int KA, int KB, class CS>
+__global__ __launch_bounds__(256) void dwithin_pair_refine_kernel(DevGeo ga, DevGeo gb, bool swapped, CS cs, uint32_t* __restrict__ large,
                                                                   uint32_t* __restrict__ n_large) {
     const int lane = threadIdx.x & (G - 1);
     const int64_t groups = (int64_t)gridDim.x * (256 / G);
@@ -139,8 +147,9 @@ __global__ __launch_bounds__(256) void dwithin_pair_refine_kernel(DevGeo ga, Dev
     for (int64_t c = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G; c < cs.n; c += groups) {
         const int64_t l = cs.l[c], r = cs.r[c];
         const int64_t ia = swapped ? r : l, ib = swapped ? l : r;
+        const double t = threshold_of(cs, l);
         double d = NAN;
-        if (!boxes_within(cs.lbox[l], cs.rbox[r], cs.t)) {
+        if (!boxes_within(cs.lbox[l], cs.rbox[r], t)) {
             ++rejected;
         } else {
             const RowSeqs a = row_seqs<KA>(ga, ia), b = row_seqs<KB>(gb, ib);
@@ -154,7 +163,7 @@ __global__ __launch_bounds__(256) void dwithin_pair_refine_kernel(DevGeo ga, Dev
             }
         }
         if (lane == 0) {
-            cs.hit[c] = d <= cs.t ? 1 : 0;
+            cs.hit[c] = d <= t ? 1 : 0;
             if (cs.dist) cs.dist[c] = d;
         }
     }
@@ -162,8 +171,8 @@ __global__ __launch_bounds__(256) void dwithin_pair_refine_kernel(DevGeo ga, Dev
 }
 
 // One 256-lane work-group per listed candidate (pair_distance_workgroup: the routine of pairdist_large_kernel).
-template <int KA, int KB>
-__global__ __launch_bounds__(256) void dwithin_pair_large_kernel(DevGeo ga, DevGeo gb, bool swapped, Cands cs, const uint32_t* __restrict__ large,
+template <int KA, int KB, class CS>
+__global__ __launch_bounds__(256) void dwithin_pair_large_kernel(DevGeo ga, DevGeo gb, bool swapped, CS cs, const uint32_t* __restrict__ large,
                                                                  const uint32_t* __restrict__ n_large) {
     __shared__ PairLargeLds lds;
     const uint32_t count = *n_large;
@@ -172,7 +181,7 @@ __global__ __launch_bounds__(256) void dwithin_pair_large_kernel(DevGeo ga, DevG
         const int64_t l = cs.l[c], r = cs.r[c];
         const double d = pair_distance_workgroup<KA, KB>(ga, swapped ? r : l, gb, swapped ? l : r, lds);
         if (threadIdx.x == 0) {
-            cs.hit[c] = d <= cs.t ? 1 : 0;
+            cs.hit[c] = d <= threshold_of(cs, l) ? 1 : 0;
             if (cs.dist) cs.dist[c] = d;
         }
     }
@@ -211,39 +220,43 @@ DwScratch carve(const DwCtx& cx, void* scratch, int64_t n_cand) {
     return sc;
 }
 
-template <int KIND>
-int32_t launch_point_refine(int G, const DevGeo& pts, const DevGeo& other, bool point_left, const Cands& cs, hipStream_t s) {
+// the profile stages of the two launches
+inline const char* refine_label(const Cands&) { return "gpk_dwithin_refine"; }
+inline const char* refine_label(const RowCands& cs) { return cs.label; }
+inline const char* large_label(const Cands&) { return "gpk_dwithin_refine_large"; }
+inline const char* large_label(const RowCands& cs) { return cs.label_large; }
+
+template <int KIND, class CS>
+int32_t launch_point_refine(int G, const DevGeo& pts, const DevGeo& other, bool point_left, const CS& cs, hipStream_t s) {
     const dim3 grid = group_grid(cs.n, G);
     if (G == 1)
-        GPK_LAUNCH("gpk_dwithin_refine", (dwithin_point_refine_kernel<1, KIND>), grid, dim3(256), 0, s, pts, other, point_left, cs);
+        GPK_LAUNCH(refine_label(cs), (dwithin_point_refine_kernel<1, KIND, CS>), grid, dim3(256), 0, s, pts, other, point_left, cs);
     else if (G == 8)
-        GPK_LAUNCH("gpk_dwithin_refine", (dwithin_point_refine_kernel<8, KIND>), grid, dim3(256), 0, s, pts, other, point_left, cs);
+        GPK_LAUNCH(refine_label(cs), (dwithin_point_refine_kernel<8, KIND, CS>), grid, dim3(256), 0, s, pts, other, point_left, cs);
     else
-        GPK_LAUNCH("gpk_dwithin_refine", (dwithin_point_refine_kernel<32, KIND>), grid, dim3(256), 0, s, pts, other, point_left, cs);
+        GPK_LAUNCH(refine_label(cs), (dwithin_point_refine_kernel<32, KIND, CS>), grid, dim3(256), 0, s, pts, other, point_left, cs);
     return GPK_OK;
 }
 
-template <int KA, int KB>
-int32_t launch_pair_refine(const DevGeo& ga, const DevGeo& gb, bool swapped, const Cands& cs, uint32_t* large, uint32_t* n_large, hipStream_t s) {
+template <int KA, int KB, class CS>
+int32_t launch_pair_refine(const DevGeo& ga, const DevGeo& gb, bool swapped, const CS& cs, uint32_t* large, uint32_t* n_large, hipStream_t s) {
     const int G = pairdist_group_size(ga, gb);
     const dim3 grid = group_grid(cs.n, G);
     if (G == 8)
-        GPK_LAUNCH("gpk_dwithin_refine", (dwithin_pair_refine_kernel<8, KA, KB>), grid, dim3(256), 0, s, ga, gb, swapped, cs, large, n_large);
+        GPK_LAUNCH(refine_label(cs), (dwithin_pair_refine_kernel<8, KA, KB, CS>), grid, dim3(256), 0, s, ga, gb, swapped, cs, large, n_large);
     else
-        GPK_LAUNCH("gpk_dwithin_refine", (dwithin_pair_refine_kernel<32, KA, KB>), grid, dim3(256), 0, s, ga, gb, swapped, cs, large, n_large);
+        GPK_LAUNCH(refine_label(cs), (dwithin_pair_refine_kernel<32, KA, KB, CS>), grid, dim3(256), 0, s, ga, gb, swapped, cs, large, n_large);
     // the listed candidates: a fixed grid that reads the list's length on the device (idle work-groups return at once)
     const int64_t lb = (int64_t)cu_count() * 4 < cs.n ? (int64_t)cu_count() * 4 : cs.n;
-    GPK_LAUNCH("gpk_dwithin_refine_large", (dwithin_pair_large_kernel<KA, KB>), dim3((unsigned)lb), dim3(256), 0, s, ga, gb, swapped, cs,
+    GPK_LAUNCH(large_label(cs), (dwithin_pair_large_kernel<KA, KB, CS>), dim3((unsigned)lb), dim3(256), 0, s, ga, gb, swapped, cs,
                (const uint32_t*)large, (const uint32_t*)n_large);
     return GPK_OK;
 }
 
-int32_t dwithin_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r, int32_t n_cand, void* scratch, uint8_t* hit,
-                       unsigned long long* stats, hipStream_t s) {
-    const DwCtx& cx = *(const DwCtx*)ctx;
-    const DwScratch sc = carve(cx, scratch, n_cand);
-    const Cands cs{cand_l, cand_r, (int64_t)n_cand, cx.lbox, cx.rbox, cx.t, hit, sc.dist, stats};
-    const DevGeo &L = cx.p.left->d, &R = cx.p.right->d;
+// The exact distance of every candidate of `cs` (and hit = d <= its threshold) for the columns L (the candidates' l) and R (their r);
+// `large` (cs.n entries) and `n_large` (one word, zeroed here) are read only when neither column is POINT.
+template <class CS>
+int32_t refine_candidates(const char* who, const DevGeo& L, const DevGeo& R, const CS& cs, uint32_t* large, uint32_t* n_large, hipStream_t s) {
     if (L.type == GPK_GEOM_POINT || R.type == GPK_GEOM_POINT) {
         // the POINT column takes the point's place (the left one when both are), as in gpk_distance_rowwise
         const bool point_left = L.type == GPK_GEOM_POINT;
@@ -258,21 +271,29 @@ int32_t dwithin_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r
         default: return launch_point_refine<GPK_GEOM_MULTIPOLYGON>(G, pts, other, point_left, cs, s);
         }
     }
-    GPK_HIP(hipMemsetAsync(sc.n_large, 0, sizeof(uint32_t), s));
+    GPK_HIP(hipMemsetAsync(n_large, 0, sizeof(uint32_t), s));
     const bool swapped = L.type > R.type;
     const DevGeo& ga = swapped ? R : L;
     const DevGeo& gb = swapped ? L : R;
     constexpr int MP = GPK_GEOM_MULTIPOINT, LS = GPK_GEOM_LINESTRING, MLS = GPK_GEOM_MULTILINESTRING, PG = GPK_GEOM_POLYGON,
                   MPG = GPK_GEOM_MULTIPOLYGON;
 #define PD(KA, KB) \
-    if (ga.type == KA && gb.type == KB) return launch_pair_refine<KA, KB>(ga, gb, swapped, cs, sc.large, sc.n_large, s)
+    if (ga.type == KA && gb.type == KB) return launch_pair_refine<KA, KB>(ga, gb, swapped, cs, large, n_large, s)
     PD(LS, LS); PD(LS, PG); PD(LS, MP); PD(LS, MLS); PD(LS, MPG);
     PD(PG, PG); PD(PG, MP); PD(PG, MLS); PD(PG, MPG);
     PD(MP, MP); PD(MP, MLS); PD(MP, MPG);
     PD(MLS, MLS); PD(MLS, MPG);
     PD(MPG, MPG);
 #undef PD
-    return fail(GPK_ERR_MISMATCHED_GEOMETRY, "dwithin_join: no kernel for geometry types %d, %d", L.type, R.type);
+    return fail(GPK_ERR_MISMATCHED_GEOMETRY, "%s: no kernel for geometry types %d, %d", who, L.type, R.type);
+}
+
+int32_t dwithin_refine(void* ctx, const uint32_t* cand_l, const uint32_t* cand_r, int32_t n_cand, void* scratch, uint8_t* hit,
+                       unsigned long long* stats, hipStream_t s) {
+    const DwCtx& cx = *(const DwCtx*)ctx;
+    const DwScratch sc = carve(cx, scratch, n_cand);
+    const Cands cs{cand_l, cand_r, (int64_t)n_cand, cx.lbox, cx.rbox, cx.t, hit, sc.dist, stats};
+    return refine_candidates("dwithin_join", cx.p.left->d, cx.p.right->d, cs, sc.large, sc.n_large, s);
 }
 
 // the left boxes of the candidate search: the rows' own boxes grown by the distance and the margin (see the top of the file)
@@ -293,6 +314,11 @@ bool dwithin_family(int32_t t) {
 }
 
 }  // namespace
+
+int32_t refine_row_candidates(const char* who, const gpk_geoarray* left, const gpk_geoarray* right, const RowCands& cs, uint32_t* large,
+                              uint32_t* n_large, hipStream_t s) {
+    return refine_candidates(who, left->d, right->d, cs, large, n_large, s);
+}
 
 }  // namespace gpk
 

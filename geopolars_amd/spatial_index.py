@@ -3,7 +3,8 @@
     SpatialJoinArgs         spatial_index.rs:15-35   (join_type, predicate, suffixes, prebuilt indexes)
     SpatialIndex            spatial_index.rs:314-350 (TryFrom<&Series>)
     spatial_join            spatial_index.rs:37-204
-    spatial_join_nearest    GeoPandas' sjoin_nearest (not in the reference): every point with the nearest geometries of another table
+    spatial_join_nearest    GeoPandas' sjoin_nearest (not in the reference): every row — points, lines or polygons — with the nearest
+                            geometries of another table (nearest_pairs for a POINT left column, nearest_pairs_any for the others)
     spatial_join_dwithin    GeoPandas' sjoin(predicate="dwithin", distance=d) (not in the reference): every pair within a distance
     spatial_join_relation   GeoPandas' sjoin(predicate=...) for lines x polygons (not in the reference): intersects, within, contains,
                             covers, covered_by, crosses, touches from the exact relation mask
@@ -421,18 +422,65 @@ def nearest_pairs_device(
     return int(n_pairs.value)
 
 
+NEAREST_FAMILIES = (_abi.GEOM_POINT, _abi.GEOM_MULTIPOINT, _abi.GEOM_LINESTRING, _abi.GEOM_MULTILINESTRING, _abi.GEOM_POLYGON, _abi.GEOM_MULTIPOLYGON)
+
+
+def _require_nearest_families(left_family: int, right_family: int) -> None:
+    """both sides of gpk_nearest_join_any hold one of the six families (checked on the series' own type: nothing is uploaded for it)"""
+    for side, t in (("left", left_family), ("right", right_family)):
+        if t not in NEAREST_FAMILIES:
+            raise _mismatch(f"nearest join: the {side} side must be Point, MultiPoint, LineString, MultiLineString, Polygon or MultiPolygon (found {_abi_name(t)})")
+
+
+def nearest_pairs_any(
+    left: GeoSeries,
+    right: GeoSeries,
+    r_index: Optional[SpatialIndex] = None,
+    max_distance: Optional[float] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """nearest_pairs for any two geometry families (gpk_nearest_join_any): for every row of `left`, the rows of `right` at the smallest
+    distance (ties all returned; within max_distance when given): (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32,
+    distances (H,) float64 — the doubles GeoSeries.distance returns for the pairs).  For a POINT `left` the result is nearest_pairs'.
+    Host-buffer variant: the pair buffer is sized like join_pairs'."""
+    md = _max_distance_arg(max_distance)
+    _require_nearest_families(left._family(), right._family())
+    return _payload_pairs("gpk_nearest_join_any", left, right, r_index, md, left_row_base)
+
+
+def nearest_pairs_any_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    out_counts,
+    out_pairs,
+    out_dist=None,
+    max_distance: Optional[float] = None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_dist (cap,) float64 torch CUDA tensors (any
+    may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
+    md = _max_distance_arg(max_distance)
+    _require_nearest_families(left.geom_type, right.geom_type)
+    return _payload_pairs_device("gpk_nearest_join_any", left, right, r_index, md, out_counts, out_pairs, out_dist, left_row_base, stream)
+
+
 def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = None):
     """GeoPandas' sjoin_nearest over pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes them): every
-    left point with every right geometry at its smallest distance (ties all kept), shaped like spatial_join's result — suffixed left
-    columns, suffixed right columns, then `distance_col` when asked for.  The left geometry column must hold points."""
+    left row with every right geometry at its smallest distance (ties all kept), shaped like spatial_join's result — suffixed left
+    columns, suffixed right columns, then `distance_col` when asked for.  Any two of the six geometry families: a POINT left column goes
+    through gpk_nearest_join, every other one through gpk_nearest_join_any."""
     options = options or SpatialJoinNearestArgs()
     if options.join_type not in ("inner", "left"):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"nearest join: join_type must be 'inner' or 'left', got {options.join_type!r}")
     md = _max_distance_arg(options.max_distance)
     lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
-    _require_point_series(lgeo)
     rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
-    pairs, counts, dist = nearest_pairs(lgeo, rgeo, options.r_index, md)
+    if lgeo._family() == _abi.GEOM_POINT:
+        pairs, counts, dist = nearest_pairs(lgeo, rgeo, options.r_index, md)
+    else:
+        pairs, counts, dist = nearest_pairs_any(lgeo, rgeo, options.r_index, md)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
     return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
 

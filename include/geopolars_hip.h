@@ -599,6 +599,40 @@ int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray* right, co
                          int64_t* n_pairs, int32_t out_space, void* stream);
 
 /*
+ * Nearest-neighbour join for any two geometry families (GeoPandas sjoin_nearest with lines or polygons on the left: buildings to the
+ * nearest road, roads to the nearest station): for every left row l, every right row r with d(l, r) == min over the usable right rows
+ * r' of d(l, r') and d(l, r) <= max_distance.  Left and right are each any of POINT, MULTIPOINT, LINESTRING, MULTILINESTRING, POLYGON,
+ * MULTIPOLYGON — all 36 ordered pairs (anything else: GPK_ERR_MISMATCHED_GEOMETRY).  gpk_nearest_join is unchanged and keeps refusing
+ * a non-POINT left side; the argument list, outputs, capacity rule and index rule here are its own.
+ *   d(l, r)              the library's own row-wise distance of the pair, as in gpk_dwithin_join: the value the per-row kernel of
+ *                        gpk_distance_rowwise(left, right, ...) computes for these two columns — the same device routine, the same
+ *                        lane-group size, the same lane order, the work-group routine above PD_LARGE_COST — so every returned distance
+ *                        is bit for bit what that call returns for the pair (0 for rows that meet, contained rows included).  (Its
+ *                        grouped schedule for LINESTRING right sides with >= 8 rows per target agrees within its 1e-9 contract.)
+ *   ties                 equality of those doubles; all rows at the minimum are returned
+ *   max_distance         only pairs with d <= max_distance (closed); INFINITY = no limit; negative or NaN: GPK_ERR_INVALID_ARGUMENT
+ *                        before any device work
+ *   never matched,       null rows, EMPTY rows (no member has a coordinate) and POINT rows with a NaN coordinate, on either side (the
+ *   never candidates     rule of gpk_dwithin_join): such a left row has count 0, such a right row is nobody's neighbour.  An empty right
+ *                        side, or one of such rows only, gives no pairs.
+ *   POINT left           counts, pairs and distances are byte for byte those of gpk_nearest_join (both evaluate
+ *                        point_geom_distance<G, KIND> with G chosen from the right column)
+ *   out_counts[n_left]   u32 matches per left row (may be NULL)
+ *   out_pairs[2*cap]     u32 (l, r) interleaved, sorted by (l, r) (NULL with cap == 0: count-only mode)
+ *   out_dist[cap]        f64 d(l, r) of each pair (may be NULL)
+ *   *n_pairs             total, always set; GPK_ERR_CAPACITY when > cap and pairs were asked for.  More than 2^31 - 1 bbox candidates
+ *                        (right boxes meeting a left box grown by the row's search radius: the distance to the right row whose box is
+ *                        nearest, at most max_distance) or pairs: GPK_ERR_CAPACITY, shard the left side.
+ * The result does not depend on scheduling: two calls give identical bytes.  `left_row_base` is added to every emitted l.  All buffers
+ * live in `out_space`.  `right_index`: an index of `right` carrying the bbox grid (else GPK_ERR_INVALID_ARGUMENT), or NULL: a
+ * GPK_INDEX_BBOX_GRID index is built for the call and freed (it is not kept on the handle).  Synchronous, like gpk_spatial_join.
+ * Magnitude range: as gpk_distance_rowwise.
+ */
+int32_t gpk_nearest_join_any(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, double max_distance,
+                             uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_dist, int64_t pair_capacity,
+                             int64_t* n_pairs, int32_t out_space, void* stream);
+
+/*
  * Within-distance join (GeoPandas sjoin(predicate="dwithin", distance=d)): every (l, r) with distance(left[l], right[r]) <= distance.
  * Left and right are each any of POINT, MULTIPOINT, LINESTRING, MULTILINESTRING, POLYGON, MULTIPOLYGON — all 36 ordered pairs
  * (anything else: GPK_ERR_MISMATCHED_GEOMETRY).
@@ -992,7 +1026,8 @@ int32_t gpk_allgatherv_rows_f64(gpk_comm* comm, const double* local_dev, int64_t
  * left rows a chain-kernel join deferred to the generic walk (list cells, sub-cells without a chain entry, orientations
  * the floating-point filter could not certify), 0}, accumulated over the joins since the last reset; gpk_join_stats waits
  * for the device.  gpk_dwithin_join uses the last two words for its own counts: out[2] += bbox candidates, out[3] += candidates its
- * box-to-box test rejected before reading a coordinate (reset between joins of the two kinds to keep the meanings apart). */
+ * box-to-box test rejected before reading a coordinate (reset between joins of the two kinds to keep the meanings apart);
+ * gpk_nearest_join_any counts the candidates of its search in the same two words. */
 int32_t gpk_join_stats_enable(int32_t on);
 int32_t gpk_join_stats(int64_t out[4], int32_t reset);
 
