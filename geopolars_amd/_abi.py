@@ -46,6 +46,7 @@ QUERY_CONTAINED, QUERY_INTERSECTING = 0, 1  # gpk_index_query_envelope modes
 PREDICATES = {"intersects": PRED_INTERSECTS, "contains": PRED_CONTAINS, "within": PRED_WITHIN}
 LP_INTERIOR, LP_BOUNDARY, LP_EXTERIOR = 1, 2, 4  # GPK_LP_*: the bits of the line x polygon relation mask
 LP_PRED_INTERSECTS, LP_PRED_WITHIN, LP_PRED_COVERED_BY, LP_PRED_CROSSES, LP_PRED_TOUCHES = 0, 1, 2, 3, 4  # GPK_LP_PRED_*
+CLIP_INSIDE, CLIP_OUTSIDE, CLIP_DROP_EMPTY = 0, 1, 1  # GPK_CLIP_*: the two modes of gpk_line_clip and its flag
 PP_INTERIORS, PP_BOUNDARIES, PP_A_OUTSIDE, PP_B_OUTSIDE = 1, 2, 4, 8  # GPK_PP_*: the bits of the polygon x polygon relation mask
 (PP_PRED_INTERSECTS, PP_PRED_WITHIN, PP_PRED_CONTAINS, PP_PRED_TOUCHES, PP_PRED_OVERLAPS, PP_PRED_EQUALS,
  PP_PRED_CONTAINS_PROPERLY) = range(7)  # GPK_PP_PRED_*
@@ -203,6 +204,7 @@ _PROTOS = {
         [_VP, _VP, _VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
     "gpk_intersection_measure": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_line_clip": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
     "gpk_intersection_measure_join": (
         C.c_int32,
         [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],

@@ -43,6 +43,7 @@ SOURCES = [
     "gpk_linearea.hip",
     "gpk_polyrel.hip",
     "gpk_overlay.hip",
+    "gpk_lineclip.hip",
     "gpk_lineline.hip",
     "gpk_validity.hip",
     "gpk_interior.hip",

@@ -633,6 +633,24 @@ class GeoSeries:
         MULTIPOLYGON."""
         return self._intersection_measure("intersection_length", LINEAL, other, other_rows)
 
+    # ---- clip lines to polygons (gpk_lineclip.hip) ------------------------------------------------
+    def _line_clip(self, op: str, mode: int, other: "GeoSeries", other_rows) -> "GeoSeries":
+        rows = line_clip_args(op, self, other, other_rows)
+        return line_clip_call(self.device(), other.device(), None, None if rows is None else rows.ctypes.data, len(self), MEM_HOST, mode, 0, None, MEM_HOST)
+
+    def intersection(self, other: "GeoSeries", other_rows=None) -> "GeoSeries":
+        """The piece of every row's line inside its closed polygon other[other_rows[i]] (gpk_line_clip), as a MULTILINESTRING series:
+        one part per maximal run of the line in the polygon's interior or along a ring, in the order the line is walked; a valid row
+        without parts where the two share no piece of positive length; a null row where intersection_length gives NaN.  Coordinates
+        are the line's or the polygon's own, bit for bit, or crossings within 1e-9 of the pair's box diagonal of both carriers.
+        self is LINESTRING / MULTILINESTRING, other POLYGON / MULTIPOLYGON."""
+        return self._line_clip("intersection", _abi.CLIP_INSIDE, other, other_rows)
+
+    def difference(self, other: "GeoSeries", other_rows=None) -> "GeoSeries":
+        """The piece of every row's line outside its polygon other[other_rows[i]] — outside every part or inside a hole — closed
+        (gpk_line_clip); shaped and ruled like `intersection`."""
+        return self._line_clip("difference", _abi.CLIP_OUTSIDE, other, other_rows)
+
     # ---- line x line relations (gpk_lineline.hip) ------------------------------------------------
     def line_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
         """The exact relation mask (uint8) of every row's line A against its line B = other[other_rows[i]] (gpk_line_relation), under
@@ -1037,6 +1055,30 @@ def intersection_measure_args(op: str, first, a: GeoSeries, b: GeoSeries, rows) 
     if len(a) != len(b):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
     return None
+
+
+def line_clip_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
+    """the checks of intersection / difference before any device call: lines x polygons (the measures exist for the other families),
+    then the row map as in intersection_measure_args"""
+    fa, fb = a._family(), b._family()
+    if fa not in LINEAL or fb not in POLYGONAL:
+        swap = ": the lines come first, swap the arguments" if fa in POLYGONAL and fb in LINEAL else ""
+        raise _mismatch(
+            f"{op}: LineString | MultiLineString x Polygon | MultiPolygon (found {_abi_name(fa)} x {_abi_name(fb)}){swap}; the other "
+            "families have intersection_area / intersection_length, not the geometry"
+        )
+    return intersection_measure_args(op, LINEAL, a, b, rows)
+
+
+def line_clip_call(lines, polys, line_rows, poly_rows, n_rows: int, rows_space: int, mode: int, flags: int, out_src, src_space: int, stream=None) -> GeoSeries:
+    """gpk_line_clip on two DeviceGeoArrays and raw row-list pointers: the owned MULTILINESTRING result as a device-resident series"""
+    h = C.c_void_p()
+    _abi.check(_abi.lib().gpk_line_clip(lines.handle, polys.handle, line_rows, poly_rows, n_rows, rows_space, mode, flags, out_src, src_space, stream, C.byref(h)))
+    dev = DeviceGeoArray(h.value, GEOM_MULTILINESTRING, 0, -1)
+    sizes = (C.c_int64 * 4)()
+    _abi.check(_abi.lib().gpk_geoarray_download(dev.handle, sizes, None, None, None, None, stream))
+    dev.n_coords, dev.n_geoms = int(sizes[0]), int(sizes[3])
+    return GeoSeries(None, device=dev)
 
 
 def intersection_min_measure_arg(min_measure) -> float:

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import MEM_DEVICE, MEM_HOST, PREDICATES
-from .geoarrow import DeviceGeoArray
+from .geoarrow import DeviceGeoArray, GeoArrowArray
 from .geoseries import (
     LINEAL,
     POLYGONAL,
@@ -40,6 +40,7 @@ from .geoseries import (
     dwithin_distance_arg,
     intersection_families_arg,
     intersection_min_measure_arg,
+    line_clip_call,
     relation_sides,
 )
 
@@ -816,6 +817,79 @@ def spatial_join_intersection(lhs, rhs, options: Optional[SpatialJoinIntersectio
         return intersection_min_measure_arg(options.min_measure)
 
     return _payload_table_join("intersection join", lhs, rhs, options, family_arg, intersection_measure_pairs, value_col=options.measure_col)
+
+
+# ---- clip lines to polygons over a pair list (gpk_line_clip) ------------------------------------------------------------------------
+
+CLIP_MODES = {"intersection": _abi.CLIP_INSIDE, "difference": _abi.CLIP_OUTSIDE}
+
+
+def line_clip_mode_arg(how: str, lines_family: int, polys_family: int) -> int:
+    """The GPK_CLIP_* mode of `how`, checked before any device call together with the families: lines x polygons, in that order."""
+    if how not in CLIP_MODES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"line clip: unknown how {how!r}: one of {sorted(CLIP_MODES)}")
+    if lines_family not in LINEAL or polys_family not in POLYGONAL:
+        swap = ": the lines come first, swap the arguments" if lines_family in POLYGONAL and polys_family in LINEAL else ""
+        raise _mismatch(
+            f"line clip: LineString | MultiLineString x Polygon | MultiPolygon (found {_abi_name(lines_family)} x {_abi_name(polys_family)}){swap}; "
+            "the other families have intersection_area / intersection_length, not the geometry"
+        )
+    return CLIP_MODES[how]
+
+
+def line_clip_pairs(lines: GeoSeries, polys: GeoSeries, l_idx, r_idx, how: str = "intersection", drop_empty: bool = False):
+    """clip(lines[l_idx[k]], polys[r_idx[k]]) for every pair k, as a MULTILINESTRING GeoSeries (gpk_line_clip): what
+    lines.intersection / difference gives row-wise, over an explicit pair list.  An index past the end of its column gives a null row.
+    With `drop_empty` the rows without parts and the null rows are left out and the result is (series, src), src[k] (int32) = the pair
+    of output row k."""
+    mode = line_clip_mode_arg(how, lines._family(), polys._family())
+    try:
+        li, ri = np.ascontiguousarray(l_idx, dtype=np.uint32), np.ascontiguousarray(r_idx, dtype=np.uint32)
+    except (TypeError, ValueError, OverflowError):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "line clip: the pair lists must be arrays of row numbers") from None
+    if li.ndim != 1 or li.shape != ri.shape:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"line clip: {li.size} line rows for {ri.size} polygon rows")
+    n = len(li)
+    src = np.empty(n, dtype=np.int32) if drop_empty else None
+    if n == 0:  # (no pair, no call: a NULL list would mean the identity)
+        z = np.zeros(1, dtype=np.int32)
+        out = GeoSeries(GeoArrowArray(_abi.GEOM_MULTILINESTRING, np.zeros((0, 2)), geom_offsets=z, ring_offsets=z.copy(), n_geoms=0))
+    else:
+        out = line_clip_call(lines.device(), polys.device(), li.ctypes.data, ri.ctypes.data, n, MEM_HOST, mode,
+                             _abi.CLIP_DROP_EMPTY if drop_empty else 0, src.ctypes.data if drop_empty else None, MEM_HOST)
+    return (out, src[: len(out)]) if drop_empty else out
+
+
+def line_clip_pairs_device(lines: DeviceGeoArray, polys: DeviceGeoArray, l_idx, r_idx, how: str = "intersection", drop_empty: bool = False,
+                           out_src=None, stream: int = 0) -> GeoSeries:
+    """Device-buffer variant: l_idx, r_idx (n,) uint32-as-int32 torch CUDA tensors (at least one row; None = the identity over that
+    column), out_src an optional (n,) int32 CUDA tensor for the map of `drop_empty`; enqueued on `stream`.  Returns the series."""
+    mode = line_clip_mode_arg(how, lines.geom_type, polys.geom_type)
+    n = l_idx.shape[0] if l_idx is not None else (r_idx.shape[0] if r_idx is not None else lines.n_geoms)
+    return line_clip_call(lines, polys, _ptr(l_idx), _ptr(r_idx), n, MEM_DEVICE, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0, _ptr(out_src),
+                          MEM_DEVICE, stream)
+
+
+@dataclass
+class SpatialJoinClipArgs:
+    """Options of spatial_join_clip."""
+
+    r_index: Optional[SpatialIndex] = None  # an index of `right` carrying the bbox grid
+
+
+def spatial_join_clip(left: GeoSeries, right: GeoSeries, args: Optional[SpatialJoinClipArgs] = None):
+    """GeoPandas' overlay(lines, polys, how="intersection", keep_geom_type=True) as a pair list: gpk_line_polygon_join(intersects),
+    then gpk_line_clip over the returned pairs, empty results dropped.  Either side may hold the lines.  Returns (l, r, geometry):
+    int64 row numbers of `left` and `right`, sorted by (l, r), for the pairs that share a piece of positive length, and that piece of
+    the LINE as a MULTILINESTRING GeoSeries — a pair that only touches is in the join and not here."""
+    args = args or SpatialJoinClipArgs()
+    line_left = relation_sides("clip join", left._family(), right._family())
+    pairs, _counts, _masks = relation_pairs(left, right, "intersects", args.r_index)
+    lines, polys = (left, right) if line_left else (right, left)
+    li, pi = (pairs[:, 0], pairs[:, 1]) if line_left else (pairs[:, 1], pairs[:, 0])
+    geometry, src = line_clip_pairs(lines, polys, li, pi, "intersection", drop_empty=True)
+    kept = pairs[src]
+    return kept[:, 0].astype(np.int64), kept[:, 1].astype(np.int64), geometry
 
 
 # ---- line x line predicate join (gpk_line_relation_join) ---------------------------------------------------------------------

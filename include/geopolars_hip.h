@@ -803,6 +803,38 @@ int32_t gpk_intersection_measure_join(const gpk_geoarray* left, const gpk_geoarr
                                       uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_measure,
                                       int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
 
+/* ---- clip lines to polygons (gpk_lineclip.hip) --------------------------------------------------------------------------------------
+ * The piece of a line that lies inside a polygonal geometry, or outside it: GeoPandas GeoSeries.intersection / difference and
+ * overlay(how="intersection") on lines x polygons.  csrc/gpk_lineclip.h has the rule. */
+#define GPK_CLIP_INSIDE  0   /* L ∩ P, P closed: pieces in P's interior or along a ring */
+#define GPK_CLIP_OUTSIDE 1   /* closure of L \ P: pieces in P's exterior (outside every part, or inside a hole) */
+#define GPK_CLIP_DROP_EMPTY 1 /* flag */
+/* Output row k = clip(lines[line_rows[k]], polys[poly_rows[k]]), k < n_rows.  `lines` LINESTRING | MULTILINESTRING, `polys` POLYGON |
+ * MULTIPOLYGON; any other family: GPK_ERR_MISMATCHED_GEOMETRY (for polygonal x lineal the message says to swap the arguments).  A NULL
+ * row list is the identity: n_rows must then equal that column's row count.  Both lists live in `rows_space`.  An unknown mode,
+ * unknown flag bits, a wrong count, out_src without GPK_CLIP_DROP_EMPTY: GPK_ERR_INVALID_ARGUMENT.  Every refusal comes before any
+ * device work.
+ *   *out   a callee-owned MULTILINESTRING column that does not view its inputs (free with gpk_geoarray_free): one row per pair, in pair
+ *          order.  A part is a maximal run of kept pieces within one coordinate sequence of the line: the run's first point, the
+ *          line's coordinates strictly inside it, its last point; parts in the order the line is walked; runs are not merged across
+ *          the closing coordinate of a closed sequence nor across members; a stretch the line covers twice is emitted twice.
+ *   empty  a pair with no piece of positive length gives a valid row with zero parts
+ *   null   (validity 0) for the conditions gpk_intersection_measure answers with NaN — either row null, without a coordinate / a
+ *          non-empty member, a ring that fails the ring rule of gpk_polygon_relation, a NaN or infinite line coordinate — and for a row
+ *          index past the end of its column
+ *   GPK_CLIP_DROP_EMPTY   rows with zero parts and null rows are left out; out_src[k] (int32, `src_space`, may be NULL; room for
+ *          n_rows entries) names the input pair of output row k, the part gpk_explode's out_parent plays
+ * Every output coordinate is a coordinate of the line or a vertex of the polygon, bit for bit, or a computed crossing within
+ * 1e-9 * d of the line's segment and of the ring edge, d = the diagonal of the pair's joint box, at any placement and any crossing
+ * angle.  When every two distinct transition points of a segment are at least 1e-6 * |segment| apart, the number of parts and the
+ * coordinates per part are those of the exact result; below that the output's point set is within 1e-9 * d of the exact one.  Invalid
+ * polygons: unspecified, the call terminates.  A result whose parts or coordinates do not fit i32 offsets: GPK_ERR_INVALID_ARGUMENT (as
+ * gpk_geoarray_concat), found after the count pass, nothing stays allocated.  The call waits once, for the sizes of the result; the
+ * result's buffers are stream-ordered.  Rows of many thousand coordinates run on the same 16 lanes as any other: correct and slow. */
+int32_t gpk_line_clip(const gpk_geoarray* lines, const gpk_geoarray* polys, const uint32_t* line_rows, const uint32_t* poly_rows,
+                      int64_t n_rows, int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, void* stream,
+                      gpk_geoarray** out);
+
 /* ---- line x line relations (gpk_lineline.hip) ---------------------------------------------------------------------------------------
  * How two lineal geometries lie to each other.  A, B = LINESTRING or MULTILINESTRING rows, each the closed point set of all its
  * segments and coordinates.  Boundary (the mod-2 rule): every non-empty member of a row counts its first and its last coordinate once

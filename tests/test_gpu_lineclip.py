@@ -1,0 +1,285 @@
+"""GPU: clip lines to polygons (gpk_line_clip, csrc/gpk_lineclip.hip) against the exact rational reference (tests/lineclip_ref.py;
+tests/test_lineclip_ref.py pins it) and against the kernels the library already has.
+
+Contract (include/geopolars_hip.h): offsets and validity exactly; coordinates of the line and vertices of the polygon bit for bit; a
+computed crossing within 1e-9 * d of its segment and of its ring edge, d = the diagonal of the pair's joint box.
+
+  1. every fixture row, both modes, both placements, both lane-group sizes; 2. the hand cases by name; 3. near-coincident transitions;
+  4. cross-checks against intersection_length, euclidean_length and the relation mask on 20 000 random pairs; 5. row lists, an
+  out-of-range index, DROP_EMPTY with out_src; 6. many blocks; 7. the join."""
+import numpy as np
+import pytest
+import torch
+
+from geopolars_amd import _abi, synth
+from geopolars_amd.geoarrow import GeoArrowArray
+from geopolars_amd.geoseries import GeoSeries
+from geopolars_amd.spatial_index import line_clip_pairs, line_clip_pairs_device, relation_pairs, spatial_join_clip
+from tests import exact_ref as X
+from tests import lineclip_ref as L
+from tests import overlay_ref as O
+
+pytestmark = pytest.mark.gpu
+
+LS, MLS, PG, MPG = L.LS, L.MLS, L.PG, L.MPG
+FAMILY_IDS = [f"{L.NAMES[a]}-{L.NAMES[b]}" for a, b in L.FAMILIES]
+HOW = {L.INSIDE: "intersection", L.OUTSIDE: "difference"}
+N_BALLAST = 8
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(L.GOLDEN)
+
+
+def dense_square(x0, y0, side, step=0.125):
+    """a square with a vertex every `step` along its edges (exact in doubles)"""
+    t = np.arange(0.0, side, step)
+    z, s = np.zeros_like(t), np.full_like(t, side)
+    xy = np.concatenate([np.stack([t, z], 1), np.stack([s, t], 1), np.stack([side - t, s], 1), np.stack([z, side - t], 1), [[0.0, 0.0]]])
+    return xy + [x0, y0]
+
+
+def with_ballast(col: GeoArrowArray, k: int) -> GeoArrowArray:
+    """the polygon column with k more rows, dense squares of 2049 coordinates that no pair names: they lift the column's mean
+    coordinate count past LP_G_MEAN = 32, and with it the lane group from 4 to 16"""
+    ring = dense_square(0.0, 0.0, 64.0)
+    n0 = col.n_geoms
+    xy, go, po, ro = col.xy, col.geom_offsets, col.part_offsets, col.ring_offsets
+    for _ in range(k):
+        xy = np.concatenate([xy, ring])
+        ro = np.append(ro, len(xy)).astype(np.int32)
+        if col.geom_type == PG:
+            go = np.append(go, len(ro) - 1).astype(np.int32)
+        else:
+            po = np.append(po, len(ro) - 1).astype(np.int32)
+            go = np.append(go, len(po) - 1).astype(np.int32)
+    valid = np.concatenate([col.is_valid(), np.ones(k, dtype=bool)])
+    out = GeoArrowArray(col.geom_type, xy, geom_offsets=go, part_offsets=po, ring_offsets=ro, validity=np.packbits(valid, bitorder="little"))
+    assert out.n_geoms == n0 + k
+    return out
+
+
+def lanes_of(polys: GeoArrowArray) -> int:
+    """the lane-group size the launch picks: 16 from a mean of 32 coordinates a polygon row"""
+    return 16 if polys.n_coords / max(polys.n_geoms, 1) >= 32.0 else 4
+
+
+def columns(golden, kl, kp, lanes, offset):
+    cl, cp = L.load(golden, kl, kp, offset)
+    both = cp if lanes == 4 else with_ballast(cp, N_BALLAST)
+    assert lanes_of(both) == lanes, (both.n_coords, both.n_geoms)
+    return cl, cp, GeoSeries(cl), GeoSeries(both)
+
+
+# ---- 1. every fixture row ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("placement", ["lattice", "georeferenced"])
+@pytest.mark.parametrize("lanes", [4, 16])
+@pytest.mark.parametrize("mode", [L.INSIDE, L.OUTSIDE], ids=["inside", "outside"])
+@pytest.mark.parametrize("kl,kp", L.FAMILIES, ids=FAMILY_IDS)
+def test_every_fixture_row(golden, kl, kp, mode, lanes, placement):
+    """offsets, validity and tags exactly, (a) / (b) coordinates bit for bit, (c) within the bound — through GeoSeries.intersection /
+    difference with a row map (the ballast rows of the 16-lane column are named by no pair), and once more through device buffers"""
+    offset = (0.0, 0.0) if placement == "lattice" else L.TRANSLATION
+    cl, cp, lines, polys = columns(golden, kl, kp, lanes, offset)
+    rows = np.arange(cl.n_geoms, dtype=np.uint32)
+    got = (lines.intersection if mode == L.INSIDE else lines.difference)(polys, other_rows=rows).array
+    worst = L.check_result(golden, kl, kp, mode, cl, cp, got, offset)
+    print(f"{FAMILY_IDS[L.FAMILIES.index((kl, kp))]} {L.MODES[mode]} G={lanes} {placement}: worst (c) / bound = {worst:.3e}")
+    r = torch.from_numpy(rows.view(np.int32)).cuda()
+    dev = line_clip_pairs_device(lines.device(), polys.device(), None, r, HOW[mode]).array
+    assert dev.xy.tobytes() == got.xy.tobytes() and (dev.ring_offsets == got.ring_offsets).all() and (dev.geom_offsets == got.geom_offsets).all()
+    assert (dev.is_valid() == got.is_valid()).all()
+
+
+# ---- 2. the hand cases ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lanes", [4, 16])
+def test_hand_cases(lanes):
+    """the smallest shapes that can go wrong, by name, with their part counts stated by hand (they are rows of the fixture too)"""
+    kl, kp = MLS, MPG
+    lines, polys, lv, pv, names = L.rows(kl, kp)
+    want = L.hand_expectations(kl, kp)
+    idx = list(want) + [names.index(s) for s in ("a null line", "a null polygon", "an empty line", "an empty polygon")]
+    cl = X.column(kl, [lines[i] for i in idx], [lv[i] for i in idx])
+    cp = X.column(kp, [polys[i] for i in idx], [pv[i] for i in idx])
+    if lanes == 16:
+        cp = with_ballast(cp, N_BALLAST)
+    assert lanes_of(cp) == lanes
+    rows = np.arange(len(idx), dtype=np.uint32)
+    inside, outside = GeoSeries(cl).intersection(GeoSeries(cp), rows).array, GeoSeries(cl).difference(GeoSeries(cp), rows).array
+    for k, i in enumerate(idx[: len(want)]):
+        got = (int(np.diff(inside.geom_offsets)[k]), int(np.diff(outside.geom_offsets)[k]))
+        assert got == want[i], (names[i], got, want[i])
+    assert not inside.is_valid()[len(want):].any() and not outside.is_valid()[len(want):].any()
+    assert inside.is_valid()[: len(want)].all() and (np.diff(inside.geom_offsets)[len(want):] == 0).all()
+    # three parts from one segment, with their coordinates
+    k = [names[i] for i in idx].index("through two holes: three inside parts from one segment")
+    p0 = inside.geom_offsets[k]
+    c0, c1 = inside.ring_offsets[p0], inside.ring_offsets[p0 + 3]
+    assert (inside.xy[c0:c1] == [[0, 6], [4, 6], [8, 6], [12, 6], [16, 6], [20, 6]]).all()
+
+
+# ---- 3. near-coincident transitions ----------------------------------------------------------------------------------------------------
+def test_near_coincident_transitions():
+    """Doubles, not the lattice: a sliver of the polygon whose two edges cross the segment a few ulps of t apart, at many places and
+    widths, in both directions.  Below the 1e-6 gap the contract promises the point set only: through the lengths — the inside piece
+    is the sliver's width at the line within 2e-9 * d, inside + outside is the whole line within 2e-9 * length(L) — and every part
+    has at least two coordinates.  A misordered pair of transitions must not invert the rest of the segment."""
+    rng = np.random.default_rng(77)
+    lines, polys, width = [], [], []
+    for k in range(256):
+        x0 = float(rng.uniform(0.1, 0.9))
+        eps = float(np.spacing(x0) * int(rng.integers(1, 5)))
+        # a body below the line with a sliver through it: apex above the line, the two feet 2 eps apart on the body's top
+        ring = [(-1.0, -2.0), (2.0, -2.0), (2.0, -1.0), (x0 + eps, -1.0), (x0, 1.0), (x0 - eps, -1.0), (-1.0, -1.0), (-1.0, -2.0)]
+        seq = [(0.0, 0.0), (1.0, 0.0)] if k % 2 == 0 else [(1.0, 0.0), (0.0, 0.0)]
+        if k % 4 >= 2:
+            seq = [(seq[0][0], -0.5)] + seq + [(seq[1][0], 0.5)]
+        lines.append(seq)
+        polys.append([ring])
+        width.append(eps)  # the sliver is 2 eps wide at y = -1 and 0 at y = 1: eps at the line
+    sl, sp = GeoSeries(X.column(LS, lines)), GeoSeries(X.column(PG, polys))
+    inside, outside = sl.intersection(sp), sl.difference(sp)
+    for s in (inside.array, outside.array):
+        assert s.is_valid().all() and (np.diff(s.ring_offsets) >= 2).all()
+    total, li, lo = sl.euclidean_length(), inside.euclidean_length(), outside.euclidean_length()
+    d = np.hypot(3.0, 3.0)
+    assert (np.abs(li + lo - total) <= 2e-9 * total).all(), float(np.abs(li + lo - total).max())
+    assert (np.abs(li - np.array(width)) <= 2e-9 * d).all(), float(np.abs(li - np.array(width)).max())
+    assert (np.diff(outside.array.geom_offsets) <= 2).all() and (np.diff(inside.array.geom_offsets) <= 1).all()
+
+
+# ---- 4. cross-checks against the kernels the library already has ------------------------------------------------------------------------
+def test_cross_checks_on_random_pairs():
+    """20 000 star x polyline pairs: the intersecting pairs of a join plus random (mostly disjoint) ones.  length(intersection) is
+    intersection_length and inside + outside is the whole line, each within 2e-9 * length(L) (both sides carry 1e-9); a non-empty
+    intersection implies `intersects`; the difference is empty exactly for covered_by rows."""
+    polys, lines = GeoSeries(synth.star_polygons(400, 24, seed=5)), GeoSeries(synth.random_linestrings(3000, seed=6, max_log2=5.0))
+    pairs, _, _ = relation_pairs(lines, polys, "intersects")
+    rng = np.random.default_rng(8)
+    n = 20000
+    assert 1000 < len(pairs) < n
+    extra = np.stack([rng.integers(0, len(lines), n - len(pairs)), rng.integers(0, len(polys), n - len(pairs))], axis=1).astype(np.uint32)
+    pairs = np.concatenate([pairs, extra])
+    li, pi = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    sub_l = GeoSeries(lines.array.take(li.astype(np.int64)))
+    inside, outside = line_clip_pairs(lines, polys, li, pi, "intersection"), line_clip_pairs(lines, polys, li, pi, "difference")
+    total, want = sub_l.euclidean_length(), sub_l.intersection_length(polys, other_rows=pi)
+    len_in, len_out = inside.euclidean_length(), outside.euclidean_length()
+    assert (np.abs(len_in - want) <= 2e-9 * total).all(), float((np.abs(len_in - want) / total).max())
+    assert (np.abs(len_in + len_out - total) <= 2e-9 * total).all(), float((np.abs(len_in + len_out - total) / total).max())
+    mask = sub_l.line_polygon_relation(polys, other_rows=pi)
+    has_in, has_out = np.diff(inside.array.geom_offsets) > 0, np.diff(outside.array.geom_offsets) > 0
+    assert ((mask & 3) != 0)[has_in].all()
+    assert (~has_out == ((mask != 0) & ((mask & 4) == 0))).all()
+    assert has_in.sum() > 1000 and (~has_in).sum() > 1000
+
+
+# ---- 5. row lists --------------------------------------------------------------------------------------------------------------------
+def _rows_of(col: GeoArrowArray, sel):
+    """the bytes of the selected rows of a MULTILINESTRING column, row by row"""
+    g, r = col.geom_offsets, col.ring_offsets
+    return [(bool(col.is_valid()[i]), (np.diff(r[g[i]:g[i + 1] + 1])).tolist() if g[i + 1] > g[i] else [], col.xy[r[g[i]]:r[g[i + 1]]].tobytes()) for i in sel]
+
+
+@pytest.mark.parametrize("mode", [L.INSIDE, L.OUTSIDE], ids=["inside", "outside"])
+def test_row_lists_and_drop_empty(golden, mode):
+    """permuted line_rows and poly_rows give the rows of the identity call; an index past the end of either column gives a null row;
+    with DROP_EMPTY the column is the undropped one with its empty and null rows removed, byte for byte, and out_src names them"""
+    kl, kp = MLS, MPG
+    cl, cp = L.load(golden, kl, kp)
+    lines, polys = GeoSeries(cl), GeoSeries(cp)
+    base = (lines.intersection if mode == L.INSIDE else lines.difference)(polys).array
+    n = cl.n_geoms
+    perm = np.random.default_rng(3).permutation(n).astype(np.uint32)
+    got = line_clip_pairs(lines, polys, perm, perm, HOW[mode]).array
+    assert _rows_of(got, range(n)) == _rows_of(base, perm)
+    li, pi = np.concatenate([perm, [n, 0, 2**32 - 1]]).astype(np.uint32), np.concatenate([perm, [0, cp.n_geoms, 1]]).astype(np.uint32)
+    got = line_clip_pairs(lines, polys, li, pi, HOW[mode]).array
+    assert _rows_of(got, range(n)) == _rows_of(base, perm)
+    assert not got.is_valid()[n:].any() and (np.diff(got.geom_offsets)[n:] == 0).all()
+    dropped, src = line_clip_pairs(lines, polys, li, pi, HOW[mode], drop_empty=True)
+    keep = np.nonzero(got.is_valid() & (np.diff(got.geom_offsets) > 0))[0]
+    assert 0 < len(keep) < n and (src == keep).all() and src.dtype == np.int32
+    d = dropped.array
+    assert d.is_valid().all() and _rows_of(d, range(len(keep))) == _rows_of(got, keep)
+    assert d.xy.tobytes() == got.xy.tobytes() and (d.ring_offsets == got.ring_offsets).all()  # only entries of geom_offsets went
+    # device buffers, the map on the device
+    src_dev = torch.full((len(li),), -1, dtype=torch.int32, device="cuda")
+    dd = line_clip_pairs_device(lines.device(), polys.device(), torch.from_numpy(li.view(np.int32)).cuda(), torch.from_numpy(pi.view(np.int32)).cuda(),
+                                HOW[mode], drop_empty=True, out_src=src_dev)
+    torch.cuda.synchronize()
+    assert (src_dev.cpu().numpy()[: len(dd)] == keep).all() and dd.array.xy.tobytes() == d.xy.tobytes()
+    assert (dd.array.geom_offsets == d.geom_offsets).all()
+
+
+def test_refusals_with_real_handles(golden):
+    """the family and count refusals of the library itself, and a result that is empty"""
+    cl, cp = L.load(golden, LS, PG)
+    lines, polys = GeoSeries(cl), GeoSeries(cp)
+    import ctypes as C
+
+    lib, out = _abi.lib(), C.c_void_p()
+    call = lambda a, b, n, mode=0, flags=0: lib.gpk_line_clip(a.device().handle, b.device().handle, None, None, n, _abi.MEM_HOST, mode, flags, None,  # noqa: E731
+                                                             _abi.MEM_HOST, None, C.byref(out))
+    assert call(polys, lines, len(lines)) == _abi.GPK_ERR_MISMATCHED_GEOMETRY and "swap" in _abi.last_error()
+    assert call(lines, lines, len(lines)) == _abi.GPK_ERR_MISMATCHED_GEOMETRY and call(polys, polys, len(lines)) == _abi.GPK_ERR_MISMATCHED_GEOMETRY
+    assert call(lines, polys, len(lines) - 1) == _abi.GPK_ERR_INVALID_ARGUMENT
+    short = GeoSeries(X.column(PG, [[O.S10]]))
+    assert call(lines, short, len(lines)) == _abi.GPK_ERR_INVALID_ARGUMENT and not out.value
+    far = GeoSeries(X.column(LS, [[(100, 100), (101, 101)]])).intersection(short)
+    assert len(far) == 1 and far.array.is_valid().all() and len(far.array.xy) == 0 and far.array.ring_offsets.tolist() == [0]
+
+
+# ---- 6. many blocks ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_pairs", [4099, 70001])
+def test_many_blocks(golden, n_pairs):
+    """The fixture rows tiled to 4 099 and to 70 001 pairs: ragged last blocks, output offsets far past one scan tile, empty and null rows
+    in between.  Every tile's rows must be the base rows, byte for byte.  The grids are uncapped, one group per pair: there is no capped
+    loop to take past its first pass."""
+    kl, kp = MLS, MPG
+    cl, cp = L.load(golden, kl, kp)
+    lines, polys = GeoSeries(cl), GeoSeries(cp)
+    base = lines.intersection(polys).array
+    n = cl.n_geoms
+    idx = (np.arange(n_pairs) % n).astype(np.uint32)
+    got = line_clip_pairs(lines, polys, idx, idx, "intersection").array
+    full, rem = divmod(n_pairs, n)
+    bg, br = base.geom_offsets, base.ring_offsets
+    n_parts = np.concatenate([np.tile(np.diff(bg), full), np.diff(bg)[:rem]])
+    assert (np.diff(got.geom_offsets) == n_parts).all() and got.geom_offsets[0] == 0
+    sizes = np.concatenate([np.tile(np.diff(br), full), np.diff(br)[: bg[rem]]])
+    assert (np.diff(got.ring_offsets) == sizes).all() and got.ring_offsets[0] == 0
+    xy = np.concatenate([np.tile(base.xy, (full, 1)), base.xy[: br[bg[rem]]]])
+    assert got.xy.tobytes() == xy.tobytes()
+    assert (got.is_valid() == np.concatenate([np.tile(base.is_valid(), full), base.is_valid()[:rem]])).all()
+    dropped, src = line_clip_pairs(lines, polys, idx, idx, "intersection", drop_empty=True)
+    keep = np.nonzero(n_parts > 0)[0]
+    assert (src == keep).all() and dropped.array.xy.tobytes() == xy.tobytes() and (np.diff(dropped.array.geom_offsets) == n_parts[keep]).all()
+
+
+# ---- 7. the join ---------------------------------------------------------------------------------------------------------------------
+def test_spatial_join_clip():
+    """on the join fixture of overlay_ref.join_rows: the pairs are exactly the reference's pairs with positive length, a subset of the
+    intersects join; the geometry is, byte for byte, the row-wise call on the same pairs; the lines may be on either side"""
+    z = np.load(O.GOLDEN)
+    lines, right = GeoSeries(O.unpack(z, "join_lines_", LS)), GeoSeries(O.unpack(z, "join_right_", PG))
+    table = z["join_length"]
+    table = table[table[:, 2] > 0]
+    table = table[np.lexsort((table[:, 1], table[:, 0]))]
+    want = table[:, :2].astype(np.int64)
+    l, r, geom = spatial_join_clip(lines, right)
+    assert (np.stack([l, r], axis=1) == want).all() and len(want) > 50
+    joined, _, _ = relation_pairs(lines, right, "intersects")
+    assert len(joined) > len(want) and {tuple(p) for p in want.tolist()} <= {tuple(p) for p in joined.astype(np.int64).tolist()}
+    rowwise = line_clip_pairs(lines, right, l, r, "intersection").array
+    g = geom.array
+    assert g.xy.tobytes() == rowwise.xy.tobytes() and (g.ring_offsets == rowwise.ring_offsets).all() and (g.geom_offsets == rowwise.geom_offsets).all()
+    assert g.is_valid().all() and (np.diff(g.geom_offsets) > 0).all()
+    # (each end of a part is within 1e-9 * d of the exact one, d < 450: the whole fixture spans less; the sum itself rounds at 1e-16)
+    assert (np.abs(geom.euclidean_length() - table[:, 2]) <= 2e-9 * 450.0 * np.diff(g.geom_offsets) + 1e-12 * table[:, 2]).all()
+    l2, r2, geom2 = spatial_join_clip(right, lines)  # the polygons on the left: pairs sorted by (polygon, line), the piece still the line's
+    order = np.lexsort((l, r))
+    assert (l2 == r[order]).all() and (r2 == l[order]).all()
+    back = line_clip_pairs(lines, right, r2, l2, "intersection").array
+    assert geom2.array.xy.tobytes() == back.xy.tobytes() and (geom2.array.geom_offsets == back.geom_offsets).all()
