@@ -46,6 +46,7 @@ QUERY_CONTAINED, QUERY_INTERSECTING = 0, 1  # gpk_index_query_envelope modes
 PREDICATES = {"intersects": PRED_INTERSECTS, "contains": PRED_CONTAINS, "within": PRED_WITHIN}
 LP_INTERIOR, LP_BOUNDARY, LP_EXTERIOR = 1, 2, 4  # GPK_LP_*: the bits of the line x polygon relation mask
 LP_PRED_INTERSECTS, LP_PRED_WITHIN, LP_PRED_COVERED_BY, LP_PRED_CROSSES, LP_PRED_TOUCHES = 0, 1, 2, 3, 4  # GPK_LP_PRED_*
+TRI_OK, TRI_EMPTY, TRI_FAILED = 0, 1, 2  # GPK_TRI_*: the row status of gpk_triangulate
 CLIP_INSIDE, CLIP_OUTSIDE, CLIP_DROP_EMPTY = 0, 1, 1  # GPK_CLIP_*: the two modes of gpk_line_clip and its flag
 PP_INTERIORS, PP_BOUNDARIES, PP_A_OUTSIDE, PP_B_OUTSIDE = 1, 2, 4, 8  # GPK_PP_*: the bits of the polygon x polygon relation mask
 (PP_PRED_INTERSECTS, PP_PRED_WITHIN, PP_PRED_CONTAINS, PP_PRED_TOUCHES, PP_PRED_OVERLAPS, PP_PRED_EQUALS,
@@ -216,6 +217,7 @@ _PROTOS = {
     ),
     "gpk_validity": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_is_simple": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
+    "gpk_triangulate": (C.c_int32, [_VP, _VP, C.c_int64, _VP, _VP, C.POINTER(C.c_int64), C.c_int32, _VP]),
     "gpk_closest_point_rowwise": (C.c_int32, [_VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_line_locate_point": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP]),
     "gpk_line_interpolate_point": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int32, _VP]),

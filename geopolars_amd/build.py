@@ -46,6 +46,7 @@ SOURCES = [
     "gpk_lineclip.hip",
     "gpk_lineline.hip",
     "gpk_validity.hip",
+    "gpk_triangulate.hip",
     "gpk_interior.hip",
     "gpk_hull.hip",
     "gpk_minbound.hip",

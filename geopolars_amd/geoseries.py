@@ -707,6 +707,44 @@ class GeoSeries:
             _abi.check(_abi.lib().gpk_is_simple(self.device().handle, out.ctypes.data, MEM_HOST, None))
         return out.astype(bool)
 
+    # ---- triangulation (gpk_triangulate.hip) -------------------------------------------------------
+    def triangulate(self, return_status: bool = False):
+        """Every row of a POLYGON or MULTIPOLYGON column as triangles over the column's own coordinate buffer (gpk_triangulate: exact
+        ear clipping, holes bridged, touching rings split): (tri_offsets int32[n + 1], tri_index uint32[T, 3]) — row i owns triangles
+        tri_offsets[i] .. tri_offsets[i + 1], each three indices into the coordinate buffer, counter-clockwise.  With `return_status`
+        also the uint8 TRIANGULATE_STATUS code per row: 0 triangulated, 1 null or empty, 2 failed (an invalid row: see is_valid)."""
+        validity_family_arg("triangulate", self._family(), POLYGONAL)
+        return_status = bool_arg("triangulate", "return_status", return_status)
+        n = len(self)
+        offsets = np.zeros(n + 1, dtype=np.int32)
+        status = np.empty(n, dtype=np.uint8)
+        total = C.c_int64(0)
+        index = np.empty((0, 3), dtype=np.uint32)
+        if n:
+            h = self.device().handle
+            _abi.check(_abi.lib().gpk_triangulate(h, None, 0, offsets.ctypes.data, status.ctypes.data, C.byref(total), MEM_HOST, None))
+            index = np.empty((int(total.value), 3), dtype=np.uint32)
+            if len(index):
+                _abi.check(_abi.lib().gpk_triangulate(h, index.ctypes.data, len(index), offsets.ctypes.data, status.ctypes.data, C.byref(total), MEM_HOST, None))
+        return (offsets, index, status) if return_status else (offsets, index)
+
+    def triangles(self, return_parents: bool = False):
+        """The triangles of triangulate() as a POLYGON series: one row per triangle, each a closed counter-clockwise ring of four
+        coordinates that are the input's bit for bit (gathered on the device).  With `return_parents` also the int32 row each triangle
+        came from, as in explode."""
+        return_parents = bool_arg("triangles", "return_parents", return_parents)
+        offsets, index = self.triangulate()
+        import torch
+
+        xy = torch.from_numpy(self.array.xy).cuda()
+        corners = torch.from_numpy(index.astype(np.int64)).cuda()[:, [0, 1, 2, 0]]
+        rings = xy[corners.reshape(-1)].cpu().numpy().reshape(-1, 2)
+        t = len(index)
+        out = GeoSeries(GeoArrowArray(GEOM_POLYGON, rings, geom_offsets=np.arange(t + 1, dtype=np.int32), ring_offsets=np.arange(0, 4 * t + 1, 4, dtype=np.int32)))
+        if not return_parents:
+            return out
+        return out, np.repeat(np.arange(len(self), dtype=np.int32), np.diff(offsets))
+
     # ---- linear referencing (gpk_linref.hip) -----------------------------------------------------
     def _family(self) -> int:
         return self._dev.geom_type if self._array is None else self._array.geom_type
@@ -998,6 +1036,45 @@ def minimum_bounding_circle_device(dev: DeviceGeoArray, out_radius, out_center=N
         _abi.check(_abi.lib().gpk_minimum_bounding_circle(
             dev.handle, None if out_center is None else out_center.data_ptr(), out_radius.data_ptr(),
             None if out_valid is None else out_valid.data_ptr(), _abi.MEM_DEVICE, stream))
+
+
+def bool_arg(op: str, name: str, value) -> bool:
+    """a flag of triangulate / triangles as a bool; anything else is refused here, before any device call"""
+    if not isinstance(value, (bool, np.bool_)):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {name} must be a bool (found {value!r})")
+    return bool(value)
+
+
+TRIANGULATE_STATUS = ("triangulated", "null or empty", "failed")
+
+
+def triangulate_device(dev: DeviceGeoArray, out_index, out_offsets, out_status=None, stream: int = 0) -> int:
+    """Device-buffer variant of triangulate: out_offsets (n + 1,) int32, out_status (n,) uint8 (optional) and out_index (capacity, 3)
+    int32 (the u32 indices: a column has fewer than 2^31 coordinates) torch CUDA tensors are filled in place on `stream`; out_index
+    None is the size query.  Returns the number
+    of triangles; a capacity below it raises GPK_ERR_CAPACITY (n_coords + 3 n_rings always suffices).  One read-back: the total."""
+    if not isinstance(dev, DeviceGeoArray):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "triangulate_device: a DeviceGeoArray is needed")
+    validity_family_arg("triangulate_device", dev.geom_type, POLYGONAL)
+    n = dev.n_geoms
+
+    def ok(t, shape, dtype):
+        return t is not None and tuple(getattr(t, "shape", ())) == shape and str(getattr(t, "dtype", None)) == dtype and t.is_cuda and t.is_contiguous()
+
+    if not ok(out_offsets, (n + 1,), "torch.int32"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"triangulate_device: out_offsets must be a contiguous CUDA tensor of shape {(n + 1,)}, torch.int32")
+    if out_status is not None and not ok(out_status, (n,), "torch.uint8"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"triangulate_device: out_status must be a contiguous CUDA tensor of shape {(n,)}, torch.uint8")
+    cap = 0
+    if out_index is not None:
+        shape = tuple(getattr(out_index, "shape", ()))
+        if len(shape) != 2 or shape[1] != 3 or not ok(out_index, shape, "torch.int32"):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "triangulate_device: out_index must be a contiguous CUDA tensor of shape (capacity, 3), torch.int32")
+        cap = shape[0]
+    total = C.c_int64(0)
+    _abi.check(_abi.lib().gpk_triangulate(dev.handle, None if out_index is None else out_index.data_ptr(), cap, out_offsets.data_ptr(),
+                                          None if out_status is None else out_status.data_ptr(), C.byref(total), _abi.MEM_DEVICE, stream))
+    return int(total.value)
 
 
 def validity_family_arg(op: str, family: int, allowed) -> None:

@@ -932,6 +932,41 @@ int32_t gpk_validity(const gpk_geoarray* a, uint8_t* out_code, int32_t* out_wher
  * null row and a row with a NaN or infinite coordinate.  Exact, stream-ordered and sized like gpk_validity.  out[n_geoms(a)] bytes. */
 int32_t gpk_is_simple(const gpk_geoarray* a, uint8_t* out, int32_t out_space, void* stream);
 
+/* ---- triangulation (gpk_triangulate.hip, the rule: csrc/gpk_triangulate.h) -----------------------------------------------------------
+ * Every polygonal row as triangles over the column's own coordinates: an index buffer for a renderer or a mesh consumer.  `a` is a
+ * POLYGON or MULTIPOLYGON column (any other family: GPK_ERR_MISMATCHED_GEOMETRY, before any device work); both coordinate layouts of an
+ * upload are accepted.  Exact ear clipping: holes are bridged into their shell, rings that touch are split at the touch first.  Every
+ * decision is an exact orientation sign or a coordinate comparison and every choice goes to the lowest node: no tolerance.
+ *   out_tri_offsets[n_geoms + 1]  int32, row i owns triangles out_tri_offsets[i] .. out_tri_offsets[i + 1]
+ *   out_index[3 * tri_capacity]   u32 indices into the column's coordinate buffer — the index space of gpk_validity's out_where —
+ *                                 three a triangle.  NULL: the size query; offsets, status and *n_triangles are still produced.
+ *   out_status[n_geoms]           u8 GPK_TRI_* (may be NULL)
+ *   *n_triangles                  the total, always set; GPK_ERR_CAPACITY when > tri_capacity and indices were asked for.
+ *                                 tri_capacity >= n_coords(a) + 3 * n_rings(a) always suffices: the same expression over one row is
+ *                                 that row's SHARE, a row that would need more is GPK_TRI_FAILED and never writes past it.
+ * Guarantee, for every row gpk_validity gives code 0, at any placement and for either winding of the input rings:
+ *   (a) every index is a coordinate of that row and never a ring's closing coordinate (the ring's first coordinate stands for it);
+ *   (b) every triangle has strictly positive exact orientation;
+ *   (c) the triangulation is conforming on the row's vertex set: by coordinate value a directed triangle edge occurs at most once, an
+ *       edge whose reverse does not occur lies on a ring edge, and no vertex of the row lies in the open interior of a triangle edge
+ *       — no T-junctions, also where a hole touches a shell edge mid-segment or two members touch;
+ *   (d) the exact sum of the triangle areas is the exact area of the row; every member is triangulated on its own;
+ *   (e) a member none of whose rings share a point gives N' + 2 h - 2 triangles (N': its ring positions without closing coordinates and
+ *       consecutive repeats, h: its holes); with s (vertex, open edge of another ring) incidences at most N' + s + 2 h - 2;
+ *   (f) the indices are a function of the figure: identical across lane-group sizes and the work-group path, coordinate layouts, host
+ *       and device buffers, repeated calls, exact translations and power-of-two scalings.
+ * Limits: a valid row whose MEMBERS touch each other in so many points that its nodes pass the share (more than 3 per ring of the
+ * row) is GPK_TRI_FAILED.  A row whose share exceeds 5000 (TRI_LDS_NODES) keeps its list in global scratch, not in LDS: correct and
+ * slow, and the call then takes 32 bytes of scratch per unit of the column's share on top of the 12 it always takes.  Invalid rows (any other validity code — GeoSeries.is_valid tells): the answer is unspecified, the call
+ * terminates, indices stay inside the row, the count inside the share; a row that stalls is GPK_TRI_FAILED with zero triangles.
+ * Stream-ordered, with one read-back (the total).  All outputs live in `out_space`. */
+#define GPK_TRI_OK     0 /* the row's triangles are written */
+#define GPK_TRI_EMPTY  1 /* null row, or no non-empty member: zero triangles */
+#define GPK_TRI_FAILED 2 /* zero triangles: a NaN / infinite coordinate, a ring that fails the ring rule of gpk_polygon_relation,
+                            a row that needs more than its share, or clipping / bridging could not finish (only invalid rows) */
+int32_t gpk_triangulate(const gpk_geoarray* a, uint32_t* out_index, int64_t tri_capacity, int32_t* out_tri_offsets, uint8_t* out_status,
+                        int64_t* n_triangles, int32_t out_space, void* stream);
+
 /* ---- linear referencing (gpk_linref.hip) ------------------------------------------------------------------------------------
  * Where on a geometry the nearest point lies, how far along a line it is, and the point at a measure along a line (geo 0.27
  * ClosestPoint / LineLocatePoint / LineInterpolatePoint; shapely / GeoPandas nearest_points, shortest_line, project, interpolate).
