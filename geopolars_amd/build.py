@@ -44,6 +44,7 @@ SOURCES = [
     "gpk_polyrel.hip",
     "gpk_overlay.hip",
     "gpk_lineclip.hip",
+    "gpk_polyclip.hip",
     "gpk_lineline.hip",
     "gpk_validity.hip",
     "gpk_triangulate.hip",

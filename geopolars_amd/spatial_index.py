@@ -41,6 +41,7 @@ from .geoseries import (
     intersection_families_arg,
     intersection_min_measure_arg,
     line_clip_call,
+    polygon_clip_call,
     relation_sides,
 )
 
@@ -888,6 +889,79 @@ def spatial_join_clip(left: GeoSeries, right: GeoSeries, args: Optional[SpatialJ
     lines, polys = (left, right) if line_left else (right, left)
     li, pi = (pairs[:, 0], pairs[:, 1]) if line_left else (pairs[:, 1], pairs[:, 0])
     geometry, src = line_clip_pairs(lines, polys, li, pi, "intersection", drop_empty=True)
+    kept = pairs[src]
+    return kept[:, 0].astype(np.int64), kept[:, 1].astype(np.int64), geometry
+
+
+# ---- polygon x polygon intersection and difference over a pair list (gpk_polygon_clip) ---------------------------------------------------
+
+PCLIP_MODES = {"intersection": _abi.PCLIP_INTERSECTION, "difference": _abi.PCLIP_DIFFERENCE}
+
+
+def polygon_clip_mode_arg(how: str, a_family: int, b_family: int) -> int:
+    """The GPK_PCLIP_* mode of `how`, checked before any device call together with the families: polygons x polygons."""
+    if how not in PCLIP_MODES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"polygon clip: unknown how {how!r}: one of {sorted(PCLIP_MODES)}")
+    if a_family not in POLYGONAL or b_family not in POLYGONAL:
+        raise _mismatch(f"polygon clip: Polygon | MultiPolygon x Polygon | MultiPolygon (found {_abi_name(a_family)} x {_abi_name(b_family)})")
+    return PCLIP_MODES[how]
+
+
+def polygon_clip_pairs(a: GeoSeries, b: GeoSeries, l_idx, r_idx, how: str = "intersection", drop_empty: bool = False, return_status: bool = False):
+    """clip(a[l_idx[k]], b[r_idx[k]]) for every pair k, as a MULTIPOLYGON GeoSeries (gpk_polygon_clip): what a.polygon_intersection /
+    polygon_difference gives row-wise, over an explicit pair list.  An index past the end of its column gives a null row.  With
+    `drop_empty` the rows without parts and the null rows are left out and src (int32), the pair of every output row, is returned as
+    well; with `return_status` the uint8 status of every PAIR.  Returns the series, or (series[, src][, status])."""
+    mode = polygon_clip_mode_arg(how, a._family(), b._family())
+    try:
+        li, ri = np.ascontiguousarray(l_idx, dtype=np.uint32), np.ascontiguousarray(r_idx, dtype=np.uint32)
+    except (TypeError, ValueError, OverflowError):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "polygon clip: the pair lists must be arrays of row numbers") from None
+    if li.ndim != 1 or li.shape != ri.shape:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"polygon clip: {li.size} rows of a for {ri.size} rows of b")
+    n = len(li)
+    src = np.empty(n, dtype=np.int32) if drop_empty else None
+    status = np.empty(n, dtype=np.uint8) if return_status else None
+    if n == 0:  # (no pair, no call: a NULL list would mean the identity)
+        z = np.zeros(1, dtype=np.int32)
+        out = GeoSeries(GeoArrowArray(_abi.GEOM_MULTIPOLYGON, np.zeros((0, 2)), geom_offsets=z, part_offsets=z.copy(), ring_offsets=z.copy(), n_geoms=0))
+    else:
+        out = polygon_clip_call(a.device(), b.device(), li.ctypes.data, ri.ctypes.data, n, MEM_HOST, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0,
+                                src.ctypes.data if drop_empty else None, MEM_HOST, status.ctypes.data if return_status else None, MEM_HOST)
+    res = (out,) + ((src[: len(out)],) if drop_empty else ()) + ((status,) if return_status else ())
+    return res if len(res) > 1 else out
+
+
+def polygon_clip_pairs_device(a: DeviceGeoArray, b: DeviceGeoArray, l_idx, r_idx, how: str = "intersection", drop_empty: bool = False,
+                              out_src=None, out_status=None, stream: int = 0) -> GeoSeries:
+    """Device-buffer variant: l_idx, r_idx (n,) uint32-as-int32 torch CUDA tensors (at least one row; None = the identity over that
+    column), out_src an optional (n,) int32 CUDA tensor for the map of `drop_empty`, out_status an optional (n,) uint8 CUDA tensor;
+    enqueued on `stream`.  Returns the series."""
+    mode = polygon_clip_mode_arg(how, a.geom_type, b.geom_type)
+    n = l_idx.shape[0] if l_idx is not None else (r_idx.shape[0] if r_idx is not None else a.n_geoms)
+    return polygon_clip_call(a, b, _ptr(l_idx), _ptr(r_idx), n, MEM_DEVICE, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0, _ptr(out_src),
+                             MEM_DEVICE, _ptr(out_status), MEM_DEVICE, stream)
+
+
+@dataclass
+class SpatialJoinOverlayArgs:
+    """Options of spatial_join_overlay."""
+
+    r_index: Optional[SpatialIndex] = None  # an index of `right` carrying the bbox grid
+
+
+def spatial_join_overlay(left: GeoSeries, right: GeoSeries, how: str = "intersection", args: Optional[SpatialJoinOverlayArgs] = None):
+    """GeoPandas' overlay(left, right, how=..., keep_geom_type=True) on two polygon layers as a pair list:
+    gpk_polygon_relation_join(intersects), then gpk_polygon_clip over the returned pairs.  Returns (l, r, geometry): int64 row numbers
+    of `left` and `right`, sorted by (l, r), and a MULTIPOLYGON GeoSeries.
+      "intersection"  the pairs that share AREA, with that area — a pair that only touches is in the join and not here.
+      "difference"    every pair of the join whose left row is not covered by its right row, with left[l] minus right[r]: ONE OUTPUT
+                      ROW PER (l, r) PAIR, not GeoPandas' row-wise fold of a left row over all its partners (left rows without a
+                      partner do not appear either).  The fold is out of scope."""
+    args = args or SpatialJoinOverlayArgs()
+    polygon_clip_mode_arg(how, left._family(), right._family())
+    pairs, _counts, _masks = polygon_relation_pairs(left, right, "intersects", args.r_index)
+    geometry, src = polygon_clip_pairs(left, right, pairs[:, 0], pairs[:, 1], how, drop_empty=True)
     kept = pairs[src]
     return kept[:, 0].astype(np.int64), kept[:, 1].astype(np.int64), geometry
 

@@ -835,6 +835,40 @@ int32_t gpk_line_clip(const gpk_geoarray* lines, const gpk_geoarray* polys, cons
                       int64_t n_rows, int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, void* stream,
                       gpk_geoarray** out);
 
+/* ---- polygon x polygon intersection and difference (gpk_polyclip.hip) ------------------------------------------------------------------
+ * The geometry two polygonal rows share, or the part of the first outside the second: GeoPandas overlay(how="intersection") /
+ * overlay(how="difference") on polygon layers with keep_geom_type=True.  csrc/gpk_polyclip.h has the rule. */
+#define GPK_PCLIP_INTERSECTION 0   /* closure of int(a) ∩ int(b) */
+#define GPK_PCLIP_DIFFERENCE   1   /* closure of int(a) \ b      */
+/* Output row k = clip(a[a_rows[k]], b[b_rows[k]]), k < n_rows.  Both columns POLYGON | MULTIPOLYGON; any other family:
+ * GPK_ERR_MISMATCHED_GEOMETRY.  The row lists, n_rows, rows_space, GPK_CLIP_DROP_EMPTY with out_src, an index past the end of its column
+ * (a null row), the refusals — every one before any device work — and their order are those of gpk_line_clip.
+ *   *out   a callee-owned MULTIPOLYGON column that does not view its inputs (free with gpk_geoarray_free): one row per pair, in pair
+ *          order.  The REGULARISED result, the area part only: points and edges the operands merely share leave no trace.  Rings are
+ *          closed, shells counter-clockwise, holes clockwise; a ring starts at its arc with the smallest key (the boundary of a before
+ *          that of b, then the order of the walk); parts in the order of their shells' keys, each hole with the shell that encloses it.
+ *          Shared boundary comes from a: equal polygons intersect to a, a polygon minus itself is empty, neighbours that share an edge
+ *          intersect to nothing.  Parts that touch at a point stay separate rings.
+ *   empty  a pair with no area in common (intersection), or with a covered by b (difference), gives a valid row with zero parts
+ *   null   (validity 0) for the conditions gpk_intersection_measure answers with NaN, for a row index past the end of its column, and
+ *          for a row of status 4
+ *   out_status[k] (uint8, `status_space`, may be NULL; always per PAIR, also under GPK_CLIP_DROP_EMPTY):
+ *          0 OK; 1 OK, and some output ring touches itself at a point (a hole whose arcs end at a point of its shell fuses into the
+ *          shell: the only case in which gpk_validity may object to an output row); 2 empty; 3 null input; 4 unresolved: the arcs did
+ *          not close into rings — the row is null, never a guessed geometry.
+ * Every output coordinate is a coordinate of a, bit for bit, a coordinate of b, bit for bit, or a computed crossing within 1e-9 * d of
+ * both carrying edges, d = the diagonal of the pair's joint box, at any placement and any crossing angle; a crossing has one value
+ * wherever it is emitted.  When every two distinct transition points of a segment are at least 1e-6 * |segment| apart, parts, rings,
+ * coordinates per ring and ring starts are those of the exact result and status 4 does not occur for OGC-valid operands.  Below that
+ * gap either the point set is within 1e-9 * d of the exact one or the row has status 4.  Invalid polygons: unspecified, the call terminates.  The
+ * result is identical at every placement, for every lane-group size and on every schedule.  A result whose arcs, parts, rings or
+ * coordinates do not fit i32 offsets: GPK_ERR_INVALID_ARGUMENT, found after the counts, nothing stays allocated.  The call waits twice,
+ * for the number of arcs and for the sizes of the result; everything else is stream-ordered.  Rows of many thousand coordinates run on
+ * the same 16 lanes as any other: correct and slow. */
+int32_t gpk_polygon_clip(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* a_rows, const uint32_t* b_rows, int64_t n_rows,
+                         int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, uint8_t* out_status,
+                         int32_t status_space, void* stream, gpk_geoarray** out);
+
 /* ---- line x line relations (gpk_lineline.hip) ---------------------------------------------------------------------------------------
  * How two lineal geometries lie to each other.  A, B = LINESTRING or MULTILINESTRING rows, each the closed point set of all its
  * segments and coordinates.  Boundary (the mod-2 rule): every non-empty member of a row counts its first and its last coordinate once
