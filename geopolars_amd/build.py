@@ -45,6 +45,7 @@ SOURCES = [
     "gpk_overlay.hip",
     "gpk_lineclip.hip",
     "gpk_polyclip.hip",
+    "gpk_polyunion.hip",
     "gpk_lineline.hip",
     "gpk_validity.hip",
     "gpk_triangulate.hip",

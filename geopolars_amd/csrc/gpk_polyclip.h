@@ -87,6 +87,12 @@ GPK_LC_FN bool kept(int cls, int walk, int mode) {
 }
 // arcs of ∂b bound a \ b with the result on their RIGHT: they are emitted backwards
 GPK_LC_FN bool emitted_backwards(int walk, int mode) { return walk == WALK_B && mode == MODE_DIFFERENCE; }
+// The two tables as a type.  The crossing type, the cut test and the device walks take any rule of this shape (gpk_polyunion.h has
+// another one); without one they take this, and compile to what they were.
+struct ClipRule {
+    static GPK_LC_FN bool kept(int cls, int walk, int mode) { return pc::kept(cls, walk, mode); }
+    static GPK_LC_FN bool emitted_backwards(int walk, int mode) { return pc::emitted_backwards(walk, mode); }
+};
 
 // The class of a piece t -> w that runs along the edge a -> b (storage order) of the other row; ccw: the winding of the edge's ring,
 // hole: the ring is a hole of its member.  The other row's interior lies left of a -> b iff the ring is a ccw shell or a cw hole.
@@ -100,11 +106,13 @@ GPK_LC_FN int boundary_class(P2 a, P2 b, P2 t, P2 w, int ccw, bool hole) {
 GPK_LC_FN int looking_back(int cls) { return cls == CLS_BOUNDARY_SAME ? CLS_BOUNDARY_OPP : (cls == CLS_BOUNDARY_OPP ? CLS_BOUNDARY_SAME : cls); }
 
 // The type of a proper crossing with no vertex at the crossing point (lc::crossing_type with this kept table)
-GPK_LC_FN int crossing_type(int side_q, int ccw, bool hole, int walk, int mode) {
+template <class Rule>
+GPK_LC_FN int crossing_type_by(int side_q, int ccw, bool hole, int walk, int mode) {
     const bool q_in_ring = side_q * ccw > 0;
     const int after = q_in_ring != hole ? CLS_INTERIOR : CLS_EXTERIOR, before = q_in_ring != hole ? CLS_EXTERIOR : CLS_INTERIOR;
-    return (kept(after, walk, mode) ? 1 : 0) - (kept(before, walk, mode) ? 1 : 0);
+    return (Rule::kept(after, walk, mode) ? 1 : 0) - (Rule::kept(before, walk, mode) ? 1 : 0);
 }
+GPK_LC_FN int crossing_type(int side_q, int ccw, bool hole, int walk, int mode) { return crossing_type_by<ClipRule>(side_q, ccw, hole, walk, mode); }
 
 // The one coordinate value of the crossing of edge a0 -> a1 of a with edge b0 -> b1 of b (storage order both), around the origin o.
 // a_left: a's interior lies left of a0 -> a1.  The rounded point is then moved, an ulp of one coordinate at a time, onto the closed
@@ -165,10 +173,12 @@ struct Run {
 GPK_LC_FN Run run_start() { return Run{0, false, false, false, false, false, false, P2{0.0, 0.0}}; }
 
 // is a touch point that is no transition a CUT: both pieces kept and neither along an edge of the other row
-GPK_LC_FN bool is_cut(int cls_before, int cls_after, int walk, int mode) {
-    return kept(cls_after, walk, mode) && kept(cls_before, walk, mode) && (cls_before & (CLS_INTERIOR | CLS_EXTERIOR)) != 0 &&
+template <class Rule>
+GPK_LC_FN bool is_cut_by(int cls_before, int cls_after, int walk, int mode) {
+    return Rule::kept(cls_after, walk, mode) && Rule::kept(cls_before, walk, mode) && (cls_before & (CLS_INTERIOR | CLS_EXTERIOR)) != 0 &&
            (cls_after & (CLS_INTERIOR | CLS_EXTERIOR)) != 0;
 }
+GPK_LC_FN bool is_cut(int cls_before, int cls_after, int walk, int mode) { return is_cut_by<ClipRule>(cls_before, cls_after, walk, mode); }
 // A cut of the open run at the input coordinate `id` of segment p -> q; inside: strictly inside the segment (else at p).  Not a
 // transition: the depth stays.
 template <class Sink>
@@ -371,10 +381,11 @@ constexpr int ORDER_SHELL = 1 << 30;  // flag of an entry of the ring order: the
 // The stitcher: the n arcs of a pair (coordinates in xy) into rings, signs and nesting.  Scratch: next, ring_first, order, info — n
 // ints each.  On return next[i] is the arc after arc i in its ring and order[0 .. n_rings) lists the rings in output order, each as
 // the number of its first arc, | ORDER_SHELL when the ring opens a part (the holes of a part follow its shell).  Returns ST_OK,
-// ST_TOUCH, ST_EMPTY (n == 0) or ST_UNRESOLVED (the counts are then 0).
+// ST_TOUCH, ST_EMPTY (n == 0) or ST_UNRESOLVED (the counts are then 0).  innermost (gpk_polyunion.h; left off by the two modes
+// above): a hole goes to the enclosing shell that every other enclosing shell encloses, not to the first one in key order.
 template <class Orient>
 GPK_LC_FN int stitch(const Arc* arcs, int n, const P2* xy, Orient orient, int* next, int* ring_first, int* order, int* info, int& n_parts,
-                     int& n_rings, int& n_coords) {
+                     int& n_rings, int& n_coords, bool innermost = false) {
     n_parts = n_rings = n_coords = 0;
     if (n == 0) return ST_EMPTY;
     bool junction = false;
@@ -440,8 +451,10 @@ GPK_LC_FN int stitch(const Arc* arcs, int n, const P2* xy, Orient orient, int* n
         if (info[r] != -1) continue;
         for (int s = 0; s < nr; ++s)
             if (info[s] == 1 && ring_encloses(arcs, next, xy, ring_first[s], ring_first[r], n, orient)) {
+                // (innermost: a later shell that also encloses the hole takes it when the home so far encloses that shell)
+                if (info[r] != -1 && !ring_encloses(arcs, next, xy, ring_first[info[r] - 2], ring_first[s], n, orient)) continue;
                 info[r] = s + 2;
-                break;
+                if (!innermost) break;
             }
         if (info[r] == -1) return ST_UNRESOLVED;
     }
@@ -526,7 +539,7 @@ struct RowRef {
 };
 
 // One ring of the walked row W (coordinates [rc0, rc0 + n), a hole or not) against the usable row O.  walk: WALK_A when W is a.
-template <int G, class Sink>
+template <int G, class Rule = ClipRule, class Sink>
 __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0, int n, bool is_hole, const DevGeo& O, const RowRef& other,
                                        const DevGeo& A, const DevGeo& B, int walk, int mode, P2 o, int lane, Sink& out) {
     cont::Ring R;
@@ -559,7 +572,7 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                     p = q;
                 }
                 // (a ring that merely touches the other row at its first coordinate is cut there: one arc, but not closed in itself)
-                out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, pp0 == GPK_LP_BOUNDARY && is_cut(last_cls, first_cls0, walk, mode) ? 0 : ARC_WHOLE);
+                out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, pp0 == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first_cls0, walk, mode) ? 0 : ARC_WHOLE);
                 return;
             }
         }
@@ -581,8 +594,8 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                 pp0 = pp;
                 first_cls0 = first;
             }
-            run_segment_begin(run, kept(first, walk, mode), lc::p2(p), lc::p2(q), seg, walk, out);
-            if (had && pp == GPK_LP_BOUNDARY && is_cut(last_cls, first, walk, mode)) run_cut(run, end_at_coord(lc::p2(p)), false, lc::p2(p), lc::p2(q), seg, walk, out);
+            run_segment_begin(run, Rule::kept(first, walk, mode), lc::p2(p), lc::p2(q), seg, walk, out);
+            if (had && pp == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first, walk, mode)) run_cut(run, end_at_coord(lc::p2(p)), false, lc::p2(p), lc::p2(q), seg, walk, out);
             if (lap == 1 && !run.open) return;  // the head (or the run into it) has ended
             if (lap == 1) run.stop = true;      // from here on the first break ends the walk
             const double lx = fmin(p.x, q.x), hx = fmax(p.x, q.x), ly = fmin(p.y, q.y), hy = fmax(p.y, q.y);
@@ -595,9 +608,9 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                     const double2 a = make_double2(e.a.x, e.a.y), b = make_double2(e.b.x, e.b.y);
                     if (e.kind == 0) {
                         const int after = piece_class<G>(O, other.p0, other.p1, a, q, lane), before = looking_back(piece_class<G>(O, other.p0, other.p1, a, p, lane));
-                        const int type = (kept(after, walk, mode) ? 1 : 0) - (kept(before, walk, mode) ? 1 : 0);
+                        const int type = (Rule::kept(after, walk, mode) ? 1 : 0) - (Rule::kept(before, walk, mode) ? 1 : 0);
                         if (type) run_transition(run, type, end_at_coord(e.a), lc::p2(p), lc::p2(q), seg, walk, out);
-                        else if (is_cut(before, after, walk, mode)) run_cut(run, end_at_coord(e.a), true, lc::p2(p), lc::p2(q), seg, walk, out);
+                        else if (is_cut_by<Rule>(before, after, walk, mode)) run_cut(run, end_at_coord(e.a), true, lc::p2(p), lc::p2(q), seg, walk, out);
                     } else if (!lp::vertex_at_crossing<G>(O.xy, other.c0, other.c1, p, q, lx, hx, ly, hy, a, b, lane)) {
                         int ccw;
                         bool hole;
@@ -609,7 +622,7 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                         // the other walk sees as a vertex on its open segment: the same identity and value here)
                         const int own = vertex_at_crossing_index<G>(W.xy, w.c0, w.c1, p, q, lx, hx, ly, hy, a, b, lane);
                         const End id = own != 0x7fffffff ? end_at_coord(lc::p2(W.xy[own])) : End{x.x, x.y, ea, eb};
-                        run_transition(run, crossing_type(cont::orient(a, b, q), ccw, hole, walk, mode), id, lc::p2(p), lc::p2(q), seg, walk, out);
+                        run_transition(run, crossing_type_by<Rule>(cont::orient(a, b, q), ccw, hole, walk, mode), id, lc::p2(p), lc::p2(q), seg, walk, out);
                     }
                     if (lap == 1 && !run.open) return;
                 }
@@ -625,7 +638,7 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
     if (run.open && run.emit) out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, 0);
 }
 
-template <int G, class Sink>
+template <int G, class Rule = ClipRule, class Sink>
 __device__ inline void walk_row_group(const DevGeo& W, const RowRef& w, const DevGeo& O, const RowRef& other, const DevGeo& A, const DevGeo& B,
                                       int walk, int mode, P2 o, int lane, Sink& out) {
     for (int pt = w.p0; pt < w.p1; ++pt) {
@@ -634,7 +647,7 @@ __device__ inline void walk_row_group(const DevGeo& W, const RowRef& w, const De
         for (int r = r0; r < r1; ++r) {
             const int c0 = W.ring_off[r], n = W.ring_off[r + 1] - c0;
             if (n == 0) continue;
-            walk_ring_group<G>(W, w, c0, n, r > r0, O, other, A, B, walk, mode, o, lane, out);
+            walk_ring_group<G, Rule>(W, w, c0, n, r > r0, O, other, A, B, walk, mode, o, lane, out);
         }
     }
 }
@@ -651,13 +664,13 @@ __device__ inline bool row_ref(const DevGeo& P, int64_t i, int lane, RowRef& r) 
 }
 
 // The arcs of clip(a[i], b[j]) into `out` (called with the same arguments on every lane of the group).  False: a null result row.
-template <int G, class Sink>
+template <int G, class Rule = ClipRule, class Sink>
 __device__ inline bool arcs_group(const DevGeo& a, int64_t i, const DevGeo& b, int64_t j, int mode, int lane, Sink& out) {
     RowRef ra, rb;
     if (!row_ref<G>(a, i, lane, ra) || !row_ref<G>(b, j, lane, rb)) return false;
     const P2 o = lc::local_origin(ra.box.x, ra.box.y, ra.box.z, ra.box.w, rb.box.x, rb.box.y, rb.box.z, rb.box.w);
-    walk_row_group<G>(a, ra, b, rb, a, b, WALK_A, mode, o, lane, out);
-    walk_row_group<G>(b, rb, a, ra, a, b, WALK_B, mode, o, lane, out);
+    walk_row_group<G, Rule>(a, ra, b, rb, a, b, WALK_A, mode, o, lane, out);
+    walk_row_group<G, Rule>(b, rb, a, ra, a, b, WALK_B, mode, o, lane, out);
     return true;
 }
 

@@ -652,11 +652,11 @@ class GeoSeries:
         return self._line_clip("difference", _abi.CLIP_OUTSIDE, other, other_rows)
 
     # ---- polygon x polygon intersection and difference (gpk_polyclip.hip) --------------------------
-    def _polygon_clip(self, op: str, mode: int, other: "GeoSeries", other_rows, return_status: bool):
+    def _polygon_clip(self, op: str, mode: int, other: "GeoSeries", other_rows, return_status: bool, entry: str = "gpk_polygon_clip"):
         rows = polygon_clip_args(op, self, other, other_rows)
         status = np.empty(len(self), dtype=np.uint8) if return_status else None
         out = polygon_clip_call(self.device(), other.device(), None, None if rows is None else rows.ctypes.data, len(self), MEM_HOST, mode, 0, None,
-                                MEM_HOST, None if status is None else status.ctypes.data, MEM_HOST)
+                                MEM_HOST, None if status is None else status.ctypes.data, MEM_HOST, entry=entry)
         return (out, status) if return_status else out
 
     def polygon_intersection(self, other: "GeoSeries", other_rows=None, return_status: bool = False):
@@ -673,6 +673,77 @@ class GeoSeries:
         """The area of every row's polygon outside other[other_rows[i]], closed (gpk_polygon_clip): the regularised difference, the
         closure of int(a) minus b; a valid row without parts where b covers a.  Shaped and ruled like `polygon_intersection`."""
         return self._polygon_clip("polygon_difference", _abi.PCLIP_DIFFERENCE, other, other_rows, return_status)
+
+    # ---- polygon x polygon union and the grouped union (gpk_polyunion.hip) ---------------------------
+    def polygon_union(self, other: "GeoSeries", other_rows=None, return_status: bool = False):
+        """The area every row's polygon or other[other_rows[i]] covers (gpk_polygon_union), as a MULTIPOLYGON series: neighbours that
+        share an edge merge across it, rows that only touch at points stay separate parts, a hole goes to the innermost shell around
+        it.  A null row where `polygon_intersection` gives one — also where either row has no coordinate: an empty row is not the
+        neutral element here (`union_all` drops such rows first).  Coordinates, status and shapes as `polygon_intersection`."""
+        return self._polygon_clip("polygon_union", _abi.PUNION_UNION, other, other_rows, return_status, entry="gpk_polygon_union")
+
+    def union_all(self, by=None, return_status: bool = False):
+        """The union of the polygons of every group, one MULTIPOLYGON row per group in ascending group id (GeoPandas union_all /
+        dissolve); `by`: an integer array, one entry per row (None: one group).  A tree reduction over gpk_polygon_union: rows that
+        are null or have no coordinate are dropped first (a group with none left gives an EMPTY row, not null); each round unites
+        rows 2i and 2i + 1 of every group's current list, an odd last row passes through, for ceil(log2(largest group)) rounds.  The
+        pairing of a round is made on the device (gpk_union_all_pairs); the rounds' results are appended to a device-resident pool
+        column (gpk_geoarray_concat) that the next round's row lists index, and nothing but two counts a round leaves the device.
+        Every result row leaves through one last union of the row with itself, which returns its own coordinates.  With
+        `return_status`: (series, status), the worst status a group met (uint8; 0 OK, 1 some ring touches itself, 2 an empty group,
+        3 / 4 a null row: an invalid ring, or a round that did not resolve).  A status-1 intermediate is fed onward as it is: the
+        result is then whatever gpk_polygon_union says for such input."""
+        groups, n_groups = union_all_groups(self, by)
+        host = self.array
+        rows0 = _union_all_live_rows(host, groups)
+        status = np.full(n_groups, _abi.PCLIP_EMPTY, dtype=np.uint8)
+        z = np.zeros(1, dtype=np.int32)
+        empty = GeoArrowArray(_abi.GEOM_MULTIPOLYGON, np.zeros((0, 2)), geom_offsets=np.zeros(n_groups + 1, dtype=np.int32), part_offsets=z,
+                              ring_offsets=z.copy(), n_geoms=n_groups)
+        if len(rows0) == 0:
+            out = GeoSeries(empty)
+            return (out, status) if return_status else out
+        import torch
+
+        lib = _abi.lib()
+        pool = DeviceGeoArray.upload(_as_multipolygon(host.take(rows0)))
+        dev = torch.device("cuda")
+        group = torch.from_numpy(groups[rows0].astype(np.int32)).to(dev)
+        rows, pool_status = None, torch.zeros(len(rows0), dtype=torch.uint8, device=dev)
+        counts = (C.c_int64 * 2)()
+        while True:
+            n = group.shape[0]
+            a_rows, b_rows = (torch.empty(max(n // 2, 1), dtype=torch.int32, device=dev) for _ in range(2))
+            next_group, next_rows = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+            _abi.check(lib.gpk_union_all_pairs(group.data_ptr(), None if rows is None else rows.data_ptr(), n, pool.n_geoms, a_rows.data_ptr(),
+                                               b_rows.data_ptr(), next_group.data_ptr(), next_rows.data_ptr(), counts, None))
+            n_pairs, n_next = int(counts[0]), int(counts[1])
+            if n_pairs == 0:
+                break
+            a_rows, b_rows = a_rows[:n_pairs], b_rows[:n_pairs]
+            st = torch.empty(n_pairs, dtype=torch.uint8, device=dev)
+            united = polygon_clip_call(pool, pool, a_rows.data_ptr(), b_rows.data_ptr(), n_pairs, _abi.MEM_DEVICE, _abi.PUNION_UNION, 0, None,
+                                       _abi.MEM_DEVICE, st.data_ptr(), _abi.MEM_DEVICE, entry="gpk_polygon_union")
+            st = torch.maximum(st, torch.maximum(pool_status[a_rows.long()], pool_status[b_rows.long()]))
+            pool_status = torch.cat([pool_status, st])
+            pool, _bases = DeviceGeoArray.concat([pool, united.device()])
+            group, rows = next_group[:n_next], next_rows[:n_next]
+        if rows is None:
+            rows = torch.arange(group.shape[0], dtype=torch.int32, device=dev)
+        n = rows.shape[0]
+        st = torch.empty(n, dtype=torch.uint8, device=dev)
+        last = polygon_clip_call(pool, pool, rows.data_ptr(), rows.data_ptr(), n, _abi.MEM_DEVICE, _abi.PUNION_UNION, 0, None, _abi.MEM_DEVICE,
+                                 st.data_ptr(), _abi.MEM_DEVICE, entry="gpk_polygon_union").array
+        present = group.cpu().numpy()
+        status[present] = torch.maximum(st, pool_status[rows.long()]).cpu().numpy()
+        parts = np.zeros(n_groups, dtype=np.int64)
+        parts[present] = np.diff(last.geom_offsets)
+        valid = np.ones(n_groups, dtype=bool)
+        valid[present] = status[present] < _abi.PCLIP_NULL
+        out = GeoSeries(GeoArrowArray(_abi.GEOM_MULTIPOLYGON, last.xy, geom_offsets=np.concatenate([[0], np.cumsum(parts)]).astype(np.int32),
+                                      part_offsets=last.part_offsets, ring_offsets=last.ring_offsets,
+                                      validity=None if valid.all() else np.packbits(valid, bitorder="little"), n_geoms=n_groups))
+        return (out, status) if return_status else out
 
     # ---- line x line relations (gpk_lineline.hip) ------------------------------------------------
     def line_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
@@ -1187,13 +1258,46 @@ def polygon_clip_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.
     return intersection_measure_args(op, POLYGONAL, a, b, rows)
 
 
+def union_all_groups(a: GeoSeries, by) -> tuple[np.ndarray, int]:
+    """the checks of union_all before any device call: a polygonal column, `by` None or a 1-D integer array with one entry per row.
+    Returns (the rank of every row's group among the ascending distinct ids, the number of groups); None is one group."""
+    if a._family() not in POLYGONAL:
+        raise _mismatch(f"union_all: Polygon | MultiPolygon (found {_abi_name(a._family())})")
+    if by is None:
+        return np.zeros(len(a), dtype=np.int64), 1
+    ids = np.asarray(by)
+    if ids.dtype.kind not in "iu" or ids.ndim != 1:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"union_all: `by` must be a 1-D integer array (found {ids.dtype}, {ids.ndim}-D)")
+    if len(ids) != len(a):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"union_all: {len(ids)} group ids for {len(a)} rows")
+    distinct, rank = np.unique(ids, return_inverse=True)
+    return rank.astype(np.int64).reshape(-1), len(distinct)
+
+
+def _union_all_live_rows(host: GeoArrowArray, groups: np.ndarray) -> np.ndarray:
+    """the rows of a polygonal host column that are valid and have a coordinate, ordered by group (stable)"""
+    g = host.geom_offsets.astype(np.int64)
+    rings = g if host.geom_type == GEOM_POLYGON else host.part_offsets.astype(np.int64)[g]
+    coords = host.ring_offsets.astype(np.int64)[rings]
+    live = np.nonzero(host.is_valid() & (np.diff(coords) > 0))[0]
+    return live[np.argsort(groups[live], kind="stable")]
+
+
+def _as_multipolygon(host: GeoArrowArray) -> GeoArrowArray:
+    """a POLYGON host column as a MULTIPOLYGON one of one member a row (offset surgery; a MULTIPOLYGON column is returned as it is)"""
+    if host.geom_type != GEOM_POLYGON:
+        return host
+    return GeoArrowArray(_abi.GEOM_MULTIPOLYGON, host.xy, geom_offsets=np.arange(host.n_geoms + 1, dtype=np.int32), part_offsets=host.geom_offsets,
+                         ring_offsets=host.ring_offsets, validity=host.validity, n_geoms=host.n_geoms)
+
+
 def polygon_clip_call(a, b, a_rows, b_rows, n_rows: int, rows_space: int, mode: int, flags: int, out_src, src_space: int, out_status=None,
-                      status_space: int = MEM_HOST, stream=None) -> GeoSeries:
-    """gpk_polygon_clip on two DeviceGeoArrays and raw row-list / output pointers: the owned MULTIPOLYGON result as a device-resident
-    series"""
+                      status_space: int = MEM_HOST, stream=None, entry: str = "gpk_polygon_clip") -> GeoSeries:
+    """gpk_polygon_clip (or, as `entry`, gpk_polygon_union, which takes the same arguments) on two DeviceGeoArrays and raw row-list /
+    output pointers: the owned MULTIPOLYGON result as a device-resident series"""
     h = C.c_void_p()
-    _abi.check(_abi.lib().gpk_polygon_clip(a.handle, b.handle, a_rows, b_rows, n_rows, rows_space, mode, flags, out_src, src_space, out_status,
-                                           status_space, stream, C.byref(h)))
+    _abi.check(getattr(_abi.lib(), entry)(a.handle, b.handle, a_rows, b_rows, n_rows, rows_space, mode, flags, out_src, src_space, out_status,
+                                          status_space, stream, C.byref(h)))
     dev = DeviceGeoArray(h.value, _abi.GEOM_MULTIPOLYGON, 0, -1)
     sizes = (C.c_int64 * 4)()
     _abi.check(_abi.lib().gpk_geoarray_download(dev.handle, sizes, None, None, None, None, stream))

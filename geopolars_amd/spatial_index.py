@@ -913,12 +913,18 @@ def polygon_clip_pairs(a: GeoSeries, b: GeoSeries, l_idx, r_idx, how: str = "int
     `drop_empty` the rows without parts and the null rows are left out and src (int32), the pair of every output row, is returned as
     well; with `return_status` the uint8 status of every PAIR.  Returns the series, or (series[, src][, status])."""
     mode = polygon_clip_mode_arg(how, a._family(), b._family())
+    return _polygon_pairs("gpk_polygon_clip", mode, a, b, l_idx, r_idx, drop_empty, return_status)
+
+
+def _polygon_pairs(entry: str, mode: int, a: GeoSeries, b: GeoSeries, l_idx, r_idx, drop_empty: bool, return_status: bool):
+    """polygon_clip_pairs / polygon_union_pairs once the mode and the families are checked"""
+    label = "polygon clip" if entry == "gpk_polygon_clip" else "polygon union"
     try:
         li, ri = np.ascontiguousarray(l_idx, dtype=np.uint32), np.ascontiguousarray(r_idx, dtype=np.uint32)
     except (TypeError, ValueError, OverflowError):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "polygon clip: the pair lists must be arrays of row numbers") from None
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{label}: the pair lists must be arrays of row numbers") from None
     if li.ndim != 1 or li.shape != ri.shape:
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"polygon clip: {li.size} rows of a for {ri.size} rows of b")
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{label}: {li.size} rows of a for {ri.size} rows of b")
     n = len(li)
     src = np.empty(n, dtype=np.int32) if drop_empty else None
     status = np.empty(n, dtype=np.uint8) if return_status else None
@@ -927,7 +933,7 @@ def polygon_clip_pairs(a: GeoSeries, b: GeoSeries, l_idx, r_idx, how: str = "int
         out = GeoSeries(GeoArrowArray(_abi.GEOM_MULTIPOLYGON, np.zeros((0, 2)), geom_offsets=z, part_offsets=z.copy(), ring_offsets=z.copy(), n_geoms=0))
     else:
         out = polygon_clip_call(a.device(), b.device(), li.ctypes.data, ri.ctypes.data, n, MEM_HOST, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0,
-                                src.ctypes.data if drop_empty else None, MEM_HOST, status.ctypes.data if return_status else None, MEM_HOST)
+                                src.ctypes.data if drop_empty else None, MEM_HOST, status.ctypes.data if return_status else None, MEM_HOST, entry=entry)
     res = (out,) + ((src[: len(out)],) if drop_empty else ()) + ((status,) if return_status else ())
     return res if len(res) > 1 else out
 
@@ -941,6 +947,36 @@ def polygon_clip_pairs_device(a: DeviceGeoArray, b: DeviceGeoArray, l_idx, r_idx
     n = l_idx.shape[0] if l_idx is not None else (r_idx.shape[0] if r_idx is not None else a.n_geoms)
     return polygon_clip_call(a, b, _ptr(l_idx), _ptr(r_idx), n, MEM_DEVICE, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0, _ptr(out_src),
                              MEM_DEVICE, _ptr(out_status), MEM_DEVICE, stream)
+
+
+# ---- polygon x polygon union over a pair list (gpk_polygon_union) ---------------------------------------------------------------------
+
+PUNION_MODES = {"union": _abi.PUNION_UNION}
+
+
+def polygon_union_mode_arg(how: str, a_family: int, b_family: int) -> int:
+    """The GPK_PUNION_* mode of `how`, checked before any device call together with the families: polygons x polygons."""
+    if how not in PUNION_MODES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"polygon union: unknown how {how!r}: one of {sorted(PUNION_MODES)}")
+    if a_family not in POLYGONAL or b_family not in POLYGONAL:
+        raise _mismatch(f"polygon union: Polygon | MultiPolygon x Polygon | MultiPolygon (found {_abi_name(a_family)} x {_abi_name(b_family)})")
+    return PUNION_MODES[how]
+
+
+def polygon_union_pairs(a: GeoSeries, b: GeoSeries, a_rows, b_rows, how: str = "union", drop_empty: bool = False, return_status: bool = False):
+    """union(a[a_rows[k]], b[b_rows[k]]) for every pair k, as a MULTIPOLYGON GeoSeries (gpk_polygon_union): what a.polygon_union gives
+    row-wise, over an explicit pair list.  Arguments, `drop_empty`, `return_status` and the returned tuple as polygon_clip_pairs."""
+    mode = polygon_union_mode_arg(how, a._family(), b._family())
+    return _polygon_pairs("gpk_polygon_union", mode, a, b, a_rows, b_rows, drop_empty, return_status)
+
+
+def polygon_union_pairs_device(a: DeviceGeoArray, b: DeviceGeoArray, a_rows, b_rows, how: str = "union", drop_empty: bool = False, out_src=None,
+                               out_status=None, stream: int = 0) -> GeoSeries:
+    """Device-buffer variant, shaped like polygon_clip_pairs_device."""
+    mode = polygon_union_mode_arg(how, a.geom_type, b.geom_type)
+    n = a_rows.shape[0] if a_rows is not None else (b_rows.shape[0] if b_rows is not None else a.n_geoms)
+    return polygon_clip_call(a, b, _ptr(a_rows), _ptr(b_rows), n, MEM_DEVICE, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0, _ptr(out_src), MEM_DEVICE,
+                             _ptr(out_status), MEM_DEVICE, stream, entry="gpk_polygon_union")
 
 
 @dataclass

@@ -869,6 +869,39 @@ int32_t gpk_polygon_clip(const gpk_geoarray* a, const gpk_geoarray* b, const uin
                          int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, uint8_t* out_status,
                          int32_t status_space, void* stream, gpk_geoarray** out);
 
+/* ---- polygon x polygon union, and the pairing of a grouped union (gpk_polyunion.hip) -----------------------------------------------------
+ * The area either of two polygonal rows covers: GeoPandas GeoSeries.union on polygon columns, area part only.
+ * csrc/gpk_polyunion.h has the rule: that of gpk_polygon_clip with another kept table and another choice of a hole's shell. */
+#define GPK_PUNION_UNION 0   /* closure of int(a) ∪ int(b), merged across shared boundary */
+/* Output row k = union(a[a_rows[k]], b[b_rows[k]]), k < n_rows.  The 14 arguments are those of gpk_polygon_clip, in the same order and
+ * with the same meaning, and so is everything but what the mode computes: the families (POLYGON | MULTIPOLYGON on both sides, else
+ * GPK_ERR_MISMATCHED_GEOMETRY), the row lists, GPK_CLIP_DROP_EMPTY with out_src, out_status 0 to 4, the refusals — every one before
+ * any device work — and their order, the two waits, the i32 offset overflow error, the owned MULTIPOLYGON column, ring orientation,
+ * ring starts and part order, and the contract on coordinates (input coordinates bit for bit, crossings within 1e-9 * d of both
+ * carrying edges, the gap of 1e-6 * |segment|, below which a row is within 1e-9 * d or null with status 4).  Any other mode:
+ * GPK_ERR_INVALID_ARGUMENT.
+ *   union  shared boundary comes from a: equal polygons unite to a.  Neighbours that share an edge merge across it; the input
+ *          coordinates along a merged edge that end a kept piece stay, collinear or not.  Rows that touch at points only unite to
+ *          separate parts, also where they touch twice around a gap (two parts, no hole); a gap closed off by overlap is a hole.  A
+ *          hole goes to the INNERMOST shell that encloses it (a shell of a union can lie inside a hole of another one).
+ *   null   for the same input conditions as gpk_polygon_clip.  That includes a row without a coordinate on either side: the pair-wise
+ *          union does NOT treat an empty row as the neutral element.  Status 2 (empty) does not occur for a row that is not null. */
+int32_t gpk_polygon_union(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* a_rows, const uint32_t* b_rows, int64_t n_rows,
+                          int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, uint8_t* out_status,
+                          int32_t status_space, void* stream, gpk_geoarray** out);
+/* One round of a grouped union (union_all / dissolve) as a tree reduction over gpk_polygon_union: who is united with whom.  The
+ * current rows live in a POOL column (the input rows, then the results of every round, appended with gpk_geoarray_concat), so a row
+ * that passes through is not copied.  All buffers on the device, except out_counts.
+ *   group[n]  the group id of every current row, ascending;  rows[n]  its pool row (NULL: row i is pool row i)
+ *   base      the pool row the result of this round's first pair will have (the pool's length)
+ * Within a group, rows 2j and 2j + 1 form pair; an odd last row passes through.  Out, in the order of the current rows:
+ *   a_rows, b_rows [n / 2]         the pool rows of every pair: the row lists of this round's gpk_polygon_union over (pool, pool)
+ *   next_group, next_rows [n]      the next round's rows: base + k for the result of pair k, its own pool row for a pass-through
+ *   out_counts[2] (host)           the number of pairs, the number of rows of the next round: the call's one read-back (it waits once)
+ * No pair: the reduction is done.  n < 0 or pool rows past 2^32 - 1: GPK_ERR_INVALID_ARGUMENT. */
+int32_t gpk_union_all_pairs(const int32_t* group, const uint32_t* rows, int64_t n, int64_t base, uint32_t* a_rows, uint32_t* b_rows,
+                            int32_t* next_group, uint32_t* next_rows, int64_t* out_counts, void* stream);
+
 /* ---- line x line relations (gpk_lineline.hip) ---------------------------------------------------------------------------------------
  * How two lineal geometries lie to each other.  A, B = LINESTRING or MULTILINESTRING rows, each the closed point set of all its
  * segments and coordinates.  Boundary (the mod-2 rule): every non-empty member of a row counts its first and its last coordinate once
