@@ -16,6 +16,7 @@
 #include <mutex>
 #include <vector>
 
+#include "gpk_column.h"
 #include "gpk_common.h"
 
 // The handful of RCCL declarations this file needs, written out: the library is opened with dlopen, and a ROCm install without
@@ -359,50 +360,22 @@ static int32_t assemble_column(const Shards& S, hipStream_t s, gpk_geoarray** ou
         for (int k = 0; k < W; ++k) row_bases[k + 1] = row_bases[k] + hdr[(size_t)HDR * k + 0];
     }
 
-    gpk_geoarray* a = new gpk_geoarray;
-    memset(a, 0, sizeof *a);
-    a->device = S.local[0]->device;
-    a->d.type = type;
-    a->d.n_geoms = tot[0];
-    a->d.n_parts = has_part ? tot[1] : (is_polygonal(type) ? tot[0] : 0);
-    a->d.n_rings = has_ring ? tot[2] : 0;
-    a->d.n_coords = tot[3];
-    auto done = [&](int32_t rc) {
-        if (rc != GPK_OK) {
-            (void)hipStreamSynchronize(s);
-            gpk_geoarray_free(a);
-        } else {
-            *out = a;
-        }
-        return rc;
-    };
     // ---- every output buffer and all scratch first, then agree that every rank has them: nothing below can fail locally
+    const bool validity = any_valid && tot[0] > 0;
+    Column col("allgatherv", type, S.local[0]->device, s);
+    int32_t rc = col.size(tot[0], tot[1], tot[2], tot[3], validity);
     struct Level {
         bool present;
-        int slot, rows_q, child_q, first_q;  // header columns: rows of this level, rows of its child level (3 = coordinates), first offset
+        int rows_q, child_q, first_q;  // header columns: rows of this level, rows of its child level (3 = coordinates), first offset
         const int32_t* DevGeo::*src;
-        const int32_t** view;
+        int32_t* (Column::*dst)();
     } levels[3] = {
-        {has_geom, 1, 0, has_part ? 1 : (has_ring ? 2 : 3), 6, &DevGeo::geom_off, &a->d.geom_off},
-        {has_part, 2, 1, 2, 7, &DevGeo::part_off, &a->d.part_off},
-        {has_ring, 3, 2, 3, 8, &DevGeo::ring_off, &a->d.ring_off},
+        {has_geom, 0, has_part ? 1 : (has_ring ? 2 : 3), 6, &DevGeo::geom_off, &Column::geom_off},
+        {has_part, 1, 2, 7, &DevGeo::part_off, &Column::part_off},
+        {has_ring, 2, 3, 8, &DevGeo::ring_off, &Column::ring_off},
     };
-    auto alloc = [&](int slot, size_t bytes, const void** view) -> int32_t {
-        void* p = nullptr;
-        const hipError_t e = device_malloc(&p, bytes ? bytes : 8);
-        if (e != hipSuccess) return fail(GPK_ERR_OOM, "allgatherv: device_malloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        a->owned[slot] = p;
-        *view = p;
-        a->nbytes += (int64_t)bytes;
-        return GPK_OK;
-    };
-    int32_t rc = alloc(0, sizeof(double2) * (size_t)tot[3], (const void**)&a->d.xy);
-    for (const Level& L : levels)
-        if (rc == GPK_OK && L.present) rc = alloc(L.slot, sizeof(int32_t) * (size_t)(tot[L.rows_q] + 1), (const void**)L.view);
-    const bool validity = any_valid && tot[0] > 0;
     uint8_t *all_bytes = nullptr, *my_bytes = nullptr;
     int32_t* zero_word = nullptr;
-    if (rc == GPK_OK && validity) rc = alloc(4, (size_t)((tot[0] + 7) / 8), (const void**)&a->d.validity);
     if (rc == GPK_OK) {
         int64_t local_rows = 0;
         for (int k = 0; k < W; ++k)
@@ -417,11 +390,10 @@ static int32_t assemble_column(const Shards& S, hipStream_t s, gpk_geoarray** ou
             if (!zero_word || (validity && (!all_bytes || !my_bytes))) rc = fail(GPK_ERR_OOM, "allgatherv: scratch");
         }
     }
-    rc = agree(S, rc, s);
-    if (rc != GPK_OK) return done(rc);
+    GPK_TRY(agree(S, rc, s));
     {
         const hipError_t e = hipMemsetAsync(zero_word, 0, 256, s);
-        if (e != hipSuccess) return done(fail(GPK_ERR_DEVICE, "allgatherv: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GPK_ERR_DEVICE, "allgatherv: %s", hipGetErrorString(e));
     }
 
     std::vector<int64_t> cnt((size_t)W), begin((size_t)W + 1);
@@ -431,7 +403,7 @@ static int32_t assemble_column(const Shards& S, hipStream_t s, gpk_geoarray** ou
         cnt[(size_t)k] = hdr[(size_t)HDR * k + 3];
         begin[(size_t)k + 1] = begin[(size_t)k] + cnt[(size_t)k];
     }
-    if ((rc = move_pieces(S, [&](int k) { return (const void*)S.mine_or(k).xy; }, cnt.data(), begin.data(), sizeof(double2), (char*)a->owned[0], s)) != GPK_OK) return done(rc);
+    GPK_TRY(move_pieces(S, [&](int k) { return (const void*)S.mine_or(k).xy; }, cnt.data(), begin.data(), sizeof(double2), (char*)col.xy(), s));
     // ---- offsets, outermost first: level `lvl` has rows + 1 entries per shard; its values count the children of the next level
     for (const Level& L : levels) {
         if (!L.present) continue;
@@ -455,8 +427,9 @@ static int32_t assemble_column(const Shards& S, hipStream_t s, gpk_geoarray** ou
             if (!p) return (const void*)zero_word;  // an empty shard without an offsets buffer: its one entry (shard 0 only) is 0
             return (const void*)(k == 0 ? p : p + 1);
         };
-        if ((rc = move_pieces(S, src, cnt.data(), begin.data(), sizeof(int32_t), (char*)a->owned[L.slot], s)) != GPK_OK) return done(rc);
-        if (at > 0) hipLaunchKernelGGL(rebase_offsets_kernel, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, (int32_t*)a->owned[L.slot], ra);
+        int32_t* dst = (col.*(L.dst))();
+        GPK_TRY(move_pieces(S, src, cnt.data(), begin.data(), sizeof(int32_t), (char*)dst, s));
+        if (at > 0) hipLaunchKernelGGL(rebase_offsets_kernel, dim3((unsigned)((at + 255) / 256)), dim3(256), 0, s, dst, ra);
     }
     // ---- validity: one byte per row travels (bit offsets of a shard's rows are not byte-aligned in the gathered bitmap)
     if (validity) {
@@ -475,15 +448,16 @@ static int32_t assemble_column(const Shards& S, hipStream_t s, gpk_geoarray** ou
             cnt[(size_t)k] = hdr[(size_t)HDR * k + 0];
             begin[(size_t)k + 1] = begin[(size_t)k] + cnt[(size_t)k];
         }
-        if ((rc = move_pieces(S, [&](int k) { return (const void*)my_at[(size_t)k]; }, cnt.data(), begin.data(), 1, (char*)all_bytes, s)) != GPK_OK) return done(rc);
-        hipLaunchKernelGGL(bytes_to_bitmap_kernel, dim3((unsigned)(((tot[0] + 7) / 8 + 255) / 256)), dim3(256), 0, s, (const uint8_t*)all_bytes, tot[0], (uint8_t*)a->owned[4]);
+        GPK_TRY(move_pieces(S, [&](int k) { return (const void*)my_at[(size_t)k]; }, cnt.data(), begin.data(), 1, (char*)all_bytes, s));
+        hipLaunchKernelGGL(bytes_to_bitmap_kernel, dim3((unsigned)(((tot[0] + 7) / 8 + 255) / 256)), dim3(256), 0, s, (const uint8_t*)all_bytes, tot[0], col.validity());
     }
-    if (out_bytes) *out_bytes = a->nbytes;
+    if (out_bytes) *out_bytes = col.nbytes();
     {
         const hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done(fail(GPK_ERR_DEVICE, "allgatherv: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GPK_ERR_DEVICE, "allgatherv: %s", hipGetErrorString(e));
     }
-    return done(GPK_OK);
+    col.release(out);
+    return GPK_OK;
 }
 
 }  // namespace gpk

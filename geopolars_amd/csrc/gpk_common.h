@@ -176,6 +176,16 @@ bool debug_sync();  // GPK_DEBUG_SYNC=1: name every launch on stderr and wait fo
 
 int32_t require_device();  // GPK_ERR_DEVICE unless the current device is a gfx950
 int cu_count();
+// hipDeviceSynchronize on `device`, which need not be the calling thread's current one (a handle is freed by whoever holds it)
+inline hipError_t sync_device(int device) {
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != device) (void)hipSetDevice(device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+    return e;
+}
+void free_seq_classes(gpk_geoarray* a);  // the tables derived from the handle's offsets (a->classes), after the device has been waited for
 // The grid of a kernel that gives G lanes of a 256-lane block to a unit (a row, a candidate pair, a sequence) and loops: one block per
 // 256 / G units, capped at 32 blocks a compute unit, at least one.
 inline dim3 group_grid(int64_t n_units, int G) {

@@ -146,13 +146,9 @@ int32_t gpk_index_free(gpk_index* idx) {
     if (!idx) return GPK_OK;
     // (hipFree's implicit wait, once: a join enqueued against this index may still be running — on the device that OWNS the tables,
     // which need not be the calling thread's current one: the blocks go back to a process-wide cache tagged by device)
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (cur != idx->device) (void)hipSetDevice(idx->device);
-    (void)hipDeviceSynchronize();
+    (void)sync_device(idx->device);
     for (int i = 0; i < 24; ++i)
         if (idx->owned[i]) cached_free(idx->owned[i]);
-    if (cur >= 0 && cur != idx->device) (void)hipSetDevice(cur);
     delete idx;
     return GPK_OK;
 }

@@ -7,8 +7,8 @@
 //   2. exclusive scans of the two counts (and, with GPK_CLIP_DROP_EMPTY, of the rows that stay) — gpk_scan.h; their 64-bit totals are
 //      gathered into one record and read back once (d2h_small / sync_small): the only synchronisation of the call.  The totals are
 //      checked against Arrow's i32 offsets before anything is allocated.
-//   3. line_clip_offsets_kernel writes geom_offsets, the validity bitmap and, under DROP_EMPTY, the compaction map and out_src.  For a
-//      MULTILINESTRING column dropping a row without parts only removes an entry of geom_offsets.
+//   3. clip_offsets_kernel (gpk_clipcall.h) writes geom_offsets, the validity bitmap and, under DROP_EMPTY, the compaction map and
+//      out_src.  For a MULTILINESTRING column dropping a row without parts only removes an entry of geom_offsets.
 //   4. fill pass (line_clip_kernel<G, FillSink>): the same routine with the other sink, so both passes make bit-identical decisions;
 //      writes part offsets and coordinates at the pair's scanned positions.  The sink also refuses to write past the pair's counted
 //      share, so a disagreement could only truncate a row, never write out of bounds.
@@ -16,6 +16,7 @@
 // Rows of many thousand coordinates run on the same lanes: correct and slow.
 #include <climits>
 
+#include "gpk_clipcall.h"
 #include "gpk_common.h"
 #include "gpk_device.h"
 #include "gpk_lineclip.h"
@@ -45,12 +46,6 @@ struct FillSink {
         ++at;
     }
 };
-
-// rows[k] or k; an entry past the column's end: -1 (a null row)
-__device__ __forceinline__ int64_t row_of(const uint32_t* __restrict__ rows, int64_t k, int64_t n_geoms) {
-    const int64_t r = rows ? (int64_t)rows[k] : k;
-    return r < n_geoms ? r : -1;
-}
 
 template <int G>
 __global__ __launch_bounds__(256) void line_clip_count_kernel(DevGeo lines, DevGeo polys, const uint32_t* __restrict__ line_rows,
@@ -85,45 +80,6 @@ __global__ __launch_bounds__(256) void line_clip_fill_kernel(DevGeo lines, DevGe
     (void)lc::clip_group<G>(lines, row_of(line_rows, k, lines.n_geoms), polys, row_of(poly_rows, k, polys.n_geoms), mode, lane, sink);
 }
 
-// the three 64-bit totals of the scans in one record
-__global__ void line_clip_totals_kernel(const unsigned long long* __restrict__ parts, const unsigned long long* __restrict__ coords,
-                                        const unsigned long long* __restrict__ rows, unsigned long long* __restrict__ out) {
-    if (threadIdx.x == 0) {
-        out[0] = *parts;
-        out[1] = *coords;
-        out[2] = *rows;
-    }
-}
-
-// geom_offsets, validity and the compaction map.  row_at[k]: the output row of pair k when it stays (keep[k]).
-__global__ __launch_bounds__(256) void line_clip_offsets_kernel(const int32_t* __restrict__ part_start, const int32_t* __restrict__ row_at,
-                                                                const int32_t* __restrict__ keep, const uint8_t* __restrict__ valid, int64_t n,
-                                                                int64_t n_out, int32_t total_parts, int32_t total_coords,
-                                                                int32_t* __restrict__ geom_off, int32_t* __restrict__ part_off,
-                                                                uint8_t* __restrict__ validity, int32_t* __restrict__ out_src) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k == 0) {
-        geom_off[n_out] = total_parts;
-        part_off[total_parts] = total_coords;
-    }
-    if (k < n && keep[k]) {
-        const int64_t row = row_at[k];
-        if (row < n_out) {
-            geom_off[row] = part_start[k];
-            if (out_src) out_src[row] = (int32_t)k;
-        }
-    }
-    // (validity only without DROP_EMPTY: output row == pair; one lane per byte of the bitmap)
-    if (validity && k < (n + 7) / 8) {
-        unsigned bits = 0;
-        for (int b = 0; b < 8; ++b)
-            if (8 * k + b < n && valid[8 * k + b]) bits |= 1u << b;
-        validity[k] = (uint8_t)bits;
-    }
-}
-
-inline dim3 pair_grid(int64_t n, int G) { return dim3((unsigned)((n + (256 / G) - 1) / (256 / G))); }
-
 int32_t check_families(int32_t tl, int32_t tp) {
     if (is_lineal(tl) && is_polygonal(tp)) return GPK_OK;
     if (is_polygonal(tl) && is_lineal(tp))
@@ -140,27 +96,16 @@ using namespace gpk;
 extern "C" int32_t gpk_line_clip(const gpk_geoarray* lines, const gpk_geoarray* polys, const uint32_t* line_rows, const uint32_t* poly_rows,
                                  int64_t n_rows, int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, void* stream,
                                  gpk_geoarray** out) {
-    // (the plain arguments are looked at first: a bad mode or flag is refused whatever else is handed over)
-    if (mode != GPK_CLIP_INSIDE && mode != GPK_CLIP_OUTSIDE) return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: unknown mode %d", mode);
-    if (flags & ~GPK_CLIP_DROP_EMPTY) return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: unknown flag bits 0x%x", flags);
+    GPK_TRY(clip_prologue("line_clip", ClipSide{"line_rows", "line rows"}, ClipSide{"poly_rows", "polygon rows"},
+                          mode == GPK_CLIP_INSIDE || mode == GPK_CLIP_OUTSIDE, mode, flags, out_src, n_rows, lines, polys, line_rows, poly_rows, out,
+                          check_families));
     const bool drop = (flags & GPK_CLIP_DROP_EMPTY) != 0;
-    if (out_src && !drop) return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: out_src is the map of GPK_CLIP_DROP_EMPTY, which is not set");
-    if (n_rows < 0 || n_rows > (int64_t)INT32_MAX) return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: %lld pairs", (long long)n_rows);
-    if (!lines || !polys || !out) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out = nullptr;
-    GPK_TRY(check_families(lines->d.type, polys->d.type));
-    if (!line_rows && n_rows != lines->d.n_geoms)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: %lld pairs without line_rows but %lld line rows", (long long)n_rows, (long long)lines->d.n_geoms);
-    if (!poly_rows && n_rows != polys->d.n_geoms)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: %lld pairs without poly_rows but %lld polygon rows", (long long)n_rows, (long long)polys->d.n_geoms);
-    GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = n_rows, n1 = n > 0 ? n : 1;
 
     // ---- scratch: the per-pair counts, their scans, the scans' block totals, the totals record, staged row lists and out_src
     const size_t i32 = align256(sizeof(int32_t) * (size_t)(n1 + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n1 + 255) / 256 + 2));
-    const bool stage_rows = rows_space != GPK_MEM_DEVICE, stage_src = out_src && src_space != GPK_MEM_DEVICE;
-    GPK_TRY(workspace().begin(7 * i32 + align256((size_t)n1) + 3 * tot + 256 + (stage_rows ? 2 * i32 : 0) + (stage_src ? i32 : 0) + 512));
+    GPK_TRY(workspace().begin(7 * i32 + align256((size_t)n1) + 3 * tot + 256 + clip_staging_bytes(rows_space, out_src, src_space, i32) + 512));
     Workspace& w = workspace();
     int32_t* n_parts = (int32_t*)w.take(i32);
     int32_t* n_coords = (int32_t*)w.take(i32);
@@ -173,97 +118,43 @@ extern "C" int32_t gpk_line_clip(const gpk_geoarray* lines, const gpk_geoarray* 
     unsigned long long* tot_coords = (unsigned long long*)w.take(tot);
     unsigned long long* tot_rows = (unsigned long long*)w.take(tot);
     unsigned long long* totals_dev = (unsigned long long*)w.take(256);
-    const uint32_t *lrows = line_rows, *prows = poly_rows;
-    if (stage_rows && n > 0) {
-        if (line_rows) {
-            uint32_t* r = (uint32_t*)w.take(i32);
-            GPK_HIP(hipMemcpyAsync(r, line_rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            lrows = r;
-        }
-        if (poly_rows) {
-            uint32_t* r = (uint32_t*)w.take(i32);
-            GPK_HIP(hipMemcpyAsync(r, poly_rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            prows = r;
-        }
-    }
-    int32_t* src_dev = stage_src ? (int32_t*)w.take(i32) : out_src;
+    ClipLists in;
+    GPK_TRY(clip_stage_lists(w, line_rows, poly_rows, rows_space, out_src, src_space, n, i32, s, &in));
 
     // ---- 1, 2: count, scan, the one read-back
     const int G = lp::relation_group_size(lines->d, polys->d);
-    unsigned long long totals[3] = {0, 0, 0};
+    unsigned long long totals[4] = {0, 0, 0, 0};  // parts, coordinates, rows that stay
     if (n > 0) {
-        if (G == lp::LP_G_SMALL)
-            GPK_LAUNCH("gpk_line_clip_count", line_clip_count_kernel<lp::LP_G_SMALL>, pair_grid(n, G), dim3(256), 0, s, lines->d, polys->d, lrows, prows, n,
-                       (int)mode, (int)drop, n_parts, n_coords, keep, valid);
-        else
-            GPK_LAUNCH("gpk_line_clip_count", line_clip_count_kernel<lp::LP_G_LARGE>, pair_grid(n, G), dim3(256), 0, s, lines->d, polys->d, lrows, prows, n,
-                       (int)mode, (int)drop, n_parts, n_coords, keep, valid);
+        GPK_LAUNCH_BY_G("gpk_line_clip_count", line_clip_count_kernel<lp::LP_G_SMALL>, line_clip_count_kernel<lp::LP_G_LARGE>, lines->d, polys->d, in.a_rows,
+                        in.b_rows, n, (int)mode, (int)drop, n_parts, n_coords, keep, valid);
         GPK_TRY(exclusive_scan_i32(n_parts, n, part_start, nullptr, tot_parts, s));
         GPK_TRY(exclusive_scan_i32(n_coords, n, coord_start, nullptr, tot_coords, s));
         GPK_TRY(exclusive_scan_i32(keep, n, row_at, nullptr, tot_rows, s));
         const int64_t at = (n + 255) / 256;
-        GPK_LAUNCH("gpk_line_clip_totals", line_clip_totals_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)(tot_parts + at),
-                   (const unsigned long long*)(tot_coords + at), (const unsigned long long*)(tot_rows + at), totals_dev);
-        GPK_HIP(d2h_small(totals, totals_dev, sizeof totals, s));
-        GPK_HIP(sync_small(s));
+        GPK_TRY(clip_read_totals("gpk_line_clip_totals", tot_parts + at, tot_coords + at, tot_rows + at, nullptr, totals_dev, totals, s));
     }
     if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
         return fail(GPK_ERR_INVALID_ARGUMENT, "line_clip: the result exceeds 2^31 - 1 parts / coordinates (Arrow i32 offsets)");
     const int64_t n_out = (int64_t)totals[2];
     const int32_t total_parts = (int32_t)totals[0], total_coords = (int32_t)totals[1];
 
-    // ---- the result column: owned buffers, as gpk_geoarray_concat's
-    gpk_geoarray* a = new gpk_geoarray;
-    memset(a, 0, sizeof *a);
-    (void)hipGetDevice(&a->device);
-    a->d.type = GPK_GEOM_MULTILINESTRING;
-    a->d.n_geoms = n_out;
-    a->d.n_rings = total_parts;
-    a->d.n_coords = total_coords;
-    auto done = [&](int32_t rc) {
-        if (rc != GPK_OK) {
-            (void)hipStreamSynchronize(s);
-            gpk_geoarray_free(a);
-        } else {
-            *out = a;
-        }
-        return rc;
-    };
-    auto alloc = [&](int slot, size_t bytes, const void** view) -> int32_t {
-        void* p = nullptr;
-        const hipError_t e = device_malloc(&p, bytes ? bytes : 8);
-        if (e != hipSuccess) return fail(GPK_ERR_OOM, "line_clip: device_malloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        a->owned[slot] = p;
-        *view = p;
-        a->nbytes += (int64_t)bytes;
-        return GPK_OK;
-    };
-    int32_t rc = alloc(0, sizeof(double2) * (size_t)total_coords, (const void**)&a->d.xy);
-    if (rc == GPK_OK) rc = alloc(1, sizeof(int32_t) * (size_t)(n_out + 1), (const void**)&a->d.geom_off);
-    if (rc == GPK_OK) rc = alloc(3, sizeof(int32_t) * (size_t)(total_parts + 1), (const void**)&a->d.ring_off);
-    if (rc == GPK_OK && !drop && n > 0) rc = alloc(4, (size_t)((n + 7) / 8), (const void**)&a->d.validity);
-    if (rc != GPK_OK) return done(rc);
+    // ---- the result column: a MULTILINESTRING's parts are its ring level
+    int device = 0;
+    (void)hipGetDevice(&device);
+    Column col("line_clip", GPK_GEOM_MULTILINESTRING, device, s);
+    GPK_TRY(col.size(n_out, 0, total_parts, total_coords, !drop && n > 0));
 
     // ---- 3, 4: offsets, fill
-    if (n == 0) {
-        hipError_t e = hipMemsetAsync(a->owned[1], 0, sizeof(int32_t), s);
-        if (e == hipSuccess) e = hipMemsetAsync(a->owned[3], 0, sizeof(int32_t), s);
-        return done(e == hipSuccess ? GPK_OK : fail(GPK_ERR_DEVICE, "line_clip: %s", hipGetErrorString(e)));
+    if (n > 0) {
+        GPK_TRY(clip_write_offsets("gpk_line_clip_offsets", part_start, row_at, keep, valid, n, n_out, 0, total_parts, total_coords, col, in.src, s));
+        if (total_parts > 0)
+            GPK_LAUNCH_BY_G("gpk_line_clip_fill", line_clip_fill_kernel<lp::LP_G_SMALL>, line_clip_fill_kernel<lp::LP_G_LARGE>, lines->d, polys->d, in.a_rows,
+                            in.b_rows, n, (int)mode, (const int32_t*)part_start, (const int32_t*)coord_start, col.ring_off(), col.xy());
+        if (in.src_staged && n_out > 0) GPK_TRY(copy_out(out_src, src_space, in.src, sizeof(int32_t) * (size_t)n_out, s));
+    } else {
+        GPK_TRY(col.zero_offsets());
     }
-    GPK_LAUNCH_OR(done, "gpk_line_clip_offsets", line_clip_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t*)part_start,
-                  (const int32_t*)row_at, (const int32_t*)keep, (const uint8_t*)valid, n, n_out, total_parts, total_coords, (int32_t*)a->owned[1],
-                  (int32_t*)a->owned[3], (uint8_t*)a->owned[4], src_dev);
-    if (total_parts > 0) {
-        if (G == lp::LP_G_SMALL)
-            GPK_LAUNCH_OR(done, "gpk_line_clip_fill", line_clip_fill_kernel<lp::LP_G_SMALL>, pair_grid(n, G), dim3(256), 0, s, lines->d, polys->d, lrows, prows,
-                          n, (int)mode, (const int32_t*)part_start, (const int32_t*)coord_start, (int32_t*)a->owned[3], (double2*)a->owned[0]);
-        else
-            GPK_LAUNCH_OR(done, "gpk_line_clip_fill", line_clip_fill_kernel<lp::LP_G_LARGE>, pair_grid(n, G), dim3(256), 0, s, lines->d, polys->d, lrows, prows,
-                          n, (int)mode, (const int32_t*)part_start, (const int32_t*)coord_start, (int32_t*)a->owned[3], (double2*)a->owned[0]);
-    }
-    if (stage_src && n_out > 0) {
-        rc = copy_out(out_src, src_space, src_dev, sizeof(int32_t) * (size_t)n_out, s);
-        if (rc != GPK_OK) return done(rc);
-    }
-    return done(GPK_OK);
+    col.release(out);
+    return GPK_OK;
 }
+

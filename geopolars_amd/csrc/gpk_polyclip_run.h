@@ -1,7 +1,8 @@
 // gpk_polyclip_run.h — the schedule that gpk_polygon_clip (gpk_polyclip.hip) and gpk_polygon_union (gpk_polyunion.hip) share: the
 // kernels and the host driver, over a rule type (pc::ClipRule, pu::UnionRule) that gives the kept table.  The count and fill kernels
-// and the stitch kernel are instantiated per rule, so each call launches kernels that hold its own table only; the totals, offsets
-// and emit kernels do not depend on the rule.  Contract: include/geopolars_hip.h; the rules: gpk_polyclip.h, gpk_polyunion.h.
+// and the stitch kernel are instantiated per rule, so each call launches kernels that hold its own table only; the emit kernel does
+// not depend on the rule, nor do the checks, the staging, the totals and the offsets kernel it shares with gpk_line_clip
+// (gpk_clipcall.h).  Contract: include/geopolars_hip.h; the rules: gpk_polyclip.h, gpk_polyunion.h.
 //
 // Two sizes are unknown in turn — the arcs, then the rings — so the call is count -> scan -> fill twice over:
 //   1. arc pass, counting (polygon_clip_arcs_kernel<G, CountSink>): G lanes per pair, G = lp::relation_group_size(a, b); walks ∂a
@@ -24,6 +25,7 @@
 
 #include <climits>
 
+#include "gpk_clipcall.h"
 #include "gpk_common.h"
 #include "gpk_device.h"
 #include "gpk_polyclip.h"
@@ -78,11 +80,6 @@ struct FillSink {
         ++arc;
     }
 };
-
-__device__ __forceinline__ int64_t row_of(const uint32_t* __restrict__ rows, int64_t k, int64_t n_geoms) {
-    const int64_t r = rows ? (int64_t)rows[k] : k;
-    return r < n_geoms ? r : -1;
-}
 
 template <int G, class Rule>
 __global__ __launch_bounds__(256) void polygon_clip_count_kernel(DevGeo a, DevGeo b, const uint32_t* __restrict__ a_rows, const uint32_t* __restrict__ b_rows,
@@ -163,45 +160,6 @@ __global__ __launch_bounds__(256) void polygon_clip_stitch_kernel(int64_t n, int
     status[k] = (uint8_t)st;
 }
 
-__global__ void polygon_clip_totals_kernel(const unsigned long long* __restrict__ t0, const unsigned long long* __restrict__ t1,
-                                           const unsigned long long* __restrict__ t2, const unsigned long long* __restrict__ t3,
-                                           unsigned long long* __restrict__ out) {
-    if (threadIdx.x == 0) {
-        out[0] = *t0;
-        out[1] = *t1;
-        out[2] = t2 ? *t2 : 0;
-        out[3] = t3 ? *t3 : 0;
-    }
-}
-
-// geom_offsets, validity and the compaction map.  row_at[k]: the output row of pair k when it stays (keep[k]).
-__global__ __launch_bounds__(256) void polygon_clip_offsets_kernel(const int32_t* __restrict__ part_start, const int32_t* __restrict__ row_at,
-                                                                   const int32_t* __restrict__ keep, const uint8_t* __restrict__ valid, int64_t n,
-                                                                   int64_t n_out, int32_t total_parts, int32_t total_rings, int32_t total_coords,
-                                                                   int32_t* __restrict__ geom_off, int32_t* __restrict__ part_off,
-                                                                   int32_t* __restrict__ ring_off, uint8_t* __restrict__ validity,
-                                                                   int32_t* __restrict__ out_src) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k == 0) {
-        geom_off[n_out] = total_parts;
-        part_off[total_parts] = total_rings;
-        ring_off[total_rings] = total_coords;
-    }
-    if (k < n && keep[k]) {
-        const int64_t row = row_at[k];
-        if (row < n_out) {
-            geom_off[row] = part_start[k];
-            if (out_src) out_src[row] = (int32_t)k;
-        }
-    }
-    if (validity && k < (n + 7) / 8) {
-        unsigned bits = 0;
-        for (int b = 0; b < 8; ++b)
-            if (8 * k + b < n && valid[8 * k + b]) bits |= 1u << b;
-        validity[k] = (uint8_t)bits;
-    }
-}
-
 template <int G>
 __global__ __launch_bounds__(256) void polygon_clip_emit_kernel(int64_t n, const int32_t* __restrict__ arc_start, const int32_t* __restrict__ acoord_start,
                                                                 const pc::Arc* __restrict__ arcs, const double2* __restrict__ axy,
@@ -244,50 +202,28 @@ __global__ __launch_bounds__(256) void polygon_clip_emit_kernel(int64_t n, const
     }
 }
 
-inline dim3 pair_grid(int64_t n, int G) { return dim3((unsigned)((n + (256 / G) - 1) / (256 / G))); }
-
 // what a call is called: in error messages, and stage by stage in a profile
 struct RunNames {
     const char *op, *count, *fill, *stitch, *totals, *offsets, *emit;
 };
-
-// the kernel at the pairs' group size: small and large are its instantiations for lp::LP_G_SMALL and lp::LP_G_LARGE, each in parentheses
-#define GPK_PCLIP_BY_G(on_fail, name, small, large, ...)                                        \
-    do {                                                                                       \
-        if (G == lp::LP_G_SMALL)                                                               \
-            GPK_LAUNCH_OR(on_fail, name, small, pair_grid(n, G), dim3(256), 0, s, __VA_ARGS__); \
-        else                                                                                   \
-            GPK_LAUNCH_OR(on_fail, name, large, pair_grid(n, G), dim3(256), 0, s, __VA_ARGS__); \
-    } while (0)
 
 // The whole call behind both entry points.  mode_ok: the entry point knows the mode.
 template <class Rule, bool INNERMOST>
 int32_t polygon_clip_run(const RunNames& nm, bool mode_ok, const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* a_rows, const uint32_t* b_rows,
                          int64_t n_rows, int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, uint8_t* out_status,
                          int32_t status_space, void* stream, gpk_geoarray** out) {
-    // (the plain arguments are looked at first, in the order of gpk_line_clip)
-    if (!mode_ok) return fail(GPK_ERR_INVALID_ARGUMENT, "%s: unknown mode %d", nm.op, mode);
-    if (flags & ~GPK_CLIP_DROP_EMPTY) return fail(GPK_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", nm.op, flags);
+    GPK_TRY(clip_prologue(nm.op, ClipSide{"a_rows", "rows of a"}, ClipSide{"b_rows", "rows of b"}, mode_ok, mode, flags, out_src, n_rows, a, b, a_rows, b_rows,
+                          out, [&](int32_t ta, int32_t tb) {
+                              if (is_polygonal(ta) && is_polygonal(tb)) return (int32_t)GPK_OK;
+                              return fail(GPK_ERR_MISMATCHED_GEOMETRY, "%s: POLYGON | MULTIPOLYGON x POLYGON | MULTIPOLYGON (found types %d, %d)", nm.op, ta, tb);
+                          }));
     const bool drop = (flags & GPK_CLIP_DROP_EMPTY) != 0;
-    if (out_src && !drop) return fail(GPK_ERR_INVALID_ARGUMENT, "%s: out_src is the map of GPK_CLIP_DROP_EMPTY, which is not set", nm.op);
-    if (n_rows < 0 || n_rows > (int64_t)INT32_MAX) return fail(GPK_ERR_INVALID_ARGUMENT, "%s: %lld pairs", nm.op, (long long)n_rows);
-    if (!a || !b || !out) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out = nullptr;
-    if (!is_polygonal(a->d.type) || !is_polygonal(b->d.type))
-        return fail(GPK_ERR_MISMATCHED_GEOMETRY, "%s: POLYGON | MULTIPOLYGON x POLYGON | MULTIPOLYGON (found types %d, %d)", nm.op, a->d.type, b->d.type);
-    if (!a_rows && n_rows != a->d.n_geoms)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "%s: %lld pairs without a_rows but %lld rows of a", nm.op, (long long)n_rows, (long long)a->d.n_geoms);
-    if (!b_rows && n_rows != b->d.n_geoms)
-        return fail(GPK_ERR_INVALID_ARGUMENT, "%s: %lld pairs without b_rows but %lld rows of b", nm.op, (long long)n_rows, (long long)b->d.n_geoms);
-    GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = n_rows, n1 = n > 0 ? n : 1;
-    auto plain = [](int32_t rc) { return rc; };
 
     // ---- scratch of the first stage: per-pair counts, their scans, the scans' block totals, the totals record, staged lists
     const size_t i32 = align256(sizeof(int32_t) * (size_t)(n1 + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n1 + 255) / 256 + 2));
-    const bool stage_rows = rows_space != GPK_MEM_DEVICE, stage_src = out_src && src_space != GPK_MEM_DEVICE;
-    GPK_TRY(workspace().begin(13 * i32 + 2 * align256((size_t)n1) + 6 * tot + 512 + (stage_rows ? 2 * i32 : 0) + (stage_src ? i32 : 0) + 512));
+    GPK_TRY(workspace().begin(13 * i32 + 2 * align256((size_t)n1) + 6 * tot + 512 + clip_staging_bytes(rows_space, out_src, src_space, i32) + 512));
     Workspace& w = workspace();
     int32_t* n_arcs = (int32_t*)w.take(i32);
     int32_t* n_acoords = (int32_t*)w.take(i32);
@@ -310,33 +246,19 @@ int32_t polygon_clip_run(const RunNames& nm, bool mode_ok, const gpk_geoarray* a
     unsigned long long* tot_coords = (unsigned long long*)w.take(tot);
     unsigned long long* tot_rows = (unsigned long long*)w.take(tot);
     unsigned long long* totals_dev = (unsigned long long*)w.take(512);
-    const uint32_t *arows = a_rows, *brows = b_rows;
-    if (stage_rows && n > 0) {
-        if (a_rows) {
-            uint32_t* r = (uint32_t*)w.take(i32);
-            GPK_HIP(hipMemcpyAsync(r, a_rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            arows = r;
-        }
-        if (b_rows) {
-            uint32_t* r = (uint32_t*)w.take(i32);
-            GPK_HIP(hipMemcpyAsync(r, b_rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            brows = r;
-        }
-    }
-    int32_t* src_dev = stage_src ? (int32_t*)w.take(i32) : out_src;
+    ClipLists in;
+    GPK_TRY(clip_stage_lists(w, a_rows, b_rows, rows_space, out_src, src_space, n, i32, s, &in));
 
     // ---- 1, 2: count the arcs, scan, the first wait
     const int G = lp::relation_group_size(a->d, b->d);
     const int64_t at = (n + 255) / 256;
-    unsigned long long totals[4] = {0, 0, 0, 0};
+    unsigned long long totals[4] = {0, 0, 0, 0};  // arcs, arc coordinates
     if (n > 0) {
-        GPK_PCLIP_BY_G(plain, nm.count, (polygon_clip_count_kernel<lp::LP_G_SMALL, Rule>), (polygon_clip_count_kernel<lp::LP_G_LARGE, Rule>), a->d, b->d, arows, brows, n, (int)mode, n_arcs, n_acoords, valid);
+        GPK_LAUNCH_BY_G(nm.count, (polygon_clip_count_kernel<lp::LP_G_SMALL, Rule>), (polygon_clip_count_kernel<lp::LP_G_LARGE, Rule>), a->d, b->d, in.a_rows,
+                        in.b_rows, n, (int)mode, n_arcs, n_acoords, valid);
         GPK_TRY(exclusive_scan_i32(n_arcs, n, arc_start, nullptr, tot_arcs, s));
         GPK_TRY(exclusive_scan_i32(n_acoords, n, acoord_start, nullptr, tot_acoords, s));
-        GPK_LAUNCH(nm.totals, polygon_clip_totals_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)(tot_arcs + at),
-                   (const unsigned long long*)(tot_acoords + at), (const unsigned long long*)nullptr, (const unsigned long long*)nullptr, totals_dev);
-        GPK_HIP(d2h_small(totals, totals_dev, sizeof totals, s));
-        GPK_HIP(sync_small(s));
+        GPK_TRY(clip_read_totals(nm.totals, tot_arcs + at, tot_acoords + at, nullptr, nullptr, totals_dev, totals, s));
     }
     if (totals[0] > (unsigned long long)INT32_MAX || totals[1] > (unsigned long long)INT32_MAX)
         return fail(GPK_ERR_INVALID_ARGUMENT, "%s: the result exceeds 2^31 - 1 arcs / coordinates (Arrow i32 offsets)", nm.op);
@@ -353,87 +275,47 @@ int32_t polygon_clip_run(const RunNames& nm, bool mode_ok, const gpk_geoarray* a
     int32_t* ring_first = (int32_t*)w2.take(link_b);
     int32_t* order = (int32_t*)w2.take(link_b);
     int32_t* info = (int32_t*)w2.take(link_b);
-    unsigned long long sizes[4] = {0, 0, 0, 0};
+    unsigned long long sizes[4] = {0, 0, 0, 0};  // parts, rings, coordinates, rows that stay
     if (n > 0) {
         // (a record the fill pass should leave unwritten has length 0, which the stitcher refuses)
         GPK_HIP(hipMemsetAsync(arcs, 0, arcs_b, s));
         if (total_arcs > 0)
-            GPK_PCLIP_BY_G(plain, nm.fill, (polygon_clip_fill_kernel<lp::LP_G_SMALL, Rule>), (polygon_clip_fill_kernel<lp::LP_G_LARGE, Rule>), a->d, b->d, arows, brows, n, (int)mode, (const int32_t*)arc_start,
-                           (const int32_t*)acoord_start, arcs, axy);
-        GPK_PCLIP_BY_G(plain, nm.stitch, (polygon_clip_stitch_kernel<lp::LP_G_SMALL, INNERMOST>), (polygon_clip_stitch_kernel<lp::LP_G_LARGE, INNERMOST>), n, (int)drop, (const int32_t*)arc_start, (const int32_t*)acoord_start,
-                       (const pc::Arc*)arcs, (const double2*)axy, next, ring_first, order, info, valid, n_parts, n_rings, n_coords, keep, status);
+            GPK_LAUNCH_BY_G(nm.fill, (polygon_clip_fill_kernel<lp::LP_G_SMALL, Rule>), (polygon_clip_fill_kernel<lp::LP_G_LARGE, Rule>), a->d, b->d, in.a_rows,
+                            in.b_rows, n, (int)mode, (const int32_t*)arc_start, (const int32_t*)acoord_start, arcs, axy);
+        GPK_LAUNCH_BY_G(nm.stitch, (polygon_clip_stitch_kernel<lp::LP_G_SMALL, INNERMOST>), (polygon_clip_stitch_kernel<lp::LP_G_LARGE, INNERMOST>), n, (int)drop,
+                        (const int32_t*)arc_start, (const int32_t*)acoord_start, (const pc::Arc*)arcs, (const double2*)axy, next, ring_first, order, info, valid,
+                        n_parts, n_rings, n_coords, keep, status);
         GPK_TRY(exclusive_scan_i32(n_parts, n, part_start, nullptr, tot_parts, s));
         GPK_TRY(exclusive_scan_i32(n_rings, n, ring_start, nullptr, tot_rings, s));
         GPK_TRY(exclusive_scan_i32(n_coords, n, coord_start, nullptr, tot_coords, s));
         GPK_TRY(exclusive_scan_i32(keep, n, row_at, nullptr, tot_rows, s));
-        GPK_LAUNCH(nm.totals, polygon_clip_totals_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)(tot_parts + at),
-                   (const unsigned long long*)(tot_rings + at), (const unsigned long long*)(tot_coords + at), (const unsigned long long*)(tot_rows + at),
-                   totals_dev + 8);
-        GPK_HIP(d2h_small(sizes, totals_dev + 8, sizeof sizes, s));
-        GPK_HIP(sync_small(s));
+        GPK_TRY(clip_read_totals(nm.totals, tot_parts + at, tot_rings + at, tot_coords + at, tot_rows + at, totals_dev + 8, sizes, s));
     }
     if (sizes[0] > (unsigned long long)INT32_MAX || sizes[1] > (unsigned long long)INT32_MAX || sizes[2] > (unsigned long long)INT32_MAX)
         return fail(GPK_ERR_INVALID_ARGUMENT, "%s: the result exceeds 2^31 - 1 parts / rings / coordinates (Arrow i32 offsets)", nm.op);
     const int64_t n_out = (int64_t)sizes[3];
     const int32_t total_parts = (int32_t)sizes[0], total_rings = (int32_t)sizes[1], total_coords = (int32_t)sizes[2];
 
-    // ---- the result column: owned buffers, as gpk_line_clip's, plus part_off
-    gpk_geoarray* r = new gpk_geoarray;
-    memset(r, 0, sizeof *r);
-    (void)hipGetDevice(&r->device);
-    r->d.type = GPK_GEOM_MULTIPOLYGON;
-    r->d.n_geoms = n_out;
-    r->d.n_parts = total_parts;
-    r->d.n_rings = total_rings;
-    r->d.n_coords = total_coords;
-    auto done = [&](int32_t rc) {
-        if (rc != GPK_OK) {
-            (void)hipStreamSynchronize(s);
-            gpk_geoarray_free(r);
-        } else {
-            *out = r;
-        }
-        return rc;
-    };
-    auto alloc = [&](int slot, size_t bytes, const void** view) -> int32_t {
-        void* p = nullptr;
-        const hipError_t e = device_malloc(&p, bytes ? bytes : 8);
-        if (e != hipSuccess) return fail(GPK_ERR_OOM, "%s: device_malloc(%zu) failed: %s", nm.op, bytes, hipGetErrorString(e));
-        r->owned[slot] = p;
-        *view = p;
-        r->nbytes += (int64_t)bytes;
-        return GPK_OK;
-    };
-    int32_t rc = alloc(0, sizeof(double2) * (size_t)total_coords, (const void**)&r->d.xy);
-    if (rc == GPK_OK) rc = alloc(1, sizeof(int32_t) * (size_t)(n_out + 1), (const void**)&r->d.geom_off);
-    if (rc == GPK_OK) rc = alloc(2, sizeof(int32_t) * (size_t)(total_parts + 1), (const void**)&r->d.part_off);
-    if (rc == GPK_OK) rc = alloc(3, sizeof(int32_t) * (size_t)(total_rings + 1), (const void**)&r->d.ring_off);
-    if (rc == GPK_OK && !drop && n > 0) rc = alloc(4, (size_t)((n + 7) / 8), (const void**)&r->d.validity);
-    if (rc != GPK_OK) return done(rc);
+    // ---- the result column
+    int device = 0;
+    (void)hipGetDevice(&device);
+    Column col(nm.op, GPK_GEOM_MULTIPOLYGON, device, s);
+    GPK_TRY(col.size(n_out, total_parts, total_rings, total_coords, !drop && n > 0));
 
     // ---- 6: offsets, emit
-    if (n == 0) {
-        hipError_t e = hipMemsetAsync(r->owned[1], 0, sizeof(int32_t), s);
-        if (e == hipSuccess) e = hipMemsetAsync(r->owned[2], 0, sizeof(int32_t), s);
-        if (e == hipSuccess) e = hipMemsetAsync(r->owned[3], 0, sizeof(int32_t), s);
-        return done(e == hipSuccess ? GPK_OK : fail(GPK_ERR_DEVICE, "%s: %s", nm.op, hipGetErrorString(e)));
+    if (n > 0) {
+        GPK_TRY(clip_write_offsets(nm.offsets, part_start, row_at, keep, valid, n, n_out, total_parts, total_rings, total_coords, col, in.src, s));
+        if (total_rings > 0)
+            GPK_LAUNCH_BY_G(nm.emit, (polygon_clip_emit_kernel<lp::LP_G_SMALL>), (polygon_clip_emit_kernel<lp::LP_G_LARGE>), n, (const int32_t*)arc_start,
+                            (const int32_t*)acoord_start, (const pc::Arc*)arcs, (const double2*)axy, (const int32_t*)next, (const int32_t*)order,
+                            (const int32_t*)part_start, (const int32_t*)ring_start, (const int32_t*)coord_start, col.part_off(), col.ring_off(), col.xy());
+        if (in.src_staged && n_out > 0) GPK_TRY(copy_out(out_src, src_space, in.src, sizeof(int32_t) * (size_t)n_out, s));
+        if (out_status) GPK_TRY(copy_out(out_status, status_space, status, (size_t)n, s));
+    } else {
+        GPK_TRY(col.zero_offsets());
     }
-    GPK_LAUNCH_OR(done, nm.offsets, polygon_clip_offsets_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t*)part_start,
-                  (const int32_t*)row_at, (const int32_t*)keep, (const uint8_t*)valid, n, n_out, total_parts, total_rings, total_coords,
-                  (int32_t*)r->owned[1], (int32_t*)r->owned[2], (int32_t*)r->owned[3], (uint8_t*)r->owned[4], src_dev);
-    if (total_rings > 0)
-        GPK_PCLIP_BY_G(done, nm.emit, (polygon_clip_emit_kernel<lp::LP_G_SMALL>), (polygon_clip_emit_kernel<lp::LP_G_LARGE>), n, (const int32_t*)arc_start, (const int32_t*)acoord_start,
-                       (const pc::Arc*)arcs, (const double2*)axy, (const int32_t*)next, (const int32_t*)order, (const int32_t*)part_start,
-                       (const int32_t*)ring_start, (const int32_t*)coord_start, (int32_t*)r->owned[2], (int32_t*)r->owned[3], (double2*)r->owned[0]);
-    if (stage_src && n_out > 0) {
-        rc = copy_out(out_src, src_space, src_dev, sizeof(int32_t) * (size_t)n_out, s);
-        if (rc != GPK_OK) return done(rc);
-    }
-    if (out_status) {
-        rc = copy_out(out_status, status_space, status, (size_t)n, s);
-        if (rc != GPK_OK) return done(rc);
-    }
-    return done(GPK_OK);
+    col.release(out);
+    return GPK_OK;
 }
 
 }  // namespace

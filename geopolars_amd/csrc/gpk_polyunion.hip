@@ -91,11 +91,8 @@ extern "C" int32_t gpk_union_all_pairs(const int32_t* group, const uint32_t* row
     GPK_TRY(exclusive_scan_i32(stays, n, next_at, nullptr, tot_next, s));
     GPK_LAUNCH("gpk_union_all_scatter", union_all_scatter_kernel, grid, dim3(256), 0, s, group, rows, n, base, (const int32_t*)opens, (const int32_t*)stays,
                (const int32_t*)pair_at, (const int32_t*)next_at, a_rows, b_rows, next_group, next_rows);
-    GPK_LAUNCH("gpk_union_all_totals", polygon_clip_totals_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)(tot_pairs + at),
-               (const unsigned long long*)(tot_next + at), (const unsigned long long*)nullptr, (const unsigned long long*)nullptr, totals_dev);
     unsigned long long totals[4] = {0, 0, 0, 0};
-    GPK_HIP(d2h_small(totals, totals_dev, sizeof totals, s));
-    GPK_HIP(sync_small(s));
+    GPK_TRY(clip_read_totals("gpk_union_all_totals", tot_pairs + at, tot_next + at, nullptr, nullptr, totals_dev, totals, s));
     out_counts[0] = (int64_t)totals[0];
     out_counts[1] = (int64_t)totals[1];
     return GPK_OK;

@@ -692,13 +692,8 @@ extern "C" {
 
 int32_t gpk_rowmap_free(gpk_rowmap* m) {
     if (!m) return GPK_OK;
-    if (m->perm || m->tsorted || m->seg_inv) {  // (cached blocks: wait once, on the owning device, for whatever still reads the map)
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != m->device) (void)hipSetDevice(m->device);
-        (void)hipDeviceSynchronize();
-        if (cur >= 0 && cur != m->device) (void)hipSetDevice(cur);
-    }
+    // (cached blocks: wait once, on the owning device, for whatever still reads the map)
+    if (m->perm || m->tsorted || m->seg_inv) (void)sync_device(m->device);
     if (m->perm) cached_free(m->perm);
     if (m->tsorted) cached_free(m->tsorted);
     if (m->seg_inv) cached_free(m->seg_inv);

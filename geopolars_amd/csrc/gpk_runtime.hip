@@ -7,6 +7,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "gpk_column.h"
 #include "gpk_common.h"
 
 namespace gpk {
@@ -596,13 +597,7 @@ int32_t gpk_geoarray_free(gpk_geoarray* a) {
     // the owning device, for whatever still reads them)
     bool any = false;
     for (int i = 0; i < 5; ++i) any = any || a->owned[i] != nullptr;
-    if (any) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != a->device) (void)hipSetDevice(a->device);
-        (void)hipDeviceSynchronize();
-        if (cur >= 0 && cur != a->device) (void)hipSetDevice(cur);
-    }
+    if (any) (void)sync_device(a->device);
     for (int i = 0; i < 5; ++i)
         if (a->owned[i]) cached_free(a->owned[i]);
     for (int k = 0; k < 2; ++k)
@@ -610,17 +605,80 @@ int32_t gpk_geoarray_free(gpk_geoarray* a) {
             gpk_index_free(a->auto_index[k]);
             a->auto_index[k] = nullptr;
         }
-    if (a->classes) {
-        if (a->classes->lists) (void)hipFree(a->classes->lists);
-        if (a->classes->chunk_begin) (void)hipFree(a->classes->chunk_begin);
-        if (a->classes->strip_first) (void)hipFree(a->classes->strip_first);
-        if (a->classes->strip_cross) (void)hipFree(a->classes->strip_cross);
-        if (a->classes->strip_desc) (void)hipFree(a->classes->strip_desc);
-        delete a->classes;
-    }
+    free_seq_classes(a);
     delete a;
     return GPK_OK;
 }
+
+}  // extern "C"
+
+namespace gpk {
+
+void free_seq_classes(gpk_geoarray* a) {
+    if (!a->classes) return;
+    if (a->classes->lists) (void)hipFree(a->classes->lists);
+    if (a->classes->chunk_begin) (void)hipFree(a->classes->chunk_begin);
+    if (a->classes->strip_first) (void)hipFree(a->classes->strip_first);
+    if (a->classes->strip_cross) (void)hipFree(a->classes->strip_cross);
+    if (a->classes->strip_desc) (void)hipFree(a->classes->strip_desc);
+    delete a->classes;
+    a->classes = nullptr;
+}
+
+// ---- gpk_column.h: the owned result column under construction ----
+Column::Column(const char* op, int32_t type, int device, hipStream_t s) : op_(op), s_(s), a_(new gpk_geoarray) {
+    memset(a_, 0, sizeof *a_);
+    a_->device = device;
+    a_->d.type = type;
+}
+Column::~Column() {
+    if (!a_) return;
+    (void)hipStreamSynchronize(s_);
+    gpk_geoarray_free(a_);
+}
+int32_t Column::size(int64_t n_geoms, int64_t n_parts, int64_t n_rings, int64_t n_coords, bool validity) {
+    DevGeo& d = a_->d;
+    const bool has_part = d.type == GPK_GEOM_MULTIPOLYGON,
+               has_ring = d.type == GPK_GEOM_POLYGON || d.type == GPK_GEOM_MULTILINESTRING || d.type == GPK_GEOM_MULTIPOLYGON;
+    d.n_geoms = n_geoms;
+    d.n_parts = has_part ? n_parts : (is_polygonal(d.type) ? n_geoms : 0);
+    d.n_rings = has_ring ? n_rings : 0;
+    d.n_coords = n_coords;
+    struct Level {
+        bool present;
+        size_t bytes;
+        const void** view;
+    } levels[5] = {
+        {true, sizeof(double2) * (size_t)n_coords, (const void**)&d.xy},
+        {d.type != GPK_GEOM_POINT, sizeof(int32_t) * (size_t)(n_geoms + 1), (const void**)&d.geom_off},
+        {has_part, sizeof(int32_t) * (size_t)(n_parts + 1), (const void**)&d.part_off},
+        {has_ring, sizeof(int32_t) * (size_t)(n_rings + 1), (const void**)&d.ring_off},
+        {validity, (size_t)((n_geoms + 7) / 8), (const void**)&d.validity},
+    };
+    for (int slot = 0; slot < 5; ++slot) {
+        const Level& L = levels[slot];
+        if (!L.present) continue;
+        void* p = nullptr;
+        const hipError_t e = device_malloc(&p, L.bytes ? L.bytes : 8);
+        if (e != hipSuccess) return fail(GPK_ERR_OOM, "%s: device_malloc(%zu) failed: %s", op_, L.bytes, hipGetErrorString(e));
+        a_->owned[slot] = p;
+        *L.view = p;
+        a_->nbytes += (int64_t)L.bytes;
+    }
+    return GPK_OK;
+}
+int32_t Column::zero_offsets() {
+    for (int slot = 1; slot <= 3; ++slot) {
+        if (!a_->owned[slot]) continue;
+        const hipError_t e = hipMemsetAsync(a_->owned[slot], 0, sizeof(int32_t), s_);
+        if (e != hipSuccess) return fail(GPK_ERR_DEVICE, "%s: %s", op_, hipGetErrorString(e));
+    }
+    return GPK_OK;
+}
+
+}  // namespace gpk
+
+extern "C" {
 
 int32_t gpk_geoarray_validity(const gpk_geoarray* a, uint8_t* out_bitmap, int32_t* out_has_validity, void* stream) {
     if (!a || !out_has_validity) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");

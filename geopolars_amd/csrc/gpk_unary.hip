@@ -1288,17 +1288,13 @@ static int32_t ring_stream_run(int op, const gpk_geoarray* a, const UnaryCtx& c,
 int32_t gpk_geoarray_invalidate(gpk_geoarray* a) {
     if (!a) return fail(GPK_ERR_INVALID_ARGUMENT, "NULL argument");
     GPK_TRY(require_device());
-    GPK_HIP(hipDeviceSynchronize());  // (launches in flight may still read the tables)
+    GPK_HIP(sync_device(a->device));  // (launches in flight, on the handle's device, may still read the tables)
     std::lock_guard<std::mutex> lk(g_classes_mu);
-    if (a->classes) {
-        if (a->classes->lists) (void)hipFree(a->classes->lists);
-        if (a->classes->chunk_begin) (void)hipFree(a->classes->chunk_begin);
-        if (a->classes->strip_first) (void)hipFree(a->classes->strip_first);
-        if (a->classes->strip_cross) (void)hipFree(a->classes->strip_cross);
-        if (a->classes->strip_desc) (void)hipFree(a->classes->strip_desc);
-        delete a->classes;
-        a->classes = nullptr;
-    }
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != a->device) (void)hipSetDevice(a->device);  // (the tables are freed on the device that holds them)
+    free_seq_classes(a);
+    if (cur >= 0 && cur != a->device) (void)hipSetDevice(cur);
     return GPK_OK;
 }
 

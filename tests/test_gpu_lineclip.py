@@ -15,6 +15,7 @@ from geopolars_amd import _abi, synth
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import line_clip_pairs, line_clip_pairs_device, relation_pairs, spatial_join_clip
+from tests import clip_abi
 from tests import exact_ref as X
 from tests import lineclip_ref as L
 from tests import overlay_ref as O
@@ -229,6 +230,19 @@ def test_refusals_with_real_handles(golden):
     assert call(lines, short, len(lines)) == _abi.GPK_ERR_INVALID_ARGUMENT and not out.value
     far = GeoSeries(X.column(LS, [[(100, 100), (101, 101)]])).intersection(short)
     assert len(far) == 1 and far.array.is_valid().all() and len(far.array.xy) == 0 and far.array.ring_offsets.tolist() == [0]
+
+
+def test_zero_pairs_through_the_abi():
+    """n_rows = 0 with host and with device row lists, with and without DROP_EMPTY (the Python layer never makes this call)"""
+    clip_abi.check_zero_pairs("gpk_line_clip", _abi.CLIP_INSIDE)
+
+
+def test_every_pair_dropped_through_the_abi():
+    clip_abi.check_every_pair_dropped("gpk_line_clip", _abi.CLIP_INSIDE)
+
+
+def test_a_partial_last_byte_of_the_bitmap():
+    clip_abi.check_bitmap_edge("gpk_line_clip", _abi.CLIP_INSIDE)
 
 
 # ---- 6. many blocks ------------------------------------------------------------------------------------------------------------------

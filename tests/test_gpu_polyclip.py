@@ -17,6 +17,7 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import polygon_clip_pairs, polygon_clip_pairs_device, polygon_relation_pairs, spatial_join_overlay
+from tests import clip_abi
 from tests import exact_ref as X
 from tests import overlay_ref as O
 from tests import polyclip_ref as L
@@ -258,6 +259,19 @@ def test_refusals_with_real_handles(golden):
     far = GeoSeries(X.column(PG, [[L.S10]])).polygon_intersection(GeoSeries(X.column(PG, [[L.sq(40, 40, 50, 50)]])))
     assert len(far) == 1 and far.array.is_valid().all() and len(far.array.xy) == 0 and far.array.ring_offsets.tolist() == [0]
     assert far.array.part_offsets.tolist() == [0] and far.array.geom_offsets.tolist() == [0, 0]
+
+
+def test_zero_pairs_through_the_abi():
+    """n_rows = 0 with host and with device row lists, with and without DROP_EMPTY (the Python layer never makes this call)"""
+    clip_abi.check_zero_pairs("gpk_polygon_clip", _abi.PCLIP_INTERSECTION)
+
+
+def test_every_pair_dropped_through_the_abi():
+    clip_abi.check_every_pair_dropped("gpk_polygon_clip", _abi.PCLIP_INTERSECTION)
+
+
+def test_a_partial_last_byte_of_the_bitmap():
+    clip_abi.check_bitmap_edge("gpk_polygon_clip", _abi.PCLIP_INTERSECTION)
 
 
 # ---- 6. many blocks ------------------------------------------------------------------------------------------------------------------

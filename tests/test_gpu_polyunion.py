@@ -21,6 +21,7 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import polygon_union_pairs, polygon_union_pairs_device
+from tests import clip_abi
 from tests import exact_ref as X
 from tests import overlay_ref as O
 from tests import polyclip_ref as L
@@ -248,6 +249,12 @@ def test_refusals_with_real_handles(golden):
     assert call(a, b, len(a) - 1) == _abi.GPK_ERR_INVALID_ARGUMENT and not out.value
     got, status = GeoSeries(X.column(PG, [[U.S10], []])).polygon_union(GeoSeries(X.column(PG, [[], [U.S10]])), return_status=True)
     assert not got.array.is_valid().any() and (status == U.ST_NULL).all()  # an empty row is not the neutral element
+
+
+def test_zero_pairs_through_the_abi():
+    """n_rows = 0 with host and with device row lists, with and without DROP_EMPTY (the Python layer never makes this call); the union
+    of disjoint shapes is never empty, so there is no "every pair dropped" here"""
+    clip_abi.check_zero_pairs("gpk_polygon_union", _abi.PUNION_UNION)
 
 
 # ---- 6. many blocks ------------------------------------------------------------------------------------------------------------------
