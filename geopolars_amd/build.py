@@ -57,6 +57,7 @@ SOURCES = [
     "gpk_wkb_device.hip",
     "gpk_wkb_encode.hip",
     "gpk_take.hip",
+    "gpk_geotake.hip",
     "gpk_structural.hip",
     "gpk_lineal_ops.hip",
     "gpk_comm.hip",

@@ -443,6 +443,51 @@ class DeviceGeoArray:
         total = int(bases[k])
         return DeviceGeoArray(out.value, chunks[0].geom_type, total, -1), np.array(list(bases), dtype=np.int64)
 
+    def _owned_result(self, handle: C.c_void_p, stream: int) -> "DeviceGeoArray":
+        """a column gpk_geoarray_take / gpk_geoarray_filter returned, its sizes filled in from the size query"""
+        out = DeviceGeoArray(handle.value, self.geom_type, 0, -1)
+        sizes = (C.c_int64 * 4)()
+        _abi.check(_abi.lib().gpk_geoarray_download(out.handle, sizes, None, None, None, None, stream))
+        out.n_coords, out.n_geoms = int(sizes[0]), int(sizes[3])
+        return out
+
+    def take(self, idx, stream: int = 0) -> "DeviceGeoArray":
+        """Rows `idx` (any order, repeats allowed; -1 or any index outside [0, n): a null row) as a new device-resident column
+        (gpk_geoarray_take).  idx: a numpy array, or a torch device tensor of int64 (used where it is)."""
+        if isinstance(idx, np.ndarray) or not hasattr(idx, "data_ptr"):
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            ptr, n, space = (idx.ctypes.data if len(idx) else None), len(idx), _abi.MEM_HOST
+        else:
+            import torch
+
+            if idx.dtype != torch.int64 or idx.dim() != 1:
+                raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"take: a 1-D int64 tensor of indices (found {idx.dtype}, {idx.dim()}-D)")
+            idx = idx.contiguous()
+            ptr, n, space = (idx.data_ptr() if idx.numel() else None), int(idx.numel()), (_abi.MEM_DEVICE if idx.is_cuda else _abi.MEM_HOST)
+        h = C.c_void_p()
+        _abi.check(_abi.lib().gpk_geoarray_take(self.handle, ptr, n, space, stream, C.byref(h)))
+        return self._owned_result(h, stream)
+
+    def filter(self, mask, stream: int = 0) -> "DeviceGeoArray":
+        """The rows `mask` keeps, in order, as a new device-resident column (gpk_geoarray_filter; the kept row numbers never visit the
+        host).  mask: a numpy bool array, or a torch bool / uint8 device tensor, one entry per row."""
+        if isinstance(mask, np.ndarray) or not hasattr(mask, "data_ptr"):
+            mask = np.ascontiguousarray(mask)
+            if mask.dtype != np.bool_ or mask.ndim != 1 or len(mask) != self.n_geoms:
+                raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"filter: a 1-D bool mask of {self.n_geoms} entries (found {mask.dtype}, shape {mask.shape})")
+            ptr, space = (mask.ctypes.data if len(mask) else None), _abi.MEM_HOST
+        else:
+            import torch
+
+            if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 or int(mask.numel()) != self.n_geoms:
+                raise _abi.GeopolarsHipError(
+                    _abi.GPK_ERR_INVALID_ARGUMENT, f"filter: a 1-D bool or uint8 tensor of {self.n_geoms} entries (found {mask.dtype}, shape {tuple(mask.shape)})")
+            mask = mask.contiguous()
+            ptr, space = (mask.data_ptr() if mask.numel() else None), (_abi.MEM_DEVICE if mask.is_cuda else _abi.MEM_HOST)
+        h, kept = C.c_void_p(), C.c_int64(0)
+        _abi.check(_abi.lib().gpk_geoarray_filter(self.handle, ptr, 8, space, stream, C.byref(h), C.byref(kept)))  # (numpy and torch bools are a byte a row)
+        return self._owned_result(h, stream)
+
     def nbytes(self) -> int:
         n = C.c_int64(0)
         _abi.check(_abi.lib().gpk_geoarray_nbytes(self.handle, C.byref(n)))

@@ -674,6 +674,30 @@ class GeoSeries:
         closure of int(a) minus b; a valid row without parts where b covers a.  Shaped and ruled like `polygon_intersection`."""
         return self._polygon_clip("polygon_difference", _abi.PCLIP_DIFFERENCE, other, other_rows, return_status)
 
+    # ---- rows of the column (gpk_geotake.hip) ------------------------------------------------------------
+    def take(self, idx, allow_null: bool = False) -> "GeoSeries":
+        """Rows `idx` — any order, repeats allowed — as a device-resident series of the same type (gpk_geoarray_take): every level
+        and the coordinates copied bit for bit on the device.  With `allow_null` an index of -1 gives a null row (a left join's
+        unmatched side); without it every index must lie in [0, len)."""
+        idx = take_args("take", self, idx, allow_null)
+        return GeoSeries(None, name=self.name, device=self.device().take(idx))
+
+    def filter(self, mask) -> "GeoSeries":
+        """The rows a bool mask keeps, in order, as a device-resident series (gpk_geoarray_filter)."""
+        mask = filter_args("filter", self, mask)
+        return GeoSeries(None, name=self.name, device=self.device().filter(mask))
+
+    def __getitem__(self, key) -> "GeoSeries":
+        """s[a:b:c] (take of the range), s[bool array] (filter), s[integer array] (take).  One row is not a series: a scalar is
+        refused."""
+        if isinstance(key, slice):
+            return self.take(np.arange(*key.indices(len(self)), dtype=np.int64))
+        k = np.asarray(key)
+        if k.ndim == 0:
+            raise _abi.GeopolarsHipError(
+                _abi.GPK_ERR_INVALID_ARGUMENT, f"GeoSeries[{key!r}]: one row is not a series: index with a slice, a bool mask or an integer array")
+        return self.filter(k) if k.dtype == np.bool_ else self.take(k)
+
     # ---- polygon x polygon union and the grouped union (gpk_polyunion.hip) ---------------------------
     def polygon_union(self, other: "GeoSeries", other_rows=None, return_status: bool = False):
         """The area every row's polygon or other[other_rows[i]] covers (gpk_polygon_union), as a MULTIPOLYGON series: neighbours that
@@ -1250,6 +1274,31 @@ def line_clip_call(lines, polys, line_rows, poly_rows, n_rows: int, rows_space: 
     _abi.check(_abi.lib().gpk_geoarray_download(dev.handle, sizes, None, None, None, None, stream))
     dev.n_coords, dev.n_geoms = int(sizes[0]), int(sizes[3])
     return GeoSeries(None, device=dev)
+
+
+def take_args(op: str, a: GeoSeries, idx, allow_null: bool) -> np.ndarray:
+    """the checks of take before any device call: a 1-D integer array whose every entry lies in [0, len) — or, with allow_null, is
+    exactly -1.  Returns it as int64."""
+    k = np.asarray(idx)
+    if k.ndim != 1 or k.dtype.kind not in "iu":
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: `idx` must be a 1-D integer array (found {k.dtype}, {k.ndim}-D)")
+    n = len(a)
+    bad = (k >= n) | (k < (-1 if allow_null else 0)) if len(k) else np.zeros(0, bool)
+    if bad.any():
+        at = int(np.flatnonzero(bad)[0])
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: idx[{at}] = {int(k[at])} is outside [0, {n})" + (" and is not -1" if allow_null else ""))
+    return np.ascontiguousarray(k, dtype=np.int64)
+
+
+def filter_args(op: str, a: GeoSeries, mask) -> np.ndarray:
+    """the checks of filter before any device call: a 1-D bool array with one entry per row"""
+    m = np.asarray(mask)
+    if m.ndim != 1 or m.dtype != np.bool_:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: `mask` must be a 1-D bool array (found {m.dtype}, {m.ndim}-D)")
+    if len(m) != len(a):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {len(m)} mask entries for {len(a)} rows")
+    return np.ascontiguousarray(m)
 
 
 def polygon_clip_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:

@@ -153,6 +153,12 @@ class SpatialJoinArgs:
     # which carries no ARROW:extension:name (geoarrow.*).  spatial_join refuses such a column without a hint rather than guess.
     l_geom_type: int = -1
     r_geom_type: int = -1
+    # how the geometry columns leave the join: "wkb" — as the reference holds them — or "geoarrow": native GeoArrow over Struct<x, y>,
+    # gathered on the device (gpk_geoarray_take) from the series the join uploaded, without a detour through WKB
+    geometry_encoding: str = "wkb"
+
+
+GEOMETRY_ENCODINGS = ("wkb", "geoarrow")
 
 
 def _pairs_with_retry(n: int, call, want_dist: bool = False, payload=np.float64):
@@ -306,15 +312,20 @@ def _as_wkb(column, geo: GeoSeries):
     return geo.device().to_arrow("wkb")  # (gpk_geoarray_to_arrow: the library's buffers, validity included, released by pyarrow)
 
 
-def _assemble(lhs, rhs, lgeo: GeoSeries, rgeo: GeoSeries, li: np.ndarray, ri: np.ndarray, l_suffix, r_suffix, distance_col=None, dist=None):
+def _assemble(lhs, rhs, lgeo: GeoSeries, rgeo: GeoSeries, li: np.ndarray, ri: np.ndarray, l_suffix, r_suffix, distance_col=None, dist=None,
+              geometry_encoding: str = "wkb"):
     """The joined table of spatial_index.rs:165-199 from the i64 row indices: suffixed left columns, suffixed right columns, then —
-    for the distance joins — `distance_col` with each pair's distance (null for an unmatched left row)."""
+    for the distance joins — `distance_col` with each pair's distance (null for an unmatched left row).  geometry_encoding "geoarrow":
+    the geometry columns are gathered as native GeoArrow on the device (a null row where r = -1) and exported over Struct<x, y>."""
     import pyarrow as pa
 
     cols, names = [], []
     for table, geo, idx, suffix in ((lhs, lgeo, li, l_suffix), (rhs, rgeo, ri, r_suffix)):
         for name in table.column_names:
-            cols.append(take_column(_as_wkb(table.column(name), geo) if name == "geometry" else table.column(name), idx))
+            if name == "geometry" and geometry_encoding == "geoarrow":
+                cols.append(geo.device().take(idx).to_arrow("struct"))
+            else:
+                cols.append(take_column(_as_wkb(table.column(name), geo) if name == "geometry" else table.column(name), idx))
             names.append(name + (suffix or ""))
     if distance_col is not None:
         # join_indices keeps the pairs' order and puts an unmatched left row (r = -1) where its pairs would be: pair k of the sorted
@@ -337,12 +348,15 @@ def spatial_join(lhs, rhs, options: Optional[SpatialJoinArgs] = None):
     if options.join_type not in ("inner", "left"):
         # spatial_index.rs:200-202 rejects every other JoinType
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "Failed to generate the spatial index for the left dataframe")
+    if options.geometry_encoding not in GEOMETRY_ENCODINGS:
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT, f"spatial_join: geometry_encoding {options.geometry_encoding!r}: one of {', '.join(GEOMETRY_ENCODINGS)}")
     lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
     rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
     r_index = options.r_index or SpatialIndex(rgeo)
     pairs, counts = join_pairs(lgeo, rgeo, options.predicate, r_index)
     li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
-    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix)
+    return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, geometry_encoding=options.geometry_encoding)
 
 
 # ---- nearest-neighbour join (gpk_nearest_join) ----------------------------------------------------------------------------------

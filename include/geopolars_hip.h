@@ -1112,6 +1112,30 @@ int32_t gpk_take_binary(const uint8_t* values, const int32_t* offsets, const uin
                         const int64_t* idx, int64_t n_idx, int32_t* out_offsets, uint8_t* out_values,
                         int64_t capacity, int64_t* n_bytes, uint8_t* out_validity, int32_t space, void* stream);
 
+/* ---- rows of a geometry column (gpk_geotake.hip, the rule: csrc/gpk_geotake.h) ---------------------------------------------------------
+ * take: output row i is source row idx[i] — any order, repeats allowed — for every one of the six geometry types; the result has the
+ * source's type and is a new handle that owns all of its buffers (gpk_geoarray_free; the source may be freed first).  What a dataframe
+ * does to every column (take, filter, slice, head), and the gather of a join's geometry columns without a detour through WKB.
+ *   - Everything is copied bit for bit: coordinates with their NaN payloads and signed zeros, and the children of a null source row
+ *     too.  All offsets start at 0.
+ *   - An index of -1, or any index outside [0, n), gives a null row without children (the convention of gpk_take_fixed; a left join's
+ *     r = -1); in a POINT column that row's coordinate is (NaN, NaN).
+ *   - The result has a validity bitmap if the source has one or some index is out of range; otherwise it has none.
+ *   - idx lives in idx_space (GPK_MEM_HOST or GPK_MEM_DEVICE).  n_idx == 0 gives a column of zero rows.
+ *   - The call waits once, for one small read-back (the child totals of every level and the count of out-of-range indices); everything
+ *     else is stream-ordered.
+ *   - A level whose total exceeds 2^31 - 1 is refused (GPK_ERR_INVALID_ARGUMENT, Arrow i32 offsets) before anything is allocated.
+ *   - Refused before any device work, with *out = NULL: a NULL a or out, a NULL idx with n_idx > 0, a negative n_idx, an unknown space.
+ * Schedule: count -> scan -> one wait -> fill; the fill works in output order, one work-group per strip of 1024 output elements, so a
+ * row of one coordinate and a row of 10^5 move at the same rate. */
+int32_t gpk_geoarray_take(const gpk_geoarray* a, const int64_t* idx, int64_t n_idx, int32_t idx_space, void* stream, gpk_geoarray** out);
+/* filter: the rows the mask keeps, in source order, under exactly the contract of take.  mask has one entry per source row, in
+ * mask_space: mask_bits == 1 is an Arrow bitmap (LSB first), mask_bits == 8 a byte per row (nonzero keeps the row); any other value
+ * is refused.  *n_kept is always set.  The kept row numbers are compacted on the device and never visit the host; the compaction is
+ * part of the counting pass, so filter also waits once.  The mask has no validity of its own: a caller with a nullable mask ANDs the
+ * two bitmaps first. */
+int32_t gpk_geoarray_filter(const gpk_geoarray* a, const uint8_t* mask, int32_t mask_bits, int32_t mask_space, void* stream, gpk_geoarray** out, int64_t* n_kept);
+
 /* ---- chunked columns ------------------------------------------------------------------------------------ */
 /* K chunks of one column held by this process -> ONE array (a new handle, gpk_geoarray_free): Arrow's rechunk — the reference turns
  * every Series into a single chunk before it looks at it (py-geopolars/src/ffi.rs:56,73,93).  Device-resident: the chunks' buffers
