@@ -398,8 +398,10 @@ BoxRefineCtx box_refine_ctx(const gpk_geoarray* left, const gpk_geoarray* right,
 
 int32_t left_boxes(const gpk_geoarray* left, hipStream_t s, const double4** out) {
     const int64_t n = left->d.n_geoms;
-    GPK_TRY(workspace_aux(0).begin(sizeof(double4) * (size_t)n + 256));
-    double4* lbbox = (double4*)workspace_aux(0).take(sizeof(double4) * (size_t)n);
+    Scratch sc(workspace_aux(0));
+    double4* lbbox;
+    sc.add(lbbox, (size_t)n);
+    GPK_TRY(sc.commit());
     *out = lbbox;
     return gpk_bounds(left, (double*)lbbox, GPK_MEM_DEVICE, (void*)s);
 }
@@ -410,31 +412,25 @@ int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk
                   const double4* lbbox, const CandRefine& refine) {
     const int64_t n = left->d.n_geoms;
     const char* what = refine.name;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
     const bool want_pairs = pair_capacity > 0;
     // left boxes and the candidate buffers live in the thread's auxiliary arenas (no hipMalloc / hipFree per call)
     // (a caller's lbbox — in device memory — takes the left boxes' place: query boxes, boxes grown by a distance)
     if (!lbbox) GPK_TRY(left_boxes(left, s, &lbbox));
     const int64_t nb = (n + 255) / 256;
-    const size_t pairs_bytes = sizeof(uint32_t) * 2 * (size_t)pair_capacity;
-    const size_t i32n = align256(sizeof(int32_t) * (size_t)(n + 1));
-    size_t need = 4 * i32n + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + 256 + 1024;
-    if (host_out && out_counts) need += align256(sizeof(uint32_t) * (size_t)n);
-    if (host_out && want_pairs) need += align256(pairs_bytes);
     // (padded staging of the candidates: up to 512 MB — 8M left rows; beyond that the two-search path)
-    const size_t stage_bytes = sizeof(uint32_t) * CAND_STAGE * (size_t)(n > 0 ? n : 1);
-    const bool staged = stage_bytes <= (size_t(512) << 20);
-    if (staged) need += align256(stage_bytes);
-    GPK_TRY(workspace().begin(need));
-    int32_t* cand_cnt = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* cand_off = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* counts = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* offsets = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
-    int32_t* big_rows = (int32_t*)workspace().take(256);
-    uint32_t* counts_out = out_counts ? (host_out ? (uint32_t*)workspace().take(sizeof(uint32_t) * (size_t)n) : out_counts) : nullptr;
-    uint32_t* pairs_dev = want_pairs ? (host_out ? (uint32_t*)workspace().take(pairs_bytes) : out_pairs) : nullptr;
-    uint32_t* stage = staged ? (uint32_t*)workspace().take(stage_bytes) : nullptr;
+    const size_t stage_words = CAND_STAGE * (size_t)(n > 0 ? n : 1);
+    const bool staged = sizeof(uint32_t) * stage_words <= (size_t(512) << 20);
+    Scratch sc(workspace());
+    int32_t *cand_cnt, *cand_off, *counts, *offsets, *big_rows;
+    unsigned long long* btot;
+    uint32_t *counts_out, *pairs_dev, *stage;
+    sc.add_n((size_t)(n + 1), cand_cnt, cand_off, counts, offsets);
+    sc.add(btot, (size_t)(nb + 2));
+    sc.add(big_rows, 64);
+    sc.stage(counts_out, out_counts, out_space, (size_t)n);
+    sc.stage(pairs_dev, want_pairs ? out_pairs : nullptr, out_space, 2 * (size_t)pair_capacity);
+    sc.add_if(staged, stage, stage_words);
+    GPK_TRY(sc.commit());
 
     // stage 1: candidates per left row
     GPK_HIP(hipMemsetAsync(big_rows, 0, 2 * sizeof(int32_t), s));
@@ -467,15 +463,16 @@ int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk
         if (qe != hipSuccess) return fail(GPK_ERR_DEVICE, "%s: %s", what, hipGetErrorString(qe));
     }
     const size_t scratch_bytes = align256(refine.scratch_fixed + refine.scratch_per_cand * nc1);
-    GPK_TRY(workspace_aux(1).begin((has_big_rows ? 3 : 2) * align256(sizeof(uint32_t) * nc1) + align256(nc1) + align256(seg_bytes) + scratch_bytes + 512));
-    uint32_t* cand_r = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
-    uint32_t* cand_l = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
-    uint8_t* hit = (uint8_t*)workspace_aux(1).take(nc1);
+    Scratch sc1(workspace_aux(1));
+    uint32_t *cand_r, *cand_l;
+    uint8_t* hit;
+    sc1.add_n(nc1, cand_r, cand_l, hit);
     if (has_big_rows) {
-        cand_sorted = (uint32_t*)workspace_aux(1).take(sizeof(uint32_t) * nc1);
-        seg_tmp = workspace_aux(1).take(seg_bytes ? seg_bytes : 1);
+        sc1.add(cand_sorted, nc1);
+        sc1.add_bytes(seg_tmp, seg_bytes);
     }
-    if (scratch_bytes) scratch = workspace_aux(1).take(scratch_bytes);
+    if (scratch_bytes) sc1.add_bytes(scratch, scratch_bytes);
+    GPK_TRY(sc1.commit());
 
     // stages 2 and 3: the candidate lists, the refine, the hits
     if (staged && !has_big_rows)
@@ -552,12 +549,15 @@ int32_t payload_join(const PayloadJoin& join, const gpk_index* right_index, uint
         return rc;
     };
     const bool want_payload = out_payload && pair_capacity > 0;
-    const size_t box_bytes = sizeof(double4) * (size_t)n, payload_bytes = cx.payload_elem * (size_t)pair_capacity;
-    int32_t rc = workspace_aux(0).begin((join.boxes ? 2 : 1) * align256(box_bytes) + (want_payload && host_out ? align256(payload_bytes) : 0) + 512);
+    Scratch sc(workspace_aux(0));
+    double4 *lbox, *other;
+    uint8_t* payload_dev;
+    sc.add(lbox, (size_t)n);
+    sc.add_if(join.boxes != nullptr, other, (size_t)n);
+    sc.stage(payload_dev, want_payload ? (uint8_t*)out_payload : nullptr, out_space, cx.payload_elem * (size_t)pair_capacity);
+    int32_t rc = sc.commit();
     if (rc != GPK_OK) return finish(rc);
-    double4* lbox = (double4*)workspace_aux(0).take(box_bytes);
-    double4* other = join.boxes ? (double4*)workspace_aux(0).take(box_bytes) : nullptr;
-    cx.payload_out = want_payload ? (host_out ? workspace_aux(0).take(payload_bytes) : out_payload) : nullptr;
+    cx.payload_out = payload_dev;
     rc = gpk_bounds(left, (double*)lbox, GPK_MEM_DEVICE, stream);
     if (rc == GPK_OK && join.boxes) rc = join.boxes(&cx, right_index, lbox, other, n, s);
     if (rc != GPK_OK) return finish(rc);
@@ -606,14 +606,13 @@ int32_t gpk_index_query_envelope(const gpk_index* idx, const double* boxes4, int
     right.d.n_geoms = idx->n_geoms;
     // the queries in the library's own memory, corners ordered the way `AABB::from_corners` orders them (lower = the component-wise
     // minimum of the two corners, upper = the maximum)
-    GPK_TRY(workspace_aux(0).begin(2 * (sizeof(double4) * (size_t)n_boxes + 256)));
-    double4* boxes_dev = (double4*)workspace_aux(0).take(sizeof(double4) * (size_t)n_boxes);
-    const double4* src = reinterpret_cast<const double4*>(boxes4);
-    if (space != GPK_MEM_DEVICE) {
-        double4* up = (double4*)workspace_aux(0).take(sizeof(double4) * (size_t)n_boxes);
-        GPK_HIP(hipMemcpyAsync(up, boxes4, sizeof(double4) * (size_t)n_boxes, hipMemcpyHostToDevice, s));
-        src = up;
-    }
+    Scratch sc(workspace_aux(0));
+    double4* boxes_dev;
+    const double4* src;
+    sc.add(boxes_dev, (size_t)n_boxes);
+    sc.stage_in(src, reinterpret_cast<const double4*>(boxes4), space, (size_t)n_boxes);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     GPK_LAUNCH("gpk_query_boxes", query_boxes_kernel, dim3((unsigned)((n_boxes + 255) / 256)), dim3(256), 0, s, src, n_boxes, boxes_dev);
     BoxRefineCtx cx = box_refine_ctx(&left, &right, idx, boxes_dev);
     return bbox_join(&left, &right, idx, 0u, out_counts, out_pairs, pair_capacity, n_pairs, space, s, boxes_dev,

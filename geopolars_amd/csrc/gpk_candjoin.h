@@ -127,20 +127,15 @@ inline int32_t rowwise_pairs(const char* who, const gpk_geoarray* a, const gpk_g
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return GPK_OK;
-    const uint32_t* rows_dev = b_rows;
-    void* out_dev = out;
     const size_t ob = elem * (size_t)n;
-    if (out_space != GPK_MEM_DEVICE) {
-        const size_t rb = sizeof(uint32_t) * (size_t)n;
-        GPK_TRY(workspace().begin(align256(ob) + (b_rows ? align256(rb) : 0) + 512));
-        out_dev = workspace().take(ob);
-        if (b_rows) {
-            uint32_t* r = (uint32_t*)workspace().take(rb);
-            GPK_HIP(hipMemcpyAsync(r, b_rows, rb, hipMemcpyHostToDevice, s));
-            rows_dev = r;
-        }
-    }
-    GPK_TRY(launch(rows_dev, out_dev, n, s));
+    Scratch sc(workspace());
+    uint8_t* out_dev;
+    const uint32_t* rows_dev;
+    sc.stage(out_dev, (uint8_t*)out, out_space, ob);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
+    GPK_TRY(launch(rows_dev, (void*)out_dev, n, s));
     return copy_out(out, out_space, out_dev, ob, s);
 }
 

@@ -39,32 +39,20 @@ int32_t clip_prologue(const char* op, const ClipSide& sa, const ClipSide& sb, bo
     return require_device();
 }
 
-// Host row lists and a host out_src are staged in the call's workspace; device ones are used where they are.
+// Host row lists and a host out_src are staged in the call's Scratch; device ones are used where they are.
 struct ClipLists {
     const uint32_t *a_rows, *b_rows;
     int32_t* src;     // where the kernels write the compaction map (nullptr: none asked for)
     bool src_staged;  // ... which the caller copies out to out_src at the end
 };
-// the workspace bytes clip_stage_lists takes; list_bytes: one list of n + 1 words, aligned
-inline size_t clip_staging_bytes(int32_t rows_space, const int32_t* out_src, int32_t src_space, size_t list_bytes) {
-    return (rows_space != GPK_MEM_DEVICE ? 2 * list_bytes : 0) + (out_src && src_space != GPK_MEM_DEVICE ? list_bytes : 0);
-}
-inline int32_t clip_stage_lists(Workspace& w, const uint32_t* a_rows, const uint32_t* b_rows, int32_t rows_space, int32_t* out_src, int32_t src_space, int64_t n,
-                                size_t list_bytes, hipStream_t s, ClipLists* out) {
-    out->a_rows = a_rows;
-    out->b_rows = b_rows;
-    if (rows_space != GPK_MEM_DEVICE && n > 0) {
-        const uint32_t** lists[2] = {&out->a_rows, &out->b_rows};
-        for (const uint32_t** list : lists) {
-            if (!*list) continue;
-            uint32_t* r = (uint32_t*)w.take(list_bytes);
-            GPK_HIP(hipMemcpyAsync(r, *list, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            *list = r;
-        }
-    }
+// records the carves (src: `words` entries; without pairs a row list is never read and stays the caller's); the caller uploads the host
+// lists with sc.upload after commit()
+inline void clip_lists_plan(Scratch& sc, const uint32_t* a_rows, const uint32_t* b_rows, int32_t rows_space, int32_t* out_src, int32_t src_space, int64_t n,
+                            size_t words, ClipLists* out) {
+    sc.stage_in(out->a_rows, a_rows, n > 0 ? rows_space : GPK_MEM_DEVICE, (size_t)n);
+    sc.stage_in(out->b_rows, b_rows, n > 0 ? rows_space : GPK_MEM_DEVICE, (size_t)n);
+    sc.stage(out->src, out_src, src_space, words);
     out->src_staged = out_src && src_space != GPK_MEM_DEVICE;
-    out->src = out->src_staged ? (int32_t*)w.take(list_bytes) : out_src;
-    return GPK_OK;
 }
 
 // the row of pair k on one side: rows[k] or k; an entry past the column's end: -1 (a null row)

@@ -263,8 +263,9 @@ static int32_t gather_header(const Shards& S, std::vector<int64_t>& hdr, hipStre
     if (S.me >= 0) {
         hdr_dev = S.c->scratch;  // (reserved with the communicator: HDR * (W + 1) words)
     } else {
-        GPK_TRY(workspace_aux(0).begin(sizeof(int64_t) * (size_t)(HDR * (W + 1)) + 512));
-        hdr_dev = (int64_t*)workspace_aux(0).take(sizeof(int64_t) * (size_t)(HDR * (W + 1)));
+        Scratch sc(workspace_aux(0));
+        sc.add(hdr_dev, (size_t)(HDR * (W + 1)));
+        GPK_TRY(sc.commit());
     }
     const int n_rows = S.me < 0 ? W : 1;
     std::vector<int64_t> rows((size_t)HDR * n_rows, 0);
@@ -380,15 +381,11 @@ static int32_t assemble_column(const Shards& S, hipStream_t s, gpk_geoarray** ou
         int64_t local_rows = 0;
         for (int k = 0; k < W; ++k)
             if (S.holds(k)) local_rows += hdr[(size_t)HDR * k + 0];
-        rc = workspace_aux(1).begin((validity ? (size_t)tot[0] + (size_t)local_rows : 0) + 2048);
-        if (rc == GPK_OK) {
-            zero_word = (int32_t*)workspace_aux(1).take(256);
-            if (validity) {
-                all_bytes = (uint8_t*)workspace_aux(1).take((size_t)tot[0]);
-                my_bytes = (uint8_t*)workspace_aux(1).take((size_t)(local_rows ? local_rows : 1));
-            }
-            if (!zero_word || (validity && (!all_bytes || !my_bytes))) rc = fail(GPK_ERR_OOM, "allgatherv: scratch");
-        }
+        Scratch sc(workspace_aux(1));
+        sc.add(zero_word, 64);
+        sc.add_if(validity, all_bytes, (size_t)tot[0]);
+        sc.add_if(validity, my_bytes, (size_t)local_rows);
+        rc = sc.commit();
     }
     GPK_TRY(agree(S, rc, s));
     {
@@ -564,8 +561,10 @@ int32_t gpk_allgatherv_rows_f64(gpk_comm* c, const double* local_dev, int64_t n_
     if (!c || !out_total_rows || n_local < 0 || width < 1 || (n_local > 0 && !local_dev)) return fail(GPK_ERR_INVALID_ARGUMENT, "bad argument");
     const Rccl* r = c->table;
     hipStream_t s = (hipStream_t)stream;
-    GPK_TRY(workspace_aux(0).begin(sizeof(int64_t) * (size_t)(c->world + 1) + 512));
-    int64_t* hdr_dev = (int64_t*)workspace_aux(0).take(sizeof(int64_t) * (size_t)(c->world + 1));
+    Scratch sc(workspace_aux(0));
+    int64_t* hdr_dev;
+    sc.add(hdr_dev, (size_t)(c->world + 1));
+    GPK_TRY(sc.commit());
     GPK_HIP(hipMemcpyAsync(hdr_dev + c->world, &n_local, sizeof n_local, hipMemcpyHostToDevice, s));
     GPK_NCCL(r, r->AllGather(hdr_dev + c->world, hdr_dev, 1, ncclInt64, c->comm, s));
     std::vector<int64_t> cnt((size_t)c->world), begin((size_t)c->world + 1, 0);

@@ -86,12 +86,10 @@ namespace gpk {
 // ---- per-thread grow-only scratch ------------------------------------------------------------
 // Steady-state calls do no hipMalloc/hipFree.  One arena per calling thread keeps the ABI
 // re-entrant; a thread that issues calls on several streams must order them itself.
+// An arena is sized and carved by a Scratch (gpk_scratch.h) and by nothing else: the entry point records its carves, commit() begins
+// the arena with their sum and hands out the pointers.  begin() grows the arena (and invalidates earlier carves) when it must.
 class Workspace {
   public:
-    // carve `bytes` (256-byte aligned) out of the arena; grows (and invalidates earlier carves) only
-    // between begin() calls.
-    int32_t begin(size_t total_bytes);
-    void* take(size_t bytes);
     void trim(size_t keep_max);  // give the arena back when it has grown beyond keep_max bytes (after a device sync)
     ~Workspace();
     // A caller that leaves the same small record at the same place of the arena call after call (the rare arm's arguments of the
@@ -101,6 +99,10 @@ class Workspace {
     void set_tag(const void* where, const void* bytes, size_t n);
 
   private:
+    friend class Scratch;
+    friend class ScratchEstimate;  // (the index build and the WKB decode: an estimate, every carve checked)
+    int32_t begin(size_t total_bytes);
+    void* take(size_t bytes);  // 256-byte aligned; nullptr past the end of what begin() sized
     char* base_ = nullptr;
     size_t cap_ = 0, used_ = 0;
     int device_ = -1;
@@ -203,3 +205,5 @@ __host__ __device__ inline bool is_polygonal(int32_t t) { return t == GPK_GEOM_P
 __host__ __device__ inline bool is_lineal(int32_t t) { return t == GPK_GEOM_LINESTRING || t == GPK_GEOM_MULTILINESTRING; }
 
 }  // namespace gpk
+
+#include "gpk_scratch.h"

@@ -74,16 +74,13 @@ int32_t gpk_reproject(const gpk_geoarray* a, int32_t src_epsg, int32_t dst_epsg,
     const size_t ob = sizeof(double) * 2 * (size_t)n;
     if (src_epsg == dst_epsg) return copy_out(out_xy, out_space, a->d.xy, ob, s);  // same -> same is a copy
     const bool stage = out_space != GPK_MEM_DEVICE;
-    void* out_dev = out_xy;
-    unsigned long long* cnt = nullptr;
-    if (stage || n_failed) {
-        GPK_TRY(workspace().begin((stage ? ob : 0) + 1024));
-        if (stage) out_dev = workspace().take(ob);
-        if (n_failed) {
-            cnt = (unsigned long long*)workspace().take(sizeof *cnt);
-            GPK_HIP(hipMemsetAsync(cnt, 0, sizeof *cnt, s));
-        }
-    }
+    Scratch sc(workspace());
+    double* out_dev;
+    unsigned long long* cnt;
+    sc.stage(out_dev, out_xy, out_space, 2 * (size_t)n);
+    sc.add_if(n_failed != nullptr, cnt, 1);
+    GPK_TRY(sc.commit());
+    if (n_failed) GPK_HIP(hipMemsetAsync(cnt, 0, sizeof *cnt, s));
     int64_t blocks = (n + 255) / 256;
     const int64_t cap = (int64_t)cu_count() * 8;
     if (blocks > cap) blocks = cap;

@@ -356,20 +356,18 @@ extern "C" int32_t gpk_dwithin_rowwise(const gpk_geoarray* a, const gpk_geoarray
     if (b_rows && a->d.type != GPK_GEOM_POINT && b->d.type == GPK_GEOM_POINT)
         return fail(GPK_ERR_INVALID_ARGUMENT, "dwithin: b_rows requires the POINT array on the left");
     if (n == 0) return GPK_OK;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    const size_t db = sizeof(double) * (size_t)n, rb = sizeof(uint32_t) * (size_t)n;
     // (the distance call carves workspace() itself; this call's buffers live in an auxiliary arena)
-    GPK_TRY(workspace_aux(0).begin(align256(db) + (b_rows && host_out ? align256(rb) : 0) + (host_out ? align256((size_t)n) : 0) + 512));
-    double* d = (double*)workspace_aux(0).take(db);
-    const uint32_t* rows_dev = b_rows;
-    if (b_rows && host_out) {
-        uint32_t* r = (uint32_t*)workspace_aux(0).take(rb);
-        GPK_HIP(hipMemcpyAsync(r, b_rows, rb, hipMemcpyHostToDevice, s));
-        rows_dev = r;
-    }
-    uint8_t* out_dev = host_out ? (uint8_t*)workspace_aux(0).take((size_t)n) : out;
+    Scratch sc(workspace_aux(0));
+    double* d;
+    const uint32_t* rows_dev;
+    uint8_t* out_dev;
+    sc.add(d, (size_t)n);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     GPK_TRY(gpk_distance_rowwise(a, b, rows_dev, d, GPK_MEM_DEVICE, stream));
     GPK_LAUNCH("gpk_dwithin_threshold", dwithin_threshold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a->d, b->d, rows_dev,
                (const double*)d, distance, n, out_dev);
-    return copy_out(out, out_space, out_dev, (size_t)n, s);
+    return sc.copy_back(s);
 }

@@ -174,23 +174,21 @@ extern "C" int32_t gpk_frechet_distance(const gpk_geoarray* a, const gpk_geoarra
     GPK_TRY(require_device());
     if (n == 0) return GPK_OK;
     hipStream_t s = (hipStream_t)stream;
-    const size_t ob = sizeof(double) * (size_t)n, lb = sizeof(uint32_t) * (size_t)n;
+    const size_t ob = sizeof(double) * (size_t)n;
     const bool host_out = out_space != GPK_MEM_DEVICE;
-    GPK_TRY(workspace().begin((host_out ? align256(ob) : 0) + (b_rows && host_out ? align256(lb) : 0) + align256(lb) + 1024));
-    double* out_dev = host_out ? (double*)workspace().take(ob) : out;
-    const uint32_t* rows_dev = b_rows;
-    if (b_rows && host_out) {
-        uint32_t* r = (uint32_t*)workspace().take(lb);
-        GPK_HIP(hipMemcpyAsync(r, b_rows, lb, hipMemcpyHostToDevice, s));
-        rows_dev = r;
-    }
-    uint32_t* large_rows = (uint32_t*)workspace().take(lb);
-    uint32_t* n_large = (uint32_t*)workspace().take(sizeof(uint32_t));
-    unsigned long long* cnt = nullptr;
-    if (n_over) {
-        cnt = (unsigned long long*)workspace().take(sizeof *cnt);
-        GPK_HIP(hipMemsetAsync(cnt, 0, sizeof *cnt, s));
-    }
+    Scratch sc(workspace());
+    double* out_dev;
+    const uint32_t* rows_dev;
+    uint32_t *large_rows, *n_large;
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    sc.add(large_rows, (size_t)n);
+    sc.add(n_large, 1);
+    unsigned long long* cnt;
+    sc.add_if(n_over != nullptr, cnt, 1);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
+    if (n_over) GPK_HIP(hipMemsetAsync(cnt, 0, sizeof *cnt, s));
     GPK_TRY(frechet_dev(a->d, b->d, rows_dev, n, (int)subdivisions, out_dev, large_rows, n_large, cnt, s));
     if (n_over) {  // as n_failed of gpk_reproject: the count is read back, so the call waits for the stream
         unsigned long long c = 0;
@@ -200,5 +198,5 @@ extern "C" int32_t gpk_frechet_distance(const gpk_geoarray* a, const gpk_geoarra
         *n_over = (int64_t)c;
         return GPK_OK;
     }
-    return copy_out(out, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }

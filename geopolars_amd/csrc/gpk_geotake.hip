@@ -177,9 +177,9 @@ __global__ __launch_bounds__(gt::LANES) void geotake_fill_kernel(Payload p, cons
 
 inline dim3 lanes_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
 
-// idx (take) or mask (filter): exactly one is given; both are device pointers (staged by the callers)
-int32_t run(const char* op, const gpk_geoarray* a, const long long* idx, const uint8_t* mask, int mask_bits, int64_t n_slots, hipStream_t s,
-            gpk_geoarray** out, int64_t* n_kept) {
+// idx (take) or mask (filter): exactly one is given, in the caller's memory space (a host one is staged here; the mask has mask_bytes bytes)
+int32_t run(const char* op, const gpk_geoarray* a, const long long* idx_in, const uint8_t* mask_in, int mask_bits, size_t mask_bytes, int32_t in_space,
+            int64_t n_slots, hipStream_t s, gpk_geoarray** out, int64_t* n_kept) {
     const DevGeo& d = a->d;
     const TakeLevels L = levels_of(d);
     int device = 0;
@@ -193,29 +193,34 @@ int32_t run(const char* op, const gpk_geoarray* a, const long long* idx, const u
         return GPK_OK;
     }
 
-    // ---- scratch (carved by the callers' begin(); see take_scratch_bytes)
-    Workspace& w = workspace();
+    // ---- scratch
+    Scratch plan(workspace());
     const int64_t n = n_slots, at = (n + 255) / 256;
-    const size_t i32 = align256(sizeof(int32_t) * (size_t)(n + 1)), tot = align256(sizeof(unsigned long long) * (size_t)(at + 2));
+    const size_t words = (size_t)(n + 1), tot = (size_t)(at + 2);
+    const long long* idx;
+    const uint8_t* mask;
+    plan.stage_in(idx, idx_in, in_space, (size_t)n);
+    plan.stage_in(mask, mask_in, in_space, mask_bytes);
     TakeScratch sc{};
     int32_t* dst_lo[gt::MAX_LEVELS] = {nullptr, nullptr, nullptr};
     unsigned long long* btot[gt::MAX_LEVELS + 1] = {nullptr, nullptr, nullptr, nullptr};
     for (int l = 0; l < L.n; ++l) {
-        sc.src_lo[l] = (int32_t*)w.take(i32);
-        sc.cnt[l] = (int32_t*)w.take(i32);
-        dst_lo[l] = (int32_t*)w.take(i32);
-        btot[l] = (unsigned long long*)w.take(tot);
+        plan.add_n(words, sc.src_lo[l], sc.cnt[l], dst_lo[l]);
+        plan.add(btot[l], tot);
     }
-    if (L.n == 0) sc.src_lo[0] = (int32_t*)w.take(i32);  // (POINT: the source row of every slot; idx and mask are not read after the wait)
-    int32_t *keep = nullptr, *row_at = nullptr;
-    if (mask) {
-        keep = (int32_t*)w.take(i32);
-        row_at = (int32_t*)w.take(i32);
-        btot[gt::MAX_LEVELS] = (unsigned long long*)w.take(tot);
-    }
-    uint8_t* ok = (uint8_t*)w.take((size_t)n);
-    uint8_t* ok_rows = mask ? (uint8_t*)w.take((size_t)n) : ok;  // the flags at their output rows
-    unsigned long long* record = (unsigned long long*)w.take(256);
+    if (L.n == 0) plan.add(sc.src_lo[0], words);  // (POINT: the source row of every slot; idx and mask are not read after the wait)
+    int32_t *keep, *row_at;
+    plan.add_if(mask_in != nullptr, keep, words);
+    plan.add_if(mask_in != nullptr, row_at, words);
+    plan.add_if(mask_in != nullptr, btot[gt::MAX_LEVELS], tot);
+    uint8_t *ok, *ok_rows;  // ok_rows: the flags at their output rows
+    unsigned long long* record;
+    plan.add(ok, (size_t)n);
+    plan.add_if(mask_in != nullptr, ok_rows, (size_t)n);
+    plan.add(record, 32);
+    GPK_TRY(plan.commit());
+    if (!mask_in) ok_rows = ok;
+    GPK_TRY(plan.upload(s));
 
     // ---- 1, 2: count, scan, the one read-back
     GPK_HIP(hipMemsetAsync(record, 0, 64, s));
@@ -259,17 +264,17 @@ int32_t run(const char* op, const gpk_geoarray* a, const long long* idx, const u
     // ---- 4: fill — level l's entries are located through the row starts of level l - 1, the coordinates through the last level's.
     // The strip tables are sized by the totals: a second arena (the first one's carves stay valid).
     int64_t n_strips[gt::MAX_LEVELS] = {0, 0, 0};  // [l]: of the elements located through dst_lo[l]
-    size_t table_bytes = 256;
+    int32_t* first_rows[gt::MAX_LEVELS];
+    Scratch tables(workspace_aux(0));
     for (int l = 0; l < L.n; ++l) {
         n_strips[l] = ((int64_t)rec[l] + gt::STRIP - 1) / gt::STRIP;
-        table_bytes += align256(sizeof(int32_t) * (size_t)(n_strips[l] + 1));
+        tables.add_if(rec[l] > 0, first_rows[l], (size_t)(n_strips[l] + 1));
     }
-    Workspace& w2 = workspace_aux(0);
-    GPK_TRY(w2.begin(table_bytes));
+    GPK_TRY(tables.commit());
     for (int l = 0; l < L.n; ++l) {
         const int64_t total = (int64_t)rec[l];
         if (total == 0) continue;
-        int32_t* first_row = (int32_t*)w2.take(sizeof(int32_t) * (size_t)(n_strips[l] + 1));
+        int32_t* first_row = first_rows[l];
         GPK_LAUNCH("gpk_geotake_strips", geotake_strips_kernel, lanes_grid(n_strips[l]), dim3(256), 0, s, (const int32_t*)dst_lo[l], n, n_strips[l], first_row);
         const dim3 grid((unsigned)n_strips[l]);
         if (l + 1 < L.n) {
@@ -284,13 +289,6 @@ int32_t run(const char* op, const gpk_geoarray* a, const long long* idx, const u
     }
     col.release(out);
     return GPK_OK;
-}
-
-// the workspace bytes of run() for n slots (every carve there, rounded up)
-size_t take_scratch_bytes(int64_t n_slots) {
-    const int64_t n = n_slots > 0 ? n_slots : 1;
-    const size_t i32 = align256(sizeof(int32_t) * (size_t)(n + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n + 255) / 256 + 2));
-    return (3 * gt::MAX_LEVELS + 2) * i32 + (gt::MAX_LEVELS + 1) * tot + 2 * align256((size_t)n) + 256 + 1024;
 }
 
 }  // namespace
@@ -309,15 +307,7 @@ int32_t gpk_geoarray_take(const gpk_geoarray* a, const int64_t* idx, int64_t n_i
     if (idx_space != GPK_MEM_HOST && idx_space != GPK_MEM_DEVICE) return fail(GPK_ERR_INVALID_ARGUMENT, "geoarray_take: unknown memory space %d", idx_space);
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    const size_t idx_bytes = sizeof(long long) * (size_t)n_idx;
-    GPK_TRY(workspace().begin(take_scratch_bytes(n_idx) + (idx_space == GPK_MEM_DEVICE ? 0 : align256(idx_bytes))));
-    const long long* ix = (const long long*)idx;
-    if (idx_space != GPK_MEM_DEVICE && n_idx > 0) {
-        long long* staged = (long long*)workspace().take(idx_bytes);
-        GPK_HIP(hipMemcpyAsync(staged, idx, idx_bytes, hipMemcpyHostToDevice, s));
-        ix = staged;
-    }
-    return run("geoarray_take", a, ix, nullptr, 0, n_idx, s, out, nullptr);
+    return run("geoarray_take", a, (const long long*)idx, nullptr, 0, 0, idx_space, n_idx, s, out, nullptr);
 }
 
 int32_t gpk_geoarray_filter(const gpk_geoarray* a, const uint8_t* mask, int32_t mask_bits, int32_t mask_space, void* stream, gpk_geoarray** out,
@@ -334,14 +324,7 @@ int32_t gpk_geoarray_filter(const gpk_geoarray* a, const uint8_t* mask, int32_t 
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
     const size_t mask_bytes = mask_bits == 1 ? (size_t)((n + 7) / 8) : (size_t)n;
-    GPK_TRY(workspace().begin(take_scratch_bytes(n) + (mask_space == GPK_MEM_DEVICE ? 0 : align256(mask_bytes))));
-    const uint8_t* m = mask;
-    if (mask_space != GPK_MEM_DEVICE && n > 0) {
-        uint8_t* staged = (uint8_t*)workspace().take(mask_bytes);
-        GPK_HIP(hipMemcpyAsync(staged, mask, mask_bytes, hipMemcpyHostToDevice, s));
-        m = staged;
-    }
-    return run("geoarray_filter", a, nullptr, m, mask_bits, n, s, out, n_kept);
+    return run("geoarray_filter", a, nullptr, mask, mask_bits, mask_bytes, mask_space, n, s, out, n_kept);
 }
 
 }  // extern "C"

@@ -246,12 +246,14 @@ int32_t gpk_index_build_ex(const gpk_geoarray* a, int32_t parts, const double* b
     // 2. extent + grid parameters, all on device (two stages beyond a few thousand boxes: one work-group walked 5M of them in 4.7 ms)
     const int64_t n_blocks = (n_cells + 255) / 256;
     const int64_t ext_blocks = n > 65536 ? 1024 : 0;
-    IX_TRY(workspace().begin(align256(sizeof(int32_t) * (size_t)(n_cells + 1)) * 2 +
-                             align256(sizeof(unsigned long long) * (size_t)(n_blocks + 1)) + align256(sizeof(double4) * 1024) + 1024));
-    int32_t* cell_cnt = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_cells + 1));
-    int32_t* cursor = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_cells + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(n_blocks + 1));
-    double4* ext_part = (double4*)workspace().take(sizeof(double4) * 1024);
+    Scratch sc(workspace());
+    int32_t *cell_cnt, *cursor;
+    unsigned long long* btot;
+    double4* ext_part;
+    sc.add_n((size_t)(n_cells + 1), cell_cnt, cursor);
+    sc.add(btot, (size_t)(n_blocks + 1));
+    sc.add(ext_part, 1024);
+    IX_TRY(sc.commit());
     if (ext_blocks) {
         GPK_LAUNCH_OR(cleanup, "gpk_index_extent_partial", extent_partial_kernel, dim3((unsigned)ext_blocks), dim3(256), 0, s, bbox, n, ext_part);
         GPK_LAUNCH_OR(cleanup, "gpk_index_extent", extent_kernel, dim3(1), dim3(1024), 0, s, (const double4*)ext_part, ext_blocks, gdim, gdim, grid);

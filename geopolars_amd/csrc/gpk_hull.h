@@ -39,13 +39,15 @@ struct HullStage {
     double2* stack;
     int32_t* sizes;
     int32_t* n_pts;
+    // the stage's own temporaries
+    double2* sorted;
+    int32_t *idx_scratch, *big_list, *mid_list;
 };
 __host__ __device__ __forceinline__ double2* hull_slice(double2* stack, int c0, int64_t g) { return stack + 2 * (int64_t)c0 + 2 * g; }
 
-// workspace bytes hull_stage takes for a column of n rows and nc coordinates
-size_t hull_stage_bytes(int64_t n, int64_t nc);
-// Takes its slices from workspace() — the caller has reserved hull_stage_bytes(n, nc) plus its own needs with workspace().begin and takes
-// its own slices afterwards — and, when the column has rows, launches the hull kernels on s.
-int32_t hull_stage(const gpk_geoarray* a, HullStage* out, hipStream_t s);
+// hull_stage_plan adds the stage's carves for a column of n rows and nc coordinates to the caller's Scratch (on workspace()), which the
+// caller commits after adding its own; hull_stage then, when the column has rows, launches the hull kernels on s.
+void hull_stage_plan(Scratch& sc, int64_t n, int64_t nc, HullStage* h);
+int32_t hull_stage(const gpk_geoarray* a, const HullStage& h, hipStream_t s);
 
 }  // namespace gpk

@@ -308,23 +308,20 @@ __global__ __launch_bounds__(256) void hull_compact_kernel(DevGeo a, const doubl
 }
 
 // ---- the hull stage (gpk_hull.h): everything up to the scratch hulls -------------------------------------------------------------------
-size_t hull_stage_bytes(int64_t n, int64_t nc) {
-    const size_t off_bytes = sizeof(int32_t) * (size_t)(n + 1);
-    return align256(sizeof(double2) * (size_t)(nc + 1)) + align256(sizeof(double2) * (2 * (size_t)nc + 2 * (size_t)n + 2)) + 4 * align256(off_bytes) +
-           align256(sizeof(int32_t) * (2 * (size_t)nc + 2 * (size_t)n + 2));
+void hull_stage_plan(Scratch& sc, int64_t n, int64_t nc, HullStage* h) {
+    const size_t rows = (size_t)(n + 1);
+    sc.add(h->sorted, (size_t)(nc + 1));
+    sc.add(h->stack, 2 * (size_t)nc + 2 * (size_t)n + 2);
+    sc.add_n(rows, h->sizes, h->n_pts);
+    sc.add(h->idx_scratch, 2 * (size_t)nc + 2 * (size_t)n + 2);
+    sc.add(h->big_list, rows);  // [0, n): ids of the geometries beyond HULL_CAP points, [n]: their number
+    sc.add(h->mid_list, rows);  // the same for 65 .. HULL_CAP points
 }
 
-int32_t hull_stage(const gpk_geoarray* a, HullStage* out, hipStream_t s) {
-    const int64_t n = a->d.n_geoms, nc = a->d.n_coords;
-    const size_t off_bytes = sizeof(int32_t) * (size_t)(n + 1);
-    double2* sorted = (double2*)workspace().take(sizeof(double2) * (size_t)(nc + 1));
-    double2* stack = (double2*)workspace().take(sizeof(double2) * (2 * (size_t)nc + 2 * (size_t)n + 2));
-    int32_t* sizes = (int32_t*)workspace().take(off_bytes);
-    int32_t* n_pts = (int32_t*)workspace().take(off_bytes);
-    int32_t* idx_scratch = (int32_t*)workspace().take(sizeof(int32_t) * (2 * (size_t)nc + 2 * (size_t)n + 2));
-    int32_t* big_list = (int32_t*)workspace().take(off_bytes);  // [0, n): ids of the geometries beyond HULL_CAP points, [n]: their number
-    int32_t* mid_list = (int32_t*)workspace().take(off_bytes);  // the same for 65 .. HULL_CAP points
-    *out = HullStage{stack, sizes, n_pts};
+int32_t hull_stage(const gpk_geoarray* a, const HullStage& h, hipStream_t s) {
+    const int64_t n = a->d.n_geoms;
+    double2 *sorted = h.sorted, *stack = h.stack;
+    int32_t *sizes = h.sizes, *n_pts = h.n_pts, *idx_scratch = h.idx_scratch, *big_list = h.big_list, *mid_list = h.mid_list;
     if (n == 0) return GPK_OK;
     const dim3 block(256);
     GPK_HIP(hipMemsetAsync(big_list + n, 0, sizeof(int32_t), s));
@@ -362,14 +359,17 @@ extern "C" int32_t gpk_convex_hull(const gpk_geoarray* a, double* out_xy, int32_
     const size_t off_bytes = sizeof(int32_t) * (size_t)(n + 1);
     const int64_t nb = (n + 255) / 256;
     const bool host_out = out_space != GPK_MEM_DEVICE;
-    size_t need = hull_stage_bytes(n, nc) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + 1024;
-    if (host_out) need += align256(sizeof(double2) * cap_coords) + align256(off_bytes);
-    GPK_TRY(workspace().begin(need));
+    Scratch sc(workspace());
     HullStage h;
-    GPK_TRY(hull_stage(a, &h, s));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
-    double2* out_dev = host_out ? (double2*)workspace().take(sizeof(double2) * cap_coords) : (double2*)out_xy;
-    int32_t* off_dev = host_out ? (int32_t*)workspace().take(off_bytes) : out_ring_offsets;
+    unsigned long long* btot;
+    double2* out_dev;
+    int32_t* off_dev;
+    hull_stage_plan(sc, n, nc, &h);
+    sc.add(btot, (size_t)(nb + 2));
+    sc.stage(out_dev, (double2*)out_xy, out_space, cap_coords);
+    sc.stage(off_dev, out_ring_offsets, out_space, (size_t)(n + 1));
+    GPK_TRY(sc.commit());
+    GPK_TRY(hull_stage(a, h, s));
     if (n == 0) {
         GPK_HIP(hipMemsetAsync(off_dev, 0, sizeof(int32_t), s));
         return copy_out(out_ring_offsets, out_space, off_dev, sizeof(int32_t), s);

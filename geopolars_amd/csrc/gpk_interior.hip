@@ -431,15 +431,19 @@ int32_t run(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, double* o
     const DevGeo& g = a->d;
     const int64_t n = g.n_geoms;
     if (n > (int64_t)INT32_MAX - 1) return fail(GPK_ERR_INVALID_ARGUMENT, "representative_point: more than 2^31 - 2 rows");
-    const bool host_out = out_space != GPK_MEM_DEVICE;
     const bool poly = is_polygonal(g.type), point = g.type == GPK_GEOM_POINT;
-    const size_t xy_bytes = sizeof(double2) * (size_t)n, w_bytes = sizeof(double) * (size_t)n, list_bytes = sizeof(int32_t) * (size_t)(n + 1);
-    Workspace& ws = workspace_aux(1);  // (gpk_centroid below uses workspace())
-    GPK_TRY(ws.begin(align256(list_bytes) + 2 * align256(xy_bytes) + 2 * align256((size_t)n) + align256(w_bytes) + 1024));
-    int32_t* big = (int32_t*)ws.take(list_bytes);
-    double2* xy_dev = host_out ? (double2*)ws.take(xy_bytes) : (double2*)out_xy;
-    uint8_t* valid_dev = out_valid ? (host_out ? (uint8_t*)ws.take((size_t)n) : out_valid) : nullptr;
-    double* width_dev = out_width ? (host_out ? (double*)ws.take(w_bytes) : out_width) : nullptr;
+    const size_t xy_bytes = sizeof(double2) * (size_t)n, w_bytes = sizeof(double) * (size_t)n;
+    Scratch sc(workspace_aux(1));  // (gpk_centroid below uses workspace())
+    int32_t* big;
+    double2 *xy_dev, *cen = nullptr;  // cen, cen_valid: the centroids of a lineal column's rows
+    uint8_t *valid_dev, *cen_valid = nullptr;
+    double* width_dev;
+    sc.add(big, (size_t)(n + 1));
+    sc.stage(xy_dev, (double2*)out_xy, out_space, (size_t)n);
+    sc.stage(valid_dev, out_valid, out_space, (size_t)n);
+    sc.stage(width_dev, out_width, out_space, (size_t)n);
+    if (!point && !poly) sc.add_n((size_t)n, cen, cen_valid);
+    GPK_TRY(sc.commit());
     if (point) {
         GPK_LAUNCH("gpk_representative_point", interior_point_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, n, xy_dev, valid_dev, width_dev);
     } else {
@@ -456,8 +460,6 @@ int32_t run(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, double* o
             GPK_LAUNCH("gpk_representative_point_large", interior_poly_big_kernel, dim3((unsigned)blocks), dim3(ip::INT_BLOCK_THREADS), 0, s, g, big, xy_dev,
                        valid_dev, width_dev);
         } else {
-            double2* cen = (double2*)ws.take(xy_bytes);
-            uint8_t* cen_valid = (uint8_t*)ws.take((size_t)n);
             GPK_TRY(gpk_centroid(a, (double*)cen, cen_valid, GPK_MEM_DEVICE, s));
             if (G == ip::INT_G_SMALL)
                 GPK_LAUNCH("gpk_representative_point", (interior_vert_rows_kernel<ip::INT_G_SMALL>), grid, dim3(256), 0, s, g, n, cen, cen_valid, big, xy_dev,

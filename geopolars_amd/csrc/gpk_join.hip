@@ -1484,8 +1484,6 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
     const int tile_points = flow ? 64 * flow_p : (chain ? 64 * CHAIN_PPT : (lean ? LEAN_TILE : (one_per_lane ? PIP_BLOCK : PIP_TILE)));
     const int64_t n_blocks = (n + tile_points - 1) / tile_points;
     const bool want_pairs = pair_capacity > 0;
-    const size_t counts_bytes = sizeof(uint32_t) * (size_t)n;
-    const size_t pairs_bytes = sizeof(uint32_t) * 2 * (size_t)pair_capacity;
     const int64_t n_super = (n_blocks >> PIP_SUPER_SHIFT) + 1;
     const int64_t n_wblocks = (n + PIP_WTILE - 1) / PIP_WTILE;
     // words in the multi-hit pool (a chain launch has no multi-hit rows in it: a rare row with several hits is CODE_MULTI)
@@ -1498,25 +1496,26 @@ static int32_t pip_join_enqueue(const gpk_geoarray* left, const gpk_geoarray* ri
     }
     const bool fused = flow;  // (no result codes, no tile totals, no writer launch)
     const size_t stage_bytes = flow ? pip_flow_pool_bytes(n) : 0;
-    size_t need = align256(fused ? 64 : counts_bytes + 64) /*code*/ + align256(sizeof(unsigned long long) * (size_t)(n_blocks + n_super + 3)) +
-                  align256(sizeof(uint32_t) * (size_t)multi_cap) + align256(sizeof(ChainCold)) + align256(stage_bytes) + 1024;
-    if (host_out && out_counts) need += align256(counts_bytes);
-    if (host_out && want_pairs) need += align256(pairs_bytes);
     // scratch of the stream-ordered join: one arena per (calling thread, stream), so that joins a thread enqueues on
     // DIFFERENT streams never share code / totals buffers (they used to: the header asked callers not to)
+    // (the order and sizes of the carves depend on the call's arguments alone: `cold` lands at the same place call after call)
     Workspace& ws = workspace_for_stream(s);
-    int32_t rc = ws.begin(need);
-    if (rc != GPK_OK) return rc;
-    uint32_t* code = (uint32_t*)ws.take(fused ? 64 : counts_bytes + 64);
-    unsigned long long* btot = (unsigned long long*)ws.take(sizeof(unsigned long long) * (size_t)(n_blocks + n_super + 3));
+    Scratch sc(ws);
+    uint32_t *code, *multi_pool, *counts_dev, *pairs_dev;
+    unsigned long long* btot;
+    ChainCold* cold;
+    uint2* stage;
+    sc.add(code, fused ? 16 : (size_t)n + 16);  // (the result codes of the rows, 64 bytes of padding)
+    sc.add(btot, (size_t)(n_blocks + n_super + 3));
+    sc.add(multi_pool, (size_t)multi_cap);
+    sc.add(cold, 1);
+    sc.add_if(flow, stage, (stage_bytes + sizeof(uint2) - 1) / sizeof(uint2));
+    sc.stage(counts_dev, out_counts, host_out ? GPK_MEM_HOST : GPK_MEM_DEVICE, (size_t)n);
+    sc.stage(pairs_dev, want_pairs ? out_pairs : nullptr, host_out ? GPK_MEM_HOST : GPK_MEM_DEVICE, 2 * (size_t)pair_capacity);
+    GPK_TRY(sc.commit());
     unsigned long long* stot = btot + n_blocks;     // n_super super-tile totals
     unsigned long long* grand = stot + n_super;     // total hits
     uint32_t* multi_top = (uint32_t*)(grand + 1);   // words used in the multi-hit pool (zeroed with the totals)
-    uint32_t* multi_pool = (uint32_t*)ws.take(sizeof(uint32_t) * (size_t)multi_cap);
-    ChainCold* cold = (ChainCold*)ws.take(sizeof(ChainCold));
-    uint2* stage = stage_bytes ? (uint2*)ws.take(stage_bytes) : nullptr;
-    uint32_t* counts_dev = out_counts ? (host_out ? (uint32_t*)ws.take(counts_bytes) : out_counts) : nullptr;
-    uint32_t* pairs_dev = want_pairs ? (host_out ? (uint32_t*)ws.take(pairs_bytes) : out_pairs) : nullptr;
 
     unsigned long long* stats = join_stats_buffer();  // nullptr unless gpk_join_stats_enable(1)
     if (fused) {  // nothing to zero; the rare arm's arguments are written when they differ from what this arena holds
@@ -1663,7 +1662,6 @@ __global__ __launch_bounds__(256) void swap_counts_kernel(const unsigned long lo
 static int32_t swapped_pip_join(const gpk_geoarray* polys, const gpk_geoarray* pts, uint32_t left_row_base, uint32_t* out_counts,
                                 uint32_t* out_pairs, int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, hipStream_t s) {
     const int64_t n_left = polys->d.n_geoms, n_pts = pts->d.n_geoms;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
     const bool want_pairs = pair_capacity > 0;
     *n_pairs = 0;
     if (n_left == 0) return GPK_OK;
@@ -1684,15 +1682,17 @@ static int32_t swapped_pip_join(const gpk_geoarray* polys, const gpk_geoarray* p
     int bits = 33;
     while (bits < 64 && (1ll << (bits - 32)) < n_left) ++bits;
     GPK_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, t1, 0, bits, s));
-    rc = workspace_aux(0).begin(align256(8 * t1) * 3 + align256(sort_bytes + 256) + align256(4 * (size_t)(n_left + 1)) +
-                                (host_out && want_pairs ? align256(8 * (size_t)pair_capacity) : 0) + 1024);
+    Scratch sc(workspace_aux(0));
+    uint2 *tmp_pairs, *pairs_dev;
+    unsigned long long *keys, *sorted;
+    void* sort_tmp;
+    uint32_t* counts_dev;
+    sc.add_n(t1, tmp_pairs, keys, sorted);
+    sc.add_bytes(sort_tmp, sort_bytes + 256);
+    sc.stage(counts_dev, out_counts, out_space, (size_t)(n_left + 1));
+    sc.stage(pairs_dev, want_pairs ? (uint2*)out_pairs : nullptr, out_space, (size_t)pair_capacity);
+    rc = sc.commit();
     if (rc != GPK_OK) return done(rc);
-    uint2* tmp_pairs = (uint2*)workspace_aux(0).take(8 * t1);
-    unsigned long long* keys = (unsigned long long*)workspace_aux(0).take(8 * t1);
-    unsigned long long* sorted = (unsigned long long*)workspace_aux(0).take(8 * t1);
-    void* sort_tmp = workspace_aux(0).take(sort_bytes + 256);
-    uint32_t* counts_dev = out_counts ? (host_out ? (uint32_t*)workspace_aux(0).take(4 * (size_t)(n_left + 1)) : out_counts) : nullptr;
-    uint2* pairs_dev = want_pairs ? (host_out ? (uint2*)workspace_aux(0).take(8 * (size_t)pair_capacity) : (uint2*)out_pairs) : nullptr;
     auto run = [&]() -> int32_t {
         if (total > 0) {
             int64_t again = 0;

@@ -247,11 +247,11 @@ int32_t gpk_geodesic_length(const gpk_geoarray* a, int32_t method, double* out, 
     int64_t n_seq;
     seq_level(a->d, &seq_off, &n_seq);
     if (a->d.type == GPK_GEOM_MULTIPOINT) n_seq = 0;
-    const bool host = out_space != GPK_MEM_DEVICE;
-    const size_t ob = sizeof(double) * (size_t)n, sb = sizeof(double) * (size_t)(n_seq > 0 ? n_seq : 1);
-    GPK_TRY(workspace_aux(0).begin(align256(sb) + (host ? align256(ob) : 0) + 512));
-    double* seq_len = (double*)workspace_aux(0).take(sb);
-    double* out_dev = host ? (double*)workspace_aux(0).take(ob) : out;
+    Scratch sc(workspace_aux(0));
+    double *seq_len, *out_dev;
+    sc.add(seq_len, (size_t)n_seq);
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
     if (n_seq > 0) {
         const double mean = (double)a->d.n_coords / (double)n_seq;
         // (Karney's method is a few hundred f64 operations per segment with a data-dependent Newton loop: always the wide groups)
@@ -270,7 +270,7 @@ int32_t gpk_geodesic_length(const gpk_geoarray* a, int32_t method, double* out, 
         }
     }
     GPK_LAUNCH("gpk_geodesic_combine", geodesic_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a->d, (const double*)seq_len, out_dev);
-    return copy_out(out, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }
 
 int32_t gpk_simplify(const gpk_geoarray* a, double epsilon, double* out_xy, int32_t* out_seq_offsets, int64_t* n_out_coords, int32_t out_space,
@@ -285,16 +285,21 @@ int32_t gpk_simplify(const gpk_geoarray* a, double epsilon, double* out_xy, int3
     seq_level(a->d, &seq_off, &n_seq);
     const int64_t nc = a->d.n_coords;
     const bool host = out_space != GPK_MEM_DEVICE;
-    const size_t offb = sizeof(int32_t) * (size_t)(n_seq + 1), xyb = sizeof(double2) * (size_t)(nc > 0 ? nc : 1);
+    const size_t offb = sizeof(int32_t) * (size_t)(n_seq + 1);
     const int64_t nb = (n_seq + 255) / 256;
-    GPK_TRY(workspace_aux(0).begin(2 * align256(offb) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + align256((size_t)nc + 8) +
-                                   align256(sizeof(int2) * (size_t)(nc + 1)) + (host ? align256(xyb) : 0) + 1024));
-    int32_t* sizes = (int32_t*)workspace_aux(0).take(offb);
-    int32_t* off_dev = host ? (int32_t*)workspace_aux(0).take(offb) : out_seq_offsets;
-    unsigned long long* btot = (unsigned long long*)workspace_aux(0).take(sizeof(unsigned long long) * (size_t)(nb + 2));
-    uint8_t* keep = (uint8_t*)workspace_aux(0).take((size_t)nc + 8);
-    int2* stack = (int2*)workspace_aux(0).take(sizeof(int2) * (size_t)(nc + 1));
-    double2* out_dev = host ? (double2*)workspace_aux(0).take(xyb) : (double2*)out_xy;
+    Scratch sc(workspace_aux(0));
+    int32_t *sizes, *off_dev;
+    unsigned long long* btot;
+    uint8_t* keep;
+    int2* stack;
+    double2* out_dev;
+    sc.add(sizes, (size_t)(n_seq + 1));
+    sc.stage(off_dev, out_seq_offsets, out_space, (size_t)(n_seq + 1));
+    sc.add(btot, (size_t)(nb + 2));
+    sc.add(keep, (size_t)nc + 8);
+    sc.add(stack, (size_t)(nc + 1));
+    sc.stage(out_dev, (double2*)out_xy, out_space, (size_t)nc);
+    GPK_TRY(sc.commit());
     if (n_seq == 0) {
         GPK_HIP(hipMemsetAsync(off_dev, 0, sizeof(int32_t), s));
         *n_out_coords = 0;

@@ -104,22 +104,19 @@ extern "C" int32_t gpk_line_clip(const gpk_geoarray* lines, const gpk_geoarray* 
     const int64_t n = n_rows, n1 = n > 0 ? n : 1;
 
     // ---- scratch: the per-pair counts, their scans, the scans' block totals, the totals record, staged row lists and out_src
-    const size_t i32 = align256(sizeof(int32_t) * (size_t)(n1 + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n1 + 255) / 256 + 2));
-    GPK_TRY(workspace().begin(7 * i32 + align256((size_t)n1) + 3 * tot + 256 + clip_staging_bytes(rows_space, out_src, src_space, i32) + 512));
-    Workspace& w = workspace();
-    int32_t* n_parts = (int32_t*)w.take(i32);
-    int32_t* n_coords = (int32_t*)w.take(i32);
-    int32_t* keep = (int32_t*)w.take(i32);
-    int32_t* part_start = (int32_t*)w.take(i32);
-    int32_t* coord_start = (int32_t*)w.take(i32);
-    int32_t* row_at = (int32_t*)w.take(i32);
-    uint8_t* valid = (uint8_t*)w.take((size_t)n1);
-    unsigned long long* tot_parts = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_coords = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_rows = (unsigned long long*)w.take(tot);
-    unsigned long long* totals_dev = (unsigned long long*)w.take(256);
+    const size_t words = (size_t)(n1 + 1), tot = (size_t)((n1 + 255) / 256 + 2);
+    Scratch sc(workspace());
+    int32_t *n_parts, *n_coords, *keep, *part_start, *coord_start, *row_at;
+    uint8_t* valid;
+    unsigned long long *tot_parts, *tot_coords, *tot_rows, *totals_dev;
     ClipLists in;
-    GPK_TRY(clip_stage_lists(w, line_rows, poly_rows, rows_space, out_src, src_space, n, i32, s, &in));
+    sc.add_n(words, n_parts, n_coords, keep, part_start, coord_start, row_at);
+    sc.add(valid, (size_t)n1);
+    sc.add_n(tot, tot_parts, tot_coords, tot_rows);
+    sc.add(totals_dev, 32);
+    clip_lists_plan(sc, line_rows, poly_rows, rows_space, out_src, src_space, n, words, &in);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
 
     // ---- 1, 2: count, scan, the one read-back
     const int G = lp::relation_group_size(lines->d, polys->d);

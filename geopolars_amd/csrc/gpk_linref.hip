@@ -185,14 +185,6 @@ dim3 tile_grid(int64_t n) {
             LAUNCH(32, KK);     \
     } while (0)
 
-// the row map of a host caller, uploaded into the workspace (carved by the caller's begin())
-int32_t upload_rows(const uint32_t* rows, int64_t n, hipStream_t s, const uint32_t** rows_dev) {
-    uint32_t* r = (uint32_t*)workspace().take(sizeof(uint32_t) * (size_t)n);
-    GPK_HIP(hipMemcpyAsync(r, rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    *rows_dev = r;
-    return GPK_OK;
-}
-
 }  // namespace
 }  // namespace gpk
 
@@ -212,15 +204,15 @@ int32_t gpk_closest_point_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, 
     const int64_t n = a->d.n_geoms;
     if (n == 0) return GPK_OK;
     const size_t xb = 2 * sizeof(double) * (size_t)n, sb = sizeof(int32_t) * (size_t)n;
-    const uint32_t* rows_dev = b_rows;
-    double* xy_dev = out_xy;
-    int32_t* seg_dev = out_seg;
-    if (out_space != GPK_MEM_DEVICE) {
-        GPK_TRY(workspace().begin(align256(xb) + (out_seg ? align256(sb) : 0) + (b_rows ? align256(sizeof(uint32_t) * (size_t)n) : 0) + 512));
-        xy_dev = (double*)workspace().take(xb);
-        if (out_seg) seg_dev = (int32_t*)workspace().take(sb);
-        if (b_rows) GPK_TRY(upload_rows(b_rows, n, s, &rows_dev));
-    }
+    Scratch sc(workspace());
+    const uint32_t* rows_dev;
+    double* xy_dev;
+    int32_t* seg_dev;
+    sc.stage(xy_dev, out_xy, out_space, 2 * (size_t)n);
+    sc.stage(seg_dev, out_seg, out_space, (size_t)n);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     const int G = distance_group_size(b->d);
     const dim3 grid = tile_grid(n), block(256);
 #define CP_LAUNCH(GG, KK) GPK_LAUNCH("gpk_closest_point", (closest_point_kernel<GG, KK>), grid, block, 0, s, a->d, b->d, rows_dev, xy_dev, seg_dev)
@@ -250,14 +242,13 @@ int32_t gpk_line_locate_point(const gpk_geoarray* pts, const gpk_geoarray* lines
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = pts->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const size_t ob = sizeof(double) * (size_t)n;
-    const uint32_t* rows_dev = line_rows;
-    double* out_dev = out;
-    if (out_space != GPK_MEM_DEVICE) {
-        GPK_TRY(workspace().begin(align256(ob) + (line_rows ? align256(sizeof(uint32_t) * (size_t)n) : 0) + 512));
-        out_dev = (double*)workspace().take(ob);
-        if (line_rows) GPK_TRY(upload_rows(line_rows, n, s, &rows_dev));
-    }
+    Scratch sc(workspace());
+    const uint32_t* rows_dev;
+    double* out_dev;
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    sc.stage_in(rows_dev, line_rows, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     const int G = distance_group_size(lines->d);
     const dim3 grid = tile_grid(n), block(256);
 #define LL_LAUNCH(GG, KK) \
@@ -267,7 +258,7 @@ int32_t gpk_line_locate_point(const gpk_geoarray* pts, const gpk_geoarray* lines
     else
         LINREF_BY_G(LL_LAUNCH, GPK_GEOM_MULTILINESTRING);
 #undef LL_LAUNCH
-    return copy_out(out, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }
 
 int32_t gpk_line_interpolate_point(const gpk_geoarray* lines, const double* distances, int64_t n_distances, int32_t normalized, double* out_xy,
@@ -284,26 +275,19 @@ int32_t gpk_line_interpolate_point(const gpk_geoarray* lines, const double* dist
     if (n == 0) return GPK_OK;
     const bool host = out_space != GPK_MEM_DEVICE;
     const bool broadcast = n_distances == 1 && n != 1;
-    const size_t xb = 2 * sizeof(double) * (size_t)n, vb = (size_t)n, db = sizeof(double) * (size_t)n;
+    const size_t xb = 2 * sizeof(double) * (size_t)n, vb = (size_t)n;
     // one value for every row: a host value travels as a kernel argument, a device value is read in place with stride 0
-    const double* dist_dev = distances;
-    double scalar = 0.0;
-    double* xy_dev = out_xy;
-    uint8_t* valid_dev = out_valid;
-    if (host) {
-        const bool by_value = n_distances == 1;
-        GPK_TRY(workspace().begin(align256(xb) + (out_valid ? align256(vb) : 0) + (by_value ? 0 : align256(db)) + 512));
-        xy_dev = (double*)workspace().take(xb);
-        if (out_valid) valid_dev = (uint8_t*)workspace().take(vb);
-        if (by_value) {
-            scalar = distances[0];
-            dist_dev = nullptr;
-        } else {
-            double* d = (double*)workspace().take(db);
-            GPK_HIP(hipMemcpyAsync(d, distances, db, hipMemcpyHostToDevice, s));
-            dist_dev = d;
-        }
-    }
+    const bool by_value = host && n_distances == 1;
+    const double scalar = by_value ? distances[0] : 0.0;
+    Scratch sc(workspace());
+    const double* dist_dev;
+    double* xy_dev;
+    uint8_t* valid_dev;
+    sc.stage(xy_dev, out_xy, out_space, 2 * (size_t)n);
+    sc.stage(valid_dev, out_valid, out_space, (size_t)n);
+    sc.stage_in(dist_dev, by_value ? nullptr : distances, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     const int64_t stride = broadcast ? 0 : 1;
     const int G = distance_group_size(lines->d);
     const dim3 grid = group_grid(n, G), block(256);  // (n > 0 here: the helper never gives an empty grid)

@@ -298,24 +298,23 @@ int32_t run(const gpk_geoarray* a, double* out_rect, double* out_centre, double*
     const int64_t n = d.n_geoms, nc = d.n_coords;
     if (n == 0) return GPK_OK;
     if (n > (int64_t)INT32_MAX - 1) return fail(GPK_ERR_INVALID_ARGUMENT, "minimum bounding shapes: more than 2^31 - 2 rows");
-    const bool host_out = out_space != GPK_MEM_DEVICE, point = d.type == GPK_GEOM_POINT;
+    const bool point = d.type == GPK_GEOM_POINT;
     const size_t rect_bytes = sizeof(double2) * 5 * (size_t)n, xy_bytes = sizeof(double2) * (size_t)n, r_bytes = sizeof(double) * (size_t)n;
-    const size_t list_bytes = sizeof(int32_t) * (size_t)(n + 1);
-    size_t need = align256(list_bytes) + 1024;
-    if (!point) need += hull_stage_bytes(n, nc);
-    if (host_out) need += (OP == OP_RECT ? align256(rect_bytes) : align256(xy_bytes) + align256(r_bytes)) + align256((size_t)n);
-    GPK_TRY(workspace().begin(need));
-    HullStage hs{nullptr, nullptr, nullptr};
-    if (!point) GPK_TRY(hull_stage(a, &hs, s));
-    int32_t* big = (int32_t*)workspace().take(list_bytes);
+    Scratch sc(workspace());
+    HullStage hs{};
+    if (!point) hull_stage_plan(sc, n, nc, &hs);
+    int32_t* big;
+    sc.add(big, (size_t)(n + 1));
     Out o{nullptr, nullptr, nullptr, nullptr};
     if (OP == OP_RECT) {
-        o.rect = host_out ? (double2*)workspace().take(rect_bytes) : (double2*)out_rect;
+        sc.stage(o.rect, (double2*)out_rect, out_space, 5 * (size_t)n);
     } else {
-        o.centre = out_centre ? (host_out ? (double2*)workspace().take(xy_bytes) : (double2*)out_centre) : nullptr;
-        o.radius = host_out ? (double*)workspace().take(r_bytes) : out_radius;
+        sc.stage(o.centre, (double2*)out_centre, out_space, (size_t)n);
+        sc.stage(o.radius, out_radius, out_space, (size_t)n);
     }
-    o.valid = out_valid ? (host_out ? (uint8_t*)workspace().take((size_t)n) : out_valid) : nullptr;
+    sc.stage(o.valid, out_valid, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    if (!point) GPK_TRY(hull_stage(a, hs, s));
     const char* name = OP == OP_RECT ? "gpk_minimum_rotated_rectangle" : "gpk_minimum_bounding_circle";
     const char* name_large = OP == OP_RECT ? "gpk_minimum_rotated_rectangle_large" : "gpk_minimum_bounding_circle_large";
     if (point) {

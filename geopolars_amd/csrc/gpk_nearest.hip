@@ -344,14 +344,16 @@ extern "C" int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray
     const NearPts pts{left->d.xy, left->d.validity, n};
 
     const int64_t nb = (n + 255) / 256;
-    const size_t i32n = align256(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t rc = workspace().begin(align256(sizeof(double) * (size_t)n) + 3 * i32n + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + 1024);
+    Scratch sc(workspace());
+    double* best_d;
+    uint32_t* best_r;
+    int32_t *cnt, *off;
+    unsigned long long* btot;
+    sc.add(best_d, (size_t)n);
+    sc.add_n((size_t)(n + 1), best_r, cnt, off);
+    sc.add(btot, (size_t)(nb + 2));
+    int32_t rc = sc.commit();
     if (rc != GPK_OK) return done(rc);
-    double* best_d = (double*)workspace().take(sizeof(double) * (size_t)n);
-    uint32_t* best_r = (uint32_t*)workspace().take(sizeof(uint32_t) * (size_t)(n + 1));
-    int32_t* cnt = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* off = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
 
     auto pass1 = [&]() -> int32_t {
         switch (right->d.type) {
@@ -384,14 +386,13 @@ extern "C" int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray
         return done(fail(GPK_ERR_CAPACITY, "nearest_join: %lld pairs but capacity %lld", (long long)total, (long long)pair_capacity));
     if (!want_pairs || total == 0) return done(GPK_OK);
 
-    uint32_t* pairs_dev = out_pairs;
-    double* dist_dev = out_dist;
-    if (host_out) {
-        rc = workspace_aux(0).begin(align256(sizeof(uint32_t) * 2 * (size_t)total) + (out_dist ? align256(sizeof(double) * (size_t)total) : 0) + 512);
-        if (rc != GPK_OK) return done(rc);
-        pairs_dev = (uint32_t*)workspace_aux(0).take(sizeof(uint32_t) * 2 * (size_t)total);
-        dist_dev = out_dist ? (double*)workspace_aux(0).take(sizeof(double) * (size_t)total) : nullptr;
-    }
+    Scratch sc_out(workspace_aux(0));
+    uint32_t* pairs_dev;
+    double* dist_dev;
+    sc_out.stage(pairs_dev, out_pairs, out_space, 2 * (size_t)total);
+    sc_out.stage(dist_dev, out_dist, out_space, (size_t)total);
+    rc = sc_out.commit();
+    if (rc != GPK_OK) return done(rc);
     auto pass2 = [&]() -> int32_t {
         switch (right->d.type) {
         case GPK_GEOM_POINT:
@@ -411,8 +412,7 @@ extern "C" int32_t gpk_nearest_join(const gpk_geoarray* left, const gpk_geoarray
     rc = pass2();
     if (rc != GPK_OK) return done(rc);
     if (host_out) {
-        rc = copy_out(out_pairs, out_space, pairs_dev, sizeof(uint32_t) * 2 * (size_t)total, s);
-        if (rc == GPK_OK && out_dist) rc = copy_out(out_dist, out_space, dist_dev, sizeof(double) * (size_t)total, s);
+        rc = sc_out.copy_back(s);
         if (rc != GPK_OK) return done(rc);
     } else {
         e = hipStreamSynchronize(s);  // (the call is synchronous, like gpk_spatial_join)

@@ -946,7 +946,7 @@ struct Temps {  // scratch of the build: carved from the thread's auxiliary aren
     template <typename T>
     int32_t alloc(T** out, size_t count) {
         const size_t bytes = sizeof(T) * (count ? count : 1);
-        void* q = gpk::workspace_aux(1).take(bytes);
+        void* q = gpk::ScratchEstimate::try_carve(gpk::workspace_aux(1), bytes);
         if (!q) {
             const auto t0 = std::chrono::steady_clock::now();
             hipError_t e = cached_malloc(&q, bytes);
@@ -1017,7 +1017,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
         // hipMalloc + a hipFree — 0.2 ms each on this runtime, a third of the whole build of a 1000-polygon right side)
         size_t est = (size_t)n_rings * 64 + (size_t)n_cells * 96 + (size_t)d.n_coords * 168 + (8u << 20);
         if (est > (size_t(256) << 20)) est = size_t(256) << 20;
-        (void)workspace_aux(1).begin(est);
+        ScratchEstimate::reserve(workspace_aux(1), est);
     }
     Temps t;
     // GPK_DEBUG_INDEX=1: wall time of every phase of the build (the stream is drained at each stamp)

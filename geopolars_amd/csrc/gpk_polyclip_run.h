@@ -222,32 +222,19 @@ int32_t polygon_clip_run(const RunNames& nm, bool mode_ok, const gpk_geoarray* a
     const int64_t n = n_rows, n1 = n > 0 ? n : 1;
 
     // ---- scratch of the first stage: per-pair counts, their scans, the scans' block totals, the totals record, staged lists
-    const size_t i32 = align256(sizeof(int32_t) * (size_t)(n1 + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n1 + 255) / 256 + 2));
-    GPK_TRY(workspace().begin(13 * i32 + 2 * align256((size_t)n1) + 6 * tot + 512 + clip_staging_bytes(rows_space, out_src, src_space, i32) + 512));
-    Workspace& w = workspace();
-    int32_t* n_arcs = (int32_t*)w.take(i32);
-    int32_t* n_acoords = (int32_t*)w.take(i32);
-    int32_t* arc_start = (int32_t*)w.take(i32);
-    int32_t* acoord_start = (int32_t*)w.take(i32);
-    int32_t* n_parts = (int32_t*)w.take(i32);
-    int32_t* n_rings = (int32_t*)w.take(i32);
-    int32_t* n_coords = (int32_t*)w.take(i32);
-    int32_t* keep = (int32_t*)w.take(i32);
-    int32_t* part_start = (int32_t*)w.take(i32);
-    int32_t* ring_start = (int32_t*)w.take(i32);
-    int32_t* coord_start = (int32_t*)w.take(i32);
-    int32_t* row_at = (int32_t*)w.take(i32);
-    uint8_t* valid = (uint8_t*)w.take((size_t)n1);
-    uint8_t* status = (uint8_t*)w.take((size_t)n1);
-    unsigned long long* tot_arcs = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_acoords = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_parts = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_rings = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_coords = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_rows = (unsigned long long*)w.take(tot);
-    unsigned long long* totals_dev = (unsigned long long*)w.take(512);
+    const size_t words = (size_t)(n1 + 1), tot = (size_t)((n1 + 255) / 256 + 2);
+    Scratch sc(workspace());
+    int32_t *n_arcs, *n_acoords, *arc_start, *acoord_start, *n_parts, *n_rings, *n_coords, *keep, *part_start, *ring_start, *coord_start, *row_at;
+    uint8_t *valid, *status;
+    unsigned long long *tot_arcs, *tot_acoords, *tot_parts, *tot_rings, *tot_coords, *tot_rows, *totals_dev;
     ClipLists in;
-    GPK_TRY(clip_stage_lists(w, a_rows, b_rows, rows_space, out_src, src_space, n, i32, s, &in));
+    sc.add_n(words, n_arcs, n_acoords, arc_start, acoord_start, n_parts, n_rings, n_coords, keep, part_start, ring_start, coord_start, row_at);
+    sc.add_n((size_t)n1, valid, status);
+    sc.add_n(tot, tot_arcs, tot_acoords, tot_parts, tot_rings, tot_coords, tot_rows);
+    sc.add(totals_dev, 64);
+    clip_lists_plan(sc, a_rows, b_rows, rows_space, out_src, src_space, n, words, &in);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
 
     // ---- 1, 2: count the arcs, scan, the first wait
     const int G = lp::relation_group_size(a->d, b->d);
@@ -265,20 +252,18 @@ int32_t polygon_clip_run(const RunNames& nm, bool mode_ok, const gpk_geoarray* a
     const int64_t total_arcs = (int64_t)totals[0], total_acoords = (int64_t)totals[1];
 
     // ---- 3, 4, 5: the arc scratch (a second arena: the first one's carves stay valid), fill, stitch, scan, the second wait
-    const size_t arcs_b = align256(sizeof(pc::Arc) * (size_t)(total_arcs + 1)), axy_b = align256(sizeof(double2) * (size_t)(total_acoords + 1)),
-                 link_b = align256(sizeof(int32_t) * (size_t)(total_arcs + 1));
-    Workspace& w2 = workspace_aux(0);
-    GPK_TRY(w2.begin(arcs_b + axy_b + 4 * link_b + 256));
-    pc::Arc* arcs = (pc::Arc*)w2.take(arcs_b);
-    double2* axy = (double2*)w2.take(axy_b);
-    int32_t* next = (int32_t*)w2.take(link_b);
-    int32_t* ring_first = (int32_t*)w2.take(link_b);
-    int32_t* order = (int32_t*)w2.take(link_b);
-    int32_t* info = (int32_t*)w2.take(link_b);
+    Scratch sc2(workspace_aux(0));
+    pc::Arc* arcs;
+    double2* axy;
+    int32_t *next, *ring_first, *order, *info;
+    sc2.add(arcs, (size_t)(total_arcs + 1));
+    sc2.add(axy, (size_t)(total_acoords + 1));
+    sc2.add_n((size_t)(total_arcs + 1), next, ring_first, order, info);
+    GPK_TRY(sc2.commit());
     unsigned long long sizes[4] = {0, 0, 0, 0};  // parts, rings, coordinates, rows that stay
     if (n > 0) {
         // (a record the fill pass should leave unwritten has length 0, which the stitcher refuses)
-        GPK_HIP(hipMemsetAsync(arcs, 0, arcs_b, s));
+        GPK_HIP(hipMemsetAsync(arcs, 0, align256(sizeof(pc::Arc) * (size_t)(total_arcs + 1)), s));
         if (total_arcs > 0)
             GPK_LAUNCH_BY_G(nm.fill, (polygon_clip_fill_kernel<lp::LP_G_SMALL, Rule>), (polygon_clip_fill_kernel<lp::LP_G_LARGE, Rule>), a->d, b->d, in.a_rows,
                             in.b_rows, n, (int)mode, (const int32_t*)arc_start, (const int32_t*)acoord_start, arcs, axy);

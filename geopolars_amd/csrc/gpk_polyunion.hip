@@ -74,16 +74,14 @@ extern "C" int32_t gpk_union_all_pairs(const int32_t* group, const uint32_t* row
     if (n == 0) return GPK_OK;
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    const size_t i32 = align256(sizeof(int32_t) * (size_t)(n + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n + 255) / 256 + 2));
-    GPK_TRY(workspace().begin(4 * i32 + 2 * tot + 512 + 512));
-    Workspace& w = workspace();
-    int32_t* opens = (int32_t*)w.take(i32);
-    int32_t* stays = (int32_t*)w.take(i32);
-    int32_t* pair_at = (int32_t*)w.take(i32);
-    int32_t* next_at = (int32_t*)w.take(i32);
-    unsigned long long* tot_pairs = (unsigned long long*)w.take(tot);
-    unsigned long long* tot_next = (unsigned long long*)w.take(tot);
-    unsigned long long* totals_dev = (unsigned long long*)w.take(512);
+    const size_t tot = (size_t)((n + 255) / 256 + 2);
+    Scratch sc(workspace());
+    int32_t *opens, *stays, *pair_at, *next_at;
+    unsigned long long *tot_pairs, *tot_next, *totals_dev;
+    sc.add_n((size_t)(n + 1), opens, stays, pair_at, next_at);
+    sc.add_n(tot, tot_pairs, tot_next);
+    sc.add(totals_dev, 64);
+    GPK_TRY(sc.commit());
     const dim3 grid((unsigned)((n + 255) / 256));
     const int64_t at = (n + 255) / 256;
     GPK_LAUNCH("gpk_union_all_roles", union_all_roles_kernel, grid, dim3(256), 0, s, group, n, opens, stays);

@@ -668,20 +668,18 @@ static int32_t distance_pairs(const gpk_geoarray* a, const gpk_geoarray* b, cons
                     (long long)b->d.n_geoms);
     const int64_t n = a->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const size_t ob = sizeof(double) * (size_t)n, lb = sizeof(uint32_t) * (size_t)n;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    GPK_TRY(workspace().begin((host_out ? align256(ob) : 0) + (b_rows && host_out ? align256(lb) : 0) + align256(lb) + 768));
-    double* out_dev = host_out ? (double*)workspace().take(ob) : out;
-    const uint32_t* rows_dev = b_rows;
-    if (b_rows && host_out) {
-        uint32_t* r = (uint32_t*)workspace().take(lb);
-        GPK_HIP(hipMemcpyAsync(r, b_rows, lb, hipMemcpyHostToDevice, s));
-        rows_dev = r;
-    }
-    uint32_t* large_rows = (uint32_t*)workspace().take(lb);  // rows for the work-group schedule, then their number
-    uint32_t* n_large = (uint32_t*)workspace().take(sizeof(uint32_t));
+    Scratch sc(workspace());
+    double* out_dev;
+    const uint32_t* rows_dev;
+    uint32_t *large_rows, *n_large;  // rows for the work-group schedule, then their number
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    sc.add(large_rows, (size_t)n);
+    sc.add(n_large, 1);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     GPK_TRY(pair_distance_dev(a->d, b->d, rows_dev, n, out_dev, large_rows, n_large, s));
-    return copy_out(out, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }
 
 }  // namespace gpk
@@ -742,14 +740,12 @@ int32_t gpk_distance_rowmap(const gpk_geoarray* a, const gpk_geoarray* b, const 
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = a->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const size_t ob = sizeof(double) * (size_t)n;
-    double* out_dev = out;
-    if (out_space != GPK_MEM_DEVICE) {
-        GPK_TRY(workspace().begin(align256(ob) + 512));
-        out_dev = (double*)workspace().take(ob);
-    }
+    Scratch sc(workspace());
+    double* out_dev;
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
     GPK_TRY(distance_rowmap_dev(a, b, map, out_dev, s));
-    return copy_out(out, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }
 
 int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double* out,
@@ -769,25 +765,19 @@ int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const
                     (long long)b->d.n_geoms);
     const int64_t n = pts->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const size_t ob = sizeof(double) * (size_t)n;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    const uint32_t* rows_dev = b_rows;
-    double* out_dev = out;
-    if (host_out) {
-        GPK_TRY(workspace().begin(align256(ob) + (b_rows ? align256(sizeof(uint32_t) * (size_t)n) : 0) + 512));
-        out_dev = (double*)workspace().take(ob);
-        if (b_rows) {
-            uint32_t* r = (uint32_t*)workspace().take(sizeof(uint32_t) * (size_t)n);
-            GPK_HIP(hipMemcpyAsync(r, b_rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            rows_dev = r;
-        }
-    }
+    Scratch sc(workspace());
+    const uint32_t* rows_dev;
+    double* out_dev;
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     // many rows per linestring: order the rows by target once (the row map), stage each linestring in LDS per chunk
     if (b_rows && other->d.type == GPK_GEOM_LINESTRING && other->d.n_geoms > 0 && n >= 8 * other->d.n_geoms) {
         gpk_rowmap* map = nullptr;
         GPK_TRY(rowmap_build_dev(other, rows_dev, n, s, &map));
         int32_t rc = distance_rowmap_dev(pts, other, map, out_dev, s);
-        if (rc == GPK_OK) rc = copy_out(out, out_space, out_dev, ob, s);
+        if (rc == GPK_OK) rc = sc.copy_back(s);
         (void)hipStreamSynchronize(s);  // the map's buffers are released below
         gpk_rowmap_free(map);
         return rc;
@@ -816,7 +806,7 @@ int32_t gpk_distance_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const
     }
 #undef DIST_BY_G
 #undef DIST_LAUNCH
-    return copy_out(out, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }
 
 int32_t gpk_predicate_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, int32_t predicate,
@@ -831,18 +821,13 @@ int32_t gpk_predicate_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, cons
                     (long long)b->d.n_geoms);
     const int64_t n = a->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const bool host_out = out_space != GPK_MEM_DEVICE;
-    const uint32_t* rows_dev = b_rows;
-    uint8_t* out_dev = out;
-    if (host_out) {
-        GPK_TRY(workspace().begin(align256((size_t)n) + (b_rows ? align256(sizeof(uint32_t) * (size_t)n) : 0) + 512));
-        out_dev = (uint8_t*)workspace().take((size_t)n);
-        if (b_rows) {
-            uint32_t* r = (uint32_t*)workspace().take(sizeof(uint32_t) * (size_t)n);
-            GPK_HIP(hipMemcpyAsync(r, b_rows, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            rows_dev = r;
-        }
-    }
+    Scratch sc(workspace());
+    const uint32_t* rows_dev;
+    uint8_t* out_dev;
+    sc.stage(out_dev, out, out_space, (size_t)n);
+    sc.stage_in(rows_dev, b_rows, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     const int ta = a->d.type, tb = b->d.type;
     const dim3 block(256);
     const dim3 flat((unsigned)((n + 255) / 256));
@@ -895,7 +880,7 @@ int32_t gpk_predicate_rowwise(const gpk_geoarray* a, const gpk_geoarray* b, cons
         // combinations the reference's dispatch table maps to `false` (spatial_index.rs:136)
         GPK_LAUNCH("gpk_fill_u8", fill_u8_kernel, flat, block, 0, s, out_dev, n, (uint8_t)0);
     }
-    return copy_out(out, out_space, out_dev, (size_t)n, s);
+    return sc.copy_back(s);
 }
 
 }  // extern "C"

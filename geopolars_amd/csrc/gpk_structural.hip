@@ -202,13 +202,12 @@ static inline dim3 rows_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256
 template <typename T, typename LAUNCH>
 static int32_t map_out(T* out, int64_t n, int32_t out_space, hipStream_t s, LAUNCH&& launch) {
     if (n == 0) return GPK_OK;
-    T* dev = out;
-    if (out_space != GPK_MEM_DEVICE) {
-        GPK_TRY(workspace_aux(0).begin(sizeof(T) * (size_t)n + 256));
-        dev = (T*)workspace_aux(0).take(sizeof(T) * (size_t)n);
-    }
+    Scratch sc(workspace_aux(0));
+    T* dev;
+    sc.stage(dev, out, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
     GPK_TRY(launch(dev));
-    return copy_out(out, out_space, dev, sizeof(T) * (size_t)n, s);
+    return sc.copy_back(s);
 }
 
 }  // namespace gpk
@@ -225,12 +224,15 @@ int32_t gpk_envelope(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, 
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = a->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const bool host = out_space != GPK_MEM_DEVICE;
-    const size_t bb = sizeof(double4) * (size_t)n, ob = sizeof(double2) * 5 * (size_t)n;
-    GPK_TRY(workspace_aux(0).begin(align256(bb) + (host ? align256(ob) + align256((size_t)n) : 0) + 512));
-    double4* box = (double4*)workspace_aux(0).take(bb);
-    double2* out_dev = host ? (double2*)workspace_aux(0).take(ob) : (double2*)out_xy;
-    uint8_t* valid_dev = out_valid ? (host ? (uint8_t*)workspace_aux(0).take((size_t)n) : out_valid) : nullptr;
+    const size_t ob = sizeof(double2) * 5 * (size_t)n;
+    Scratch sc(workspace_aux(0));
+    double4* box;
+    double2* out_dev;
+    uint8_t* valid_dev;
+    sc.add(box, (size_t)n);
+    sc.stage(out_dev, (double2*)out_xy, out_space, 5 * (size_t)n);
+    sc.stage(valid_dev, out_valid, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
     GPK_TRY(gpk_bounds(a, (double*)box, GPK_MEM_DEVICE, stream));
     GPK_LAUNCH("gpk_envelope", envelope_kernel, rows_grid(n), dim3(256), 0, s, (const double4*)box, a->d.validity, n, out_dev, valid_dev);
     if (out_valid) GPK_TRY(copy_out(out_valid, out_space, valid_dev, (size_t)n, s));
@@ -245,13 +247,17 @@ int32_t gpk_exterior(const gpk_geoarray* a, double* out_xy, int32_t* out_geom_of
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = a->d.n_geoms, nc = a->d.n_coords;
     const bool host = out_space != GPK_MEM_DEVICE;
-    const size_t offb = sizeof(int32_t) * (size_t)(n + 1), xyb = sizeof(double2) * (size_t)(nc > 0 ? nc : 1);
+    const size_t offb = sizeof(int32_t) * (size_t)(n + 1);
     const int64_t nb = (n + 255) / 256;
-    GPK_TRY(workspace_aux(0).begin(2 * align256(offb) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) + (host ? align256(xyb) : 0) + 512));
-    int32_t* sizes = (int32_t*)workspace_aux(0).take(offb);
-    int32_t* off_dev = host ? (int32_t*)workspace_aux(0).take(offb) : out_geom_offsets;
-    unsigned long long* btot = (unsigned long long*)workspace_aux(0).take(sizeof(unsigned long long) * (size_t)(nb + 2));
-    double2* out_dev = host ? (double2*)workspace_aux(0).take(xyb) : (double2*)out_xy;
+    Scratch sc(workspace_aux(0));
+    int32_t *sizes, *off_dev;
+    unsigned long long* btot;
+    double2* out_dev;
+    sc.add(sizes, (size_t)(n + 1));
+    sc.stage(off_dev, out_geom_offsets, out_space, (size_t)(n + 1));
+    sc.add(btot, (size_t)(nb + 2));
+    sc.stage(out_dev, (double2*)out_xy, out_space, (size_t)nc);
+    GPK_TRY(sc.commit());
     if (n == 0) {
         GPK_HIP(hipMemsetAsync(off_dev, 0, sizeof(int32_t), s));
         *n_out_coords = 0;
@@ -325,14 +331,9 @@ int32_t gpk_explode(const gpk_geoarray* a, int32_t* out_parent, int32_t parent_s
     const bool need_valid = d.validity != nullptr && members > 0;
     int32_t* parent_dev = nullptr;
     const bool host_parent = out_parent && parent_space != GPK_MEM_DEVICE;
-    if (out_parent && members > 0) {
-        parent_dev = out_parent;
-        if (host_parent) {
-            const int32_t rc = workspace_aux(0).begin(sizeof(int32_t) * (size_t)members + 256);
-            if (rc != GPK_OK) return cleanup(rc);
-            parent_dev = (int32_t*)workspace_aux(0).take(sizeof(int32_t) * (size_t)members);
-        }
-    }
+    Scratch sc(workspace_aux(0));
+    sc.stage(parent_dev, members > 0 ? out_parent : nullptr, parent_space, (size_t)members);
+    if (const int32_t rc = sc.commit(); rc != GPK_OK) return cleanup(rc);
     if (need_valid) {  // the members' bitmap is owned by the result
         const size_t vb = (((size_t)members + 31) / 32) * 4;
         void* v = nullptr;
@@ -401,18 +402,13 @@ int32_t gpk_point_xy(const gpk_geoarray* a, double* out_x, double* out_y, int32_
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = a->d.n_geoms;
     if (n == 0) return GPK_OK;
-    const bool host = out_space != GPK_MEM_DEVICE;
-    const size_t b = sizeof(double) * (size_t)n;
-    double *xd = out_x, *yd = out_y;
-    if (host) {
-        GPK_TRY(workspace_aux(0).begin(2 * align256(b) + 256));
-        if (out_x) xd = (double*)workspace_aux(0).take(b);
-        if (out_y) yd = (double*)workspace_aux(0).take(b);
-    }
+    Scratch sc(workspace_aux(0));
+    double *xd, *yd;
+    sc.stage(xd, out_x, out_space, (size_t)n);
+    sc.stage(yd, out_y, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
     GPK_LAUNCH("gpk_point_xy", point_xy_kernel, rows_grid(n), dim3(256), 0, s, a->d, xd, yd);
-    if (out_x) GPK_TRY(copy_out(out_x, out_space, xd, b, s));
-    if (out_y) GPK_TRY(copy_out(out_y, out_space, yd, b, s));
-    return GPK_OK;
+    return sc.copy_back(s);
 }
 
 int32_t gpk_affine_about_origin(const gpk_geoarray* a, int32_t kind, double p0, double p1, int32_t origin, double ox, double oy, double* out_xy,
@@ -435,11 +431,13 @@ int32_t gpk_affine_about_origin(const gpk_geoarray* a, int32_t kind, double p0, 
         k0 = tan(p0 * rad);
         k1 = tan(p1 * rad);
     }
-    const size_t mb = sizeof(double) * 6 * (size_t)n, ob = sizeof(double4) * (size_t)n;
-    GPK_TRY(workspace_aux(1).begin(align256(mb) + align256(ob) + align256((size_t)n) + 512));
-    double* mats = (double*)workspace_aux(1).take(mb);
-    void* org = workspace_aux(1).take(ob);  // centroids (double2) or boxes (double4)
-    uint8_t* cvalid = (uint8_t*)workspace_aux(1).take((size_t)n);
+    Scratch sc(workspace_aux(1));
+    double* mats;
+    double4* org;  // centroids (double2) or boxes (double4)
+    uint8_t* cvalid;
+    sc.add(mats, 6 * (size_t)n);
+    sc.add_n((size_t)n, org, cvalid);
+    GPK_TRY(sc.commit());
     if (origin == GPK_ORIGIN_CENTROID) GPK_TRY(gpk_centroid(a, (double*)org, cvalid, GPK_MEM_DEVICE, stream));
     if (origin == GPK_ORIGIN_CENTER) GPK_TRY(gpk_bounds(a, (double*)org, GPK_MEM_DEVICE, stream));
     GPK_LAUNCH("gpk_origin_matrices", origin_matrices_kernel, rows_grid(n), dim3(256), 0, s, n, (int)kind, k0, k1, (int)origin, (const double2*)org,

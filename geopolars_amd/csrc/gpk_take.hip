@@ -12,36 +12,6 @@
 
 namespace gpk {
 
-// ---- staging: inputs / outputs in the caller's memory space ------------------------------------------------
-struct Stage {  // device views of caller buffers; host buffers are copied through the thread's workspace
-    hipStream_t s;
-    int32_t space;
-    template <typename T>
-    int32_t in(const T* p, size_t count, const T** out) {
-        *out = nullptr;
-        if (!p || count == 0) return GPK_OK;
-        if (space == GPK_MEM_DEVICE) {
-            *out = p;
-            return GPK_OK;
-        }
-        T* d = (T*)workspace().take(sizeof(T) * count);
-        GPK_HIP(hipMemcpyAsync(d, p, sizeof(T) * count, hipMemcpyHostToDevice, s));
-        *out = d;
-        return GPK_OK;
-    }
-    template <typename T>
-    T* out(T* p, size_t count) {
-        if (!p) return nullptr;
-        return space == GPK_MEM_DEVICE ? p : (T*)workspace().take(sizeof(T) * (count ? count : 1));
-    }
-    template <typename T>
-    int32_t back(T* user, const T* dev, size_t count) {
-        if (!user || space == GPK_MEM_DEVICE || count == 0) return GPK_OK;
-        return copy_out(user, space, dev, sizeof(T) * count, s);
-    }
-};
-static inline size_t staged(int32_t space, size_t bytes) { return space == GPK_MEM_DEVICE ? 0 : align256(bytes); }
-
 // ---- join indices ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void left_rows_kernel(const uint32_t* __restrict__ counts, int64_t n, int32_t* __restrict__ rows) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -166,19 +136,22 @@ int32_t gpk_join_indices(const uint32_t* counts, const uint32_t* pairs, int64_t 
     if (capacity < 0 || (capacity > 0 && (!out_l || !out_r))) return fail(GPK_ERR_INVALID_ARGUMENT, "capacity without output buffers");
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    Stage st{s, space};
+    Scratch sc(workspace());
+    const uint32_t* c;
+    const uint2* p;
+    long long *dl, *dr;
     *n_rows = 0;
     if (join_type == GPK_JOIN_INNER) {
         *n_rows = n_pairs;
         if (capacity == 0 || n_pairs == 0) return GPK_OK;
         if (n_pairs > capacity) return fail(GPK_ERR_CAPACITY, "join_indices: %lld rows but capacity %lld", (long long)n_pairs, (long long)capacity);
-        GPK_TRY(workspace().begin(staged(space, 8 * (size_t)n_pairs) * 3 + 1024));
-        const uint2* p;
-        GPK_TRY(st.in((const uint2*)pairs, (size_t)n_pairs, &p));
-        long long *dl = st.out((long long*)out_l, (size_t)n_pairs), *dr = st.out((long long*)out_r, (size_t)n_pairs);
+        sc.stage_in(p, (const uint2*)pairs, space, (size_t)n_pairs);
+        sc.stage(dl, (long long*)out_l, space, (size_t)n_pairs);
+        sc.stage(dr, (long long*)out_r, space, (size_t)n_pairs);
+        GPK_TRY(sc.commit());
+        GPK_TRY(sc.upload(s));
         GPK_LAUNCH("gpk_join_inner_indices", inner_indices_kernel, grid1(n_pairs), dim3(256), 0, s, p, n_pairs, left_row_base, dl, dr);
-        GPK_TRY(st.back((long long*)out_l, dl, (size_t)n_pairs));
-        GPK_TRY(st.back((long long*)out_r, dr, (size_t)n_pairs));
+        GPK_TRY(sc.copy_back(s));
         GPK_HIP(hipStreamSynchronize(s));
         return GPK_OK;
     }
@@ -186,18 +159,16 @@ int32_t gpk_join_indices(const uint32_t* counts, const uint32_t* pairs, int64_t 
     if (n_left >= 0x7FFFFFFFLL || n_pairs + n_left >= 0x7FFFFFFFLL)
         return fail(GPK_ERR_CAPACITY, "join_indices: more than 2^31 rows; assemble per row shard");
     const int64_t nb = (n_left + 255) / 256;
-    const size_t i32n = align256(sizeof(int32_t) * (size_t)(n_left + 1));
-    GPK_TRY(workspace().begin(4 * i32n + align256(8 * (size_t)(nb + 2)) + staged(space, 4 * (size_t)n_left) + staged(space, 8 * (size_t)n_pairs) +
-                              2 * staged(space, 8 * (size_t)capacity) + 1024));
-    const uint32_t* c;
-    const uint2* p;
-    GPK_TRY(st.in(counts, (size_t)n_left, &c));
-    GPK_TRY(st.in((const uint2*)pairs, (size_t)n_pairs, &p));
-    int32_t* rows = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_left + 1));
-    int32_t* row_off = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_left + 1));
-    int32_t* ci32 = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_left + 1));
-    int32_t* pair_off = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_left + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(8 * (size_t)(nb + 2));
+    int32_t *rows, *row_off, *ci32, *pair_off;
+    unsigned long long* btot;
+    sc.stage_in(c, counts, space, (size_t)n_left);
+    sc.stage_in(p, n_pairs ? (const uint2*)pairs : nullptr, space, (size_t)n_pairs);  // (an empty input is none)
+    sc.add_n((size_t)(n_left + 1), rows, row_off, ci32, pair_off);
+    sc.add(btot, (size_t)(nb + 2));
+    sc.stage(dl, (long long*)out_l, space, (size_t)capacity);  // (the row count is known only after the scans; it is at most the capacity)
+    sc.stage(dr, (long long*)out_r, space, (size_t)capacity);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     GPK_LAUNCH("gpk_join_left_rows", left_rows_kernel, grid1(n_left), dim3(256), 0, s, c, n_left, rows);
     GPK_TRY(exclusive_scan_i32(rows, n_left, row_off, nullptr, btot, s));
     GPK_LAUNCH("gpk_join_counts_i32", u32_to_i32_kernel, grid1(n_left), dim3(256), 0, s, c, ci32, n_left);
@@ -211,11 +182,10 @@ int32_t gpk_join_indices(const uint32_t* counts, const uint32_t* pairs, int64_t 
     *n_rows = total;
     if (capacity == 0) return GPK_OK;
     if ((int64_t)total > capacity) return fail(GPK_ERR_CAPACITY, "join_indices: %d rows but capacity %lld", total, (long long)capacity);
-    long long *dl = st.out((long long*)out_l, (size_t)total), *dr = st.out((long long*)out_r, (size_t)total);
     GPK_LAUNCH("gpk_join_left_indices", left_indices_kernel, grid1(n_left), dim3(256), 0, s, c, (const int32_t*)row_off,
                (const int32_t*)pair_off, p, n_left, dl, dr);
-    GPK_TRY(st.back((long long*)out_l, dl, (size_t)total));
-    GPK_TRY(st.back((long long*)out_r, dr, (size_t)total));
+    GPK_TRY(copy_out(out_l, space, dl, 8 * (size_t)total, s));
+    GPK_TRY(copy_out(out_r, space, dr, 8 * (size_t)total, s));
     GPK_HIP(hipStreamSynchronize(s));
     return GPK_OK;
 }
@@ -228,24 +198,25 @@ int32_t gpk_take_fixed(const void* values, int32_t elem_bits, const uint8_t* val
     GPK_TRY(require_device());
     if (n_idx == 0) return GPK_OK;
     hipStream_t s = (hipStream_t)stream;
-    Stage st{s, space};
+    Scratch sc(workspace());
     const size_t in_bytes = elem_bits == 1 ? (size_t)(n_values + 7) / 8 : (size_t)n_values * (size_t)(elem_bits / 8);
     const size_t out_bytes = elem_bits == 1 ? (size_t)(n_idx + 7) / 8 : (size_t)n_idx * (size_t)(elem_bits / 8);
     const size_t vbytes = (size_t)(n_values + 7) / 8, obytes = (size_t)(n_idx + 7) / 8;
-    GPK_TRY(workspace().begin(staged(space, in_bytes) + staged(space, vbytes) + staged(space, 8 * (size_t)n_idx) + staged(space, out_bytes) +
-                              staged(space, obytes) + 3 * align256((size_t)n_idx) + 2 * align256(obytes) + 1024));
     const uint8_t *v, *val;
     const long long* ix;
-    GPK_TRY(st.in((const uint8_t*)values, in_bytes, &v));
-    GPK_TRY(st.in(validity, vbytes, &val));
-    GPK_TRY(st.in((const long long*)idx, (size_t)n_idx, &ix));
-    uint8_t* ov = st.out((uint8_t*)out_values, out_bytes);
-    uint8_t* ob = st.out(out_validity, obytes);
-    uint8_t* flags = out_validity ? (uint8_t*)workspace().take((size_t)n_idx) : nullptr;
+    uint8_t *ov, *ob, *flags, *bytes;  // flags, bytes: a byte per output row, packed into ob / ov afterwards
+    sc.stage_in(v, in_bytes ? (const uint8_t*)values : nullptr, space, in_bytes);  // (an empty input is none)
+    sc.stage_in(val, vbytes ? validity : nullptr, space, vbytes);
+    sc.stage_in(ix, (const long long*)idx, space, (size_t)n_idx);
+    sc.stage(ov, (uint8_t*)out_values, space, out_bytes);
+    sc.stage(ob, out_validity, space, obytes);
+    sc.add_if(out_validity != nullptr, flags, (size_t)n_idx);
+    sc.add_if(elem_bits == 1 && out_values, bytes, (size_t)n_idx);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     const dim3 g = grid1(n_idx);
     switch (elem_bits) {
     case 1: {
-        uint8_t* bytes = out_values ? (uint8_t*)workspace().take((size_t)n_idx) : nullptr;
         GPK_LAUNCH("gpk_take_bits", take_bits_kernel, g, dim3(256), 0, s, v, val, n_values, ix, n_idx, bytes, flags);
         if (bytes) GPK_LAUNCH("gpk_take_pack", pack_bits_kernel, grid1((n_idx + 7) / 8), dim3(256), 0, s, (const uint8_t*)bytes, n_idx, ov);
         break;
@@ -265,8 +236,7 @@ int32_t gpk_take_fixed(const void* values, int32_t elem_bits, const uint8_t* val
         GPK_LAUNCH("gpk_take_fixed128", take_fixed_kernel<uint4>, g, dim3(256), 0, s, (const uint4*)v, val, n_values, ix, n_idx, (uint4*)ov, flags);
     }
     if (flags) GPK_LAUNCH("gpk_take_pack", pack_bits_kernel, grid1((n_idx + 7) / 8), dim3(256), 0, s, (const uint8_t*)flags, n_idx, ob);
-    GPK_TRY(st.back((uint8_t*)out_values, ov, out_bytes));
-    GPK_TRY(st.back(out_validity, ob, obytes));
+    GPK_TRY(sc.copy_back(s));
     GPK_HIP(hipStreamSynchronize(s));
     return GPK_OK;
 }
@@ -279,7 +249,7 @@ int32_t gpk_take_binary(const uint8_t* values, const int32_t* offsets, const uin
     if (capacity < 0 || (capacity > 0 && !out_values)) return fail(GPK_ERR_INVALID_ARGUMENT, "capacity without out_values");
     GPK_TRY(require_device());
     hipStream_t s = (hipStream_t)stream;
-    Stage st{s, space};
+    Scratch sc(workspace());
     *n_bytes = 0;
     if (n_idx >= 0x7FFFFFFFLL) return fail(GPK_ERR_CAPACITY, "take_binary: more than 2^31 rows");
     const size_t vbytes = (size_t)(n_values + 7) / 8, obytes = (size_t)(n_idx + 7) / 8;
@@ -295,21 +265,24 @@ int32_t gpk_take_binary(const uint8_t* values, const int32_t* offsets, const uin
         in_bytes = last;
     }
     const int64_t nb = (n_idx + 255) / 256;
-    GPK_TRY(workspace().begin(staged(space, (size_t)in_bytes) + staged(space, 4 * (size_t)(n_values + 1)) + staged(space, vbytes) +
-                              staged(space, 8 * (size_t)n_idx) + staged(space, (size_t)capacity) + staged(space, obytes) +
-                              2 * align256(4 * (size_t)(n_idx + 1)) + align256(8 * (size_t)(nb + 2)) + align256((size_t)n_idx) + align256(obytes) + 2048));
     const uint8_t *v, *val;
     const int32_t* off;
     const long long* ix;
-    GPK_TRY(st.in(values, (size_t)in_bytes, &v));
-    GPK_TRY(st.in(offsets, (size_t)(n_values + 1), &off));
-    GPK_TRY(st.in(validity, vbytes, &val));
-    GPK_TRY(st.in((const long long*)idx, (size_t)n_idx, &ix));
-    int32_t* sizes = (int32_t*)workspace().take(4 * (size_t)(n_idx + 1));
-    int32_t* ooff = (space == GPK_MEM_DEVICE && out_offsets) ? out_offsets : (int32_t*)workspace().take(4 * (size_t)(n_idx + 1));
-    unsigned long long* btot = (unsigned long long*)workspace().take(8 * (size_t)(nb + 2));
-    uint8_t* flags = out_validity ? (uint8_t*)workspace().take((size_t)(n_idx ? n_idx : 1)) : nullptr;
-    uint8_t* ob = st.out(out_validity, obytes);
+    int32_t *sizes, *ooff;
+    unsigned long long* btot;
+    uint8_t *flags, *ob, *ov;
+    sc.stage_in(v, in_bytes ? values : nullptr, space, (size_t)in_bytes);  // (an empty input is none)
+    sc.stage_in(off, offsets, space, (size_t)(n_values + 1));
+    sc.stage_in(val, vbytes ? validity : nullptr, space, vbytes);
+    sc.stage_in(ix, n_idx ? (const long long*)idx : nullptr, space, (size_t)n_idx);
+    sc.add(sizes, (size_t)(n_idx + 1));
+    sc.stage_or_add(ooff, out_offsets, space, (size_t)(n_idx + 1));
+    sc.add(btot, (size_t)(nb + 2));
+    sc.add_if(out_validity != nullptr, flags, (size_t)n_idx);
+    sc.stage(ob, out_validity, space, obytes);
+    sc.stage(ov, out_values, space, (size_t)capacity);  // (the byte count is known only after the scan; it is at most the capacity)
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     unsigned long long total = 0;
     if (n_idx > 0) {
         GPK_LAUNCH("gpk_take_binary_sizes", take_binary_sizes_kernel, grid1(n_idx), dim3(256), 0, s, off, val, n_values, ix, n_idx, sizes, flags);
@@ -323,16 +296,15 @@ int32_t gpk_take_binary(const uint8_t* values, const int32_t* offsets, const uin
     if (total > 0x7FFFFFFFull) return fail(GPK_ERR_CAPACITY, "take_binary: %llu bytes do not fit i32 offsets; gather row slices", total);
     if (flags && n_idx > 0) GPK_LAUNCH("gpk_take_pack", pack_bits_kernel, grid1((n_idx + 7) / 8), dim3(256), 0, s, (const uint8_t*)flags, n_idx, ob);
     if (out_offsets && space != GPK_MEM_DEVICE) GPK_TRY(copy_out(out_offsets, space, ooff, 4 * (size_t)(n_idx + 1), s));
-    GPK_TRY(st.back(out_validity, ob, obytes));
+    if (out_validity) GPK_TRY(copy_out(out_validity, space, ob, obytes, s));
     if (!out_values) {
         GPK_HIP(hipStreamSynchronize(s));
         return GPK_OK;  // size query
     }
     if ((int64_t)total > capacity) return fail(GPK_ERR_CAPACITY, "take_binary: %llu bytes but capacity %lld", total, (long long)capacity);
-    uint8_t* ov = st.out(out_values, (size_t)total);
     if (total > 0)
         GPK_LAUNCH("gpk_take_binary_copy", take_binary_copy_kernel, grid1(n_idx * TAKE_GS), dim3(256), 0, s, v, off, ix, n_idx, (const int32_t*)ooff, ov);
-    GPK_TRY(st.back(out_values, ov, (size_t)total));
+    GPK_TRY(copy_out(out_values, space, ov, (size_t)total, s));
     GPK_HIP(hipStreamSynchronize(s));
     return GPK_OK;
 }

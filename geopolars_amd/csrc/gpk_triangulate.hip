@@ -200,18 +200,21 @@ extern "C" int32_t gpk_triangulate(const gpk_geoarray* a, uint32_t* out_index, i
     const int G = tri_group_size(total_share, n);
     const int slice = G == tri::TRI_G_LARGE ? tri::TRI_SLICE_LARGE : tri::TRI_SLICE_SMALL;
     const bool any_big = total_share > slice, any_huge = total_share > tri::TRI_LDS_NODES;  // (else no row can be listed)
-    const size_t i32 = align256(sizeof(int32_t) * (size_t)(n + 1)), tot = align256(sizeof(unsigned long long) * (size_t)((n + 255) / 256 + 2));
-    const size_t tri_bytes = align256(sizeof(uint32_t) * 3 * (size_t)total_share);
-    const size_t node_bytes = any_huge ? align256((size_t)tri::NODE_BYTES * (size_t)total_share) : 0;
-    GPK_TRY(workspace().begin(4 * i32 + align256((size_t)n) + tot + tri_bytes + node_bytes + 1024));
-    Workspace& w = workspace();
-    int32_t* counts = (int32_t*)w.take(i32);
-    int32_t* offsets_dev = host_out ? (int32_t*)w.take(i32) : out_tri_offsets;
-    const Lists lists{(int32_t*)w.take(i32), (int32_t*)w.take(i32)};
-    uint8_t* status_dev = (host_out || !out_status) ? (uint8_t*)w.take((size_t)n) : out_status;
-    unsigned long long* block_tot = (unsigned long long*)w.take(tot);
-    uint32_t* tris = (uint32_t*)w.take(tri_bytes);
-    char* node_scratch = any_huge ? (char*)w.take(node_bytes) : nullptr;
+    Scratch sc(workspace());
+    int32_t *counts, *offsets_dev;
+    Lists lists;
+    uint8_t* status_dev;
+    unsigned long long* block_tot;
+    uint32_t* tris;
+    char* node_scratch;
+    sc.add(counts, (size_t)(n + 1));
+    sc.stage(offsets_dev, out_tri_offsets, out_space, (size_t)(n + 1));
+    sc.add_n((size_t)(n + 1), lists.big, lists.huge);
+    sc.stage_or_add(status_dev, out_status, out_space, (size_t)n);
+    sc.add(block_tot, (size_t)((n + 255) / 256 + 2));
+    sc.add(tris, 3 * (size_t)total_share);
+    sc.add_if(any_huge, node_scratch, (size_t)tri::NODE_BYTES * (size_t)total_share);
+    GPK_TRY(sc.commit());
     GPK_HIP(hipMemsetAsync(lists.big, 0, sizeof(int32_t), s));
     GPK_HIP(hipMemsetAsync(lists.huge, 0, sizeof(int32_t), s));
 
@@ -246,14 +249,11 @@ extern "C" int32_t gpk_triangulate(const gpk_geoarray* a, uint32_t* out_index, i
     if ((int64_t)total > tri_capacity)
         return fail(GPK_ERR_CAPACITY, "triangulate: %lld triangles, capacity %lld", (long long)total, (long long)tri_capacity);
     if (total == 0) return GPK_OK;
-    uint32_t* index_dev = out_index;
-    const size_t index_bytes = sizeof(uint32_t) * 3 * (size_t)total;
-    if (host_out) {
-        GPK_TRY(workspace_aux(0).begin(align256(index_bytes) + 256));
-        index_dev = (uint32_t*)workspace_aux(0).take(index_bytes);
-    }
+    Scratch sc_index(workspace_aux(0));
+    uint32_t* index_dev;
+    sc_index.stage(index_dev, out_index, out_space, 3 * (size_t)total);
+    GPK_TRY(sc_index.commit());
     GPK_LAUNCH("gpk_triangulate_gather", triangulate_gather_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, d, n, (const uint32_t*)tris,
                (const int32_t*)offsets_dev, index_dev);
-    if (host_out) return copy_out(out_index, out_space, index_dev, index_bytes, s);
-    return GPK_OK;
+    return sc_index.copy_back(s);
 }

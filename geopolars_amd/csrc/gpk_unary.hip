@@ -1203,12 +1203,12 @@ static inline dim3 grid_for(int64_t n, int block = 256) {
     return dim3((unsigned)(b > 0 ? b : 1));
 }
 
-// common prologue: stats + output staging in the workspace
+// common prologue: stats + output staging in the workspace (one Scratch, planned and committed here: the operators add no carves)
 struct UnaryCtx {
     double* stats = nullptr;
     double* long_part = nullptr;  // chunk partials of the long sequences (seq_stats_long_kernel)
-    void* out_dev = nullptr;
-    void* out2_dev = nullptr;
+    uint8_t* out_dev = nullptr;
+    uint8_t* out2_dev = nullptr;
     int64_t n_seq = 0;
     int32_t* flag = nullptr;  // one device word for the operator (centroid: "some ring has zero area")
     const gpk_seq_classes* classes = nullptr;
@@ -1221,25 +1221,22 @@ static int32_t unary_begin(const gpk_geoarray* a, size_t out_bytes, size_t out2_
     const int32_t* so;
     seq_view(a->d, &so, &c->n_seq);
     if (a->d.type == GPK_GEOM_POINT) c->n_seq = 0;
-    const size_t stats_bytes = sizeof(double) * ST_COUNT * (size_t)c->n_seq;
-    const bool stage = out_space != GPK_MEM_DEVICE;
-    size_t part_bytes = 0;
+    size_t n_chunks = 0;
     if (c->n_seq > 0) {
         const gpk_seq_classes* cl;
         GPK_TRY(seq_classes_of(a, (hipStream_t) nullptr, &cl));
-        part_bytes = sizeof(double) * 12 * (size_t)cl->n_chunks;
+        n_chunks = (size_t)cl->n_chunks;
         c->classes = cl;
     }
-    const size_t strip_bytes = c->classes && c->classes->strips_ok ? sizeof(double) * 8 * (size_t)ring_stream_strips(a->d.n_coords) : 0;
-    GPK_TRY(workspace().begin(align256(stats_bytes) + align256(part_bytes) + align256(strip_bytes) +
-                              (stage ? align256(out_bytes) + align256(out2_bytes) : 0) + 1024));
-    c->stats = (double*)workspace().take(stats_bytes ? stats_bytes : 8);
-    c->long_part = part_bytes ? (double*)workspace().take(part_bytes) : nullptr;
-    c->strip_part = strip_bytes ? (double*)workspace().take(strip_bytes) : nullptr;
-    c->out_dev = stage ? workspace().take(out_bytes ? out_bytes : 8) : out;
-    c->out2_dev = out2 ? (stage ? workspace().take(out2_bytes ? out2_bytes : 8) : out2) : nullptr;
-    c->flag = (int32_t*)workspace().take(64);
-    return GPK_OK;
+    const size_t n_strips = c->classes && c->classes->strips_ok ? (size_t)ring_stream_strips(a->d.n_coords) : 0;
+    Scratch sc(workspace());
+    sc.add(c->stats, ST_COUNT * (size_t)c->n_seq);
+    sc.add_if(n_chunks > 0, c->long_part, 12 * n_chunks);
+    sc.add_if(n_strips > 0, c->strip_part, 8 * n_strips);
+    sc.stage(c->out_dev, (uint8_t*)out, out_space, out_bytes);
+    sc.stage(c->out2_dev, (uint8_t*)out2, out_space, out2_bytes);
+    sc.add(c->flag, 16);
+    return sc.commit();
 }
 
 __global__ void stats_to_bbox_kernel(const double* __restrict__ stats, const int32_t* __restrict__ seq_off, int64_t n_seq,
@@ -1259,10 +1256,11 @@ int32_t ring_bboxes(const gpk_geoarray* a, double4* out_dev, hipStream_t s) {
     if (n_seq == 0) return GPK_OK;
     const gpk_seq_classes* cl;
     GPK_TRY(seq_classes_of(a, s, &cl));
-    const size_t part_bytes = sizeof(double) * 12 * (size_t)cl->n_chunks;
-    GPK_TRY(workspace().begin(align256(sizeof(double) * ST_COUNT * (size_t)n_seq) + align256(part_bytes) + 1024));
-    double* stats = (double*)workspace().take(sizeof(double) * ST_COUNT * (size_t)n_seq);
-    double* long_part = part_bytes ? (double*)workspace().take(part_bytes) : nullptr;
+    Scratch sc(workspace());
+    double *stats, *long_part;
+    sc.add(stats, ST_COUNT * (size_t)n_seq);
+    sc.add_if(cl->n_chunks > 0, long_part, 12 * (size_t)cl->n_chunks);
+    GPK_TRY(sc.commit());
     GPK_TRY(launch_seq_stats<M_BBOX>(a, stats, long_part, s, "gpk_seq_bbox"));
     GPK_LAUNCH("gpk_stats_to_bbox", stats_to_bbox_kernel, grid_for(n_seq), dim3(256), 0, s, stats, seq_off, n_seq, out_dev);
     return GPK_OK;
@@ -1432,17 +1430,15 @@ int32_t gpk_affine_transform(const gpk_geoarray* a, const double m[6], double* o
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = a->d.n_coords;
     if (n == 0) return GPK_OK;
-    const size_t ob = sizeof(double) * 2 * (size_t)n;
-    void* out_dev = out_xy;
-    if (out_space != GPK_MEM_DEVICE) {
-        GPK_TRY(workspace().begin(ob + 512));
-        out_dev = workspace().take(ob);
-    }
+    Scratch sc(workspace());
+    double* out_dev;
+    sc.stage(out_dev, out_xy, out_space, 2 * (size_t)n);
+    GPK_TRY(sc.commit());
     int64_t blocks = (n + 255) / 256;
     const int64_t cap = (int64_t)cu_count() * 8;
     if (blocks > cap) blocks = cap;
     GPK_LAUNCH("gpk_affine", affine_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a->d.xy, n, m[0], m[1], m[2], m[3], m[4], m[5], (double2*)out_dev);
-    return copy_out(out_xy, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }
 
 int32_t gpk_affine_transform_rows(const gpk_geoarray* a, const double* matrices, double* out_xy, int32_t out_space, void* stream) {
@@ -1457,18 +1453,13 @@ int32_t gpk::affine_rows_impl(const gpk_geoarray* a, const double* matrices, int
     GPK_TRY(require_device());
     const int64_t n = a->d.n_coords, ng = a->d.n_geoms;
     if (n == 0 || ng == 0) return GPK_OK;
-    const size_t ob = sizeof(double) * 2 * (size_t)n, mb = sizeof(double) * 6 * (size_t)ng;
-    void* out_dev = out_xy;
-    const double* mats_dev = matrices;
-    if (out_space != GPK_MEM_DEVICE || mat_space != GPK_MEM_DEVICE) {
-        GPK_TRY(workspace().begin(align256(ob) + align256(mb) + 512));
-        if (out_space != GPK_MEM_DEVICE) out_dev = workspace().take(ob);
-        if (mat_space != GPK_MEM_DEVICE) {
-            double* m = (double*)workspace().take(mb);
-            GPK_HIP(hipMemcpyAsync(m, matrices, mb, hipMemcpyHostToDevice, s));
-            mats_dev = m;
-        }
-    }
+    Scratch sc(workspace());
+    double* out_dev;
+    const double* mats_dev;
+    sc.stage(out_dev, out_xy, out_space, 2 * (size_t)n);
+    sc.stage_in(mats_dev, matrices, mat_space, 6 * (size_t)ng);
+    GPK_TRY(sc.commit());
+    GPK_TRY(sc.upload(s));
     const int G = pick_group(n, ng);
     const int64_t per_block = 256 / G;
     int64_t blocks = (ng + per_block - 1) / per_block;
@@ -1482,5 +1473,5 @@ int32_t gpk::affine_rows_impl(const gpk_geoarray* a, const double* matrices, int
     case 32: GPK_LAUNCH("gpk_affine_rows", affine_rows_kernel<32>, grid, block, 0, s, a->d, mats_dev, (double2*)out_dev); break;
     default: GPK_LAUNCH("gpk_affine_rows", affine_rows_kernel<64>, grid, block, 0, s, a->d, mats_dev, (double2*)out_dev); break;
     }
-    return copy_out(out_xy, out_space, out_dev, ob, s);
+    return sc.copy_back(s);
 }

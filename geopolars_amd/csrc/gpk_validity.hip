@@ -198,13 +198,15 @@ int32_t run(const gpk_geoarray* a, uint8_t* out_code, int32_t* out_where, int32_
     const bool host_out = out_space != GPK_MEM_DEVICE;
     const bool want_where = POLY && out_where;
     const bool want_parent = POLY && g.n_rings > 1;  // (a column of one ring has no member of two)
-    const size_t list_bytes = sizeof(int32_t) * (size_t)(n + 1), parent_bytes = want_parent ? sizeof(int32_t) * (size_t)g.n_rings : 0;
     const size_t where_bytes = sizeof(int32_t) * (size_t)n;
-    GPK_TRY(workspace().begin(align256(list_bytes) + align256(parent_bytes) + (host_out ? align256((size_t)n) + align256(where_bytes) : 0) + 1024));
-    int32_t* big = (int32_t*)workspace().take(list_bytes);
-    int32_t* parent = want_parent ? (int32_t*)workspace().take(parent_bytes) : nullptr;
-    uint8_t* code_dev = host_out ? (uint8_t*)workspace().take((size_t)n) : out_code;
-    int32_t* where_dev = want_where ? (host_out ? (int32_t*)workspace().take(where_bytes) : out_where) : nullptr;
+    Scratch sc(workspace());
+    int32_t *big, *parent, *where_dev;
+    uint8_t* code_dev;
+    sc.add(big, (size_t)(n + 1));
+    sc.add_if(want_parent, parent, (size_t)g.n_rings);
+    sc.stage(code_dev, out_code, out_space, (size_t)n);
+    sc.stage(where_dev, want_where ? out_where : nullptr, out_space, (size_t)n);
+    GPK_TRY(sc.commit());
     GPK_HIP(hipMemsetAsync(big, 0, sizeof(int32_t), s));
     const int G = val::validity_group_size(g);
     const dim3 grid = group_grid(n, G);

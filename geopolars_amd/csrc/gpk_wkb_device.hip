@@ -467,11 +467,11 @@ extern "C" int32_t gpk_geoarray_from_wkb(const uint8_t* wkb_values, const int32_
     {
         size_t est = (size_t)n_rows * 64 + (1u << 20);
         if (est > (size_t(256) << 20)) est = size_t(256) << 20;
-        (void)workspace_aux(1).begin(est);
+        ScratchEstimate::reserve(workspace_aux(1), est);
     }
     auto dalloc = [&](void** p, size_t bytes, bool temporary) -> int32_t {
         if (temporary) {
-            *p = workspace_aux(1).take(bytes ? bytes : 8);
+            *p = ScratchEstimate::try_carve(workspace_aux(1), bytes ? bytes : 8);
             if (*p) return GPK_OK;
         }
         // (the decoded buffers come from the library's block cache like index tables do: a dataframe pipeline decodes and drops

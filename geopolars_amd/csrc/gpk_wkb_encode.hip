@@ -231,15 +231,16 @@ extern "C" int32_t gpk_geoarray_to_wkb(const gpk_geoarray* a, int32_t* out_offse
     const bool host_out = out_space != GPK_MEM_DEVICE;
     const int64_t nb = (n + 255) / 256;
     const int64_t n_seq_enc = d.type == GPK_GEOM_LINESTRING ? n : d.n_rings;
-    size_t need = 2 * align256(sizeof(int32_t) * (size_t)(n + 1)) + align256(sizeof(unsigned long long) * (size_t)(nb + 2)) +
-                  align256(sizeof(int32_t) * (size_t)(n_seq_enc + 2)) + 1024;
-    if (host_out && out_values) need += align256((size_t)capacity);
-    GPK_TRY(workspace().begin(need));
-    int32_t* sizes = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1));
-    int32_t* off_dev = (host_out || !out_offsets) ? (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n + 1)) : out_offsets;
-    unsigned long long* btot = (unsigned long long*)workspace().take(sizeof(unsigned long long) * (size_t)(nb + 2));
-    uint8_t* val_dev = out_values ? (host_out ? (uint8_t*)workspace().take((size_t)capacity) : out_values) : nullptr;
-    int32_t* seq_dst = (int32_t*)workspace().take(sizeof(int32_t) * (size_t)(n_seq_enc + 2));
+    Scratch sc(workspace());
+    int32_t *sizes, *off_dev, *seq_dst;
+    unsigned long long* btot;
+    uint8_t* val_dev;
+    sc.add(sizes, (size_t)(n + 1));
+    sc.stage_or_add(off_dev, out_offsets, out_space, (size_t)(n + 1));
+    sc.add(btot, (size_t)(nb + 2));
+    sc.stage(val_dev, out_values, out_space, (size_t)capacity);
+    sc.add(seq_dst, (size_t)(n_seq_enc + 2));
+    GPK_TRY(sc.commit());
 
     int32_t total = 0;
     if (n > 0) {
