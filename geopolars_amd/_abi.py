@@ -234,6 +234,10 @@ _PROTOS = {
     "gpk_take_binary": (C.c_int32, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP, C.c_int32, _VP]),
     "gpk_geoarray_take": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int32, _VP, C.POINTER(_VP)]),
     "gpk_geoarray_filter": (C.c_int32, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.POINTER(_VP), C.POINTER(C.c_int64)]),
+    "gpk_segmentize": (C.c_int32, [_VP, C.c_double, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
+    "gpk_remove_repeated_points": (C.c_int32, [_VP, C.c_double, _VP, C.POINTER(_VP)]),
+    "gpk_reverse": (C.c_int32, [_VP, _VP, C.POINTER(_VP)]),
+    "gpk_orient_polygons": (C.c_int32, [_VP, C.c_int32, _VP, C.POINTER(_VP)]),
     "gpk_comm_unique_id":(C.c_int32, [C.POINTER(C.c_uint8)]),
     "gpk_comm_init": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(_VP)]),
     "gpk_comm_free": (C.c_int32, [_VP]),

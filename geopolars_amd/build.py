@@ -58,6 +58,7 @@ SOURCES = [
     "gpk_wkb_encode.hip",
     "gpk_take.hip",
     "gpk_geotake.hip",
+    "gpk_seqedit.hip",
     "gpk_structural.hip",
     "gpk_lineal_ops.hip",
     "gpk_comm.hip",

@@ -444,7 +444,7 @@ class DeviceGeoArray:
         return DeviceGeoArray(out.value, chunks[0].geom_type, total, -1), np.array(list(bases), dtype=np.int64)
 
     def _owned_result(self, handle: C.c_void_p, stream: int) -> "DeviceGeoArray":
-        """a column gpk_geoarray_take / gpk_geoarray_filter returned, its sizes filled in from the size query"""
+        """a column gpk_geoarray_take / gpk_geoarray_filter or a sequence edit returned, its sizes filled in from the size query"""
         out = DeviceGeoArray(handle.value, self.geom_type, 0, -1)
         sizes = (C.c_int64 * 4)()
         _abi.check(_abi.lib().gpk_geoarray_download(out.handle, sizes, None, None, None, None, stream))
@@ -486,6 +486,51 @@ class DeviceGeoArray:
             ptr, space = (mask.data_ptr() if mask.numel() else None), (_abi.MEM_DEVICE if mask.is_cuda else _abi.MEM_HOST)
         h, kept = C.c_void_p(), C.c_int64(0)
         _abi.check(_abi.lib().gpk_geoarray_filter(self.handle, ptr, 8, space, stream, C.byref(h), C.byref(kept)))  # (numpy and torch bools are a byte a row)
+        return self._owned_result(h, stream)
+
+    # ---- edits of the coordinate sequences (gpk_seqedit.hip): new device-resident columns of the same type and rows ----------------
+    def segmentize(self, max_segment_length, stream: int = 0) -> "DeviceGeoArray":
+        """Every segment longer than the bound split into equal pieces (gpk_segmentize).  max_segment_length: a float, or one f64 per
+        row as a numpy array or a torch tensor (used where it is); a per-row value that is NaN or <= 0 leaves its row unchanged."""
+        h = C.c_void_p()
+        if isinstance(max_segment_length, (int, float, np.floating, np.integer)) and not isinstance(max_segment_length, bool):
+            rc = _abi.lib().gpk_segmentize(self.handle, float(max_segment_length), None, _abi.MEM_HOST, stream, C.byref(h))
+        else:
+            m = max_segment_length
+            if isinstance(m, np.ndarray) or not hasattr(m, "data_ptr"):
+                m = np.ascontiguousarray(m, dtype=np.float64)
+                n, ptr, space = m.size if m.ndim == 1 else -1, m.ctypes.data, _abi.MEM_HOST
+            else:
+                import torch
+
+                if m.dtype != torch.float64:
+                    raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"segmentize: a float64 tensor of bounds (found {m.dtype})")
+                m = m.contiguous()
+                n, ptr, space = (int(m.numel()) if m.dim() == 1 else -1), m.data_ptr(), (_abi.MEM_DEVICE if m.is_cuda else _abi.MEM_HOST)
+            if n != self.n_geoms:
+                raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"segmentize: a 1-D array of {self.n_geoms} bounds, one per row")
+            if n == 0:
+                ptr = np.zeros(1).ctypes.data  # (never read: a column without rows)
+            rc = _abi.lib().gpk_segmentize(self.handle, 0.0, ptr, space, stream, C.byref(h))
+        _abi.check(rc)
+        return self._owned_result(h, stream)
+
+    def remove_repeated_points(self, tolerance: float = 0.0, stream: int = 0) -> "DeviceGeoArray":
+        """Consecutive equal coordinates of a sequence dropped (gpk_remove_repeated_points; only tolerance == 0)."""
+        h = C.c_void_p()
+        _abi.check(_abi.lib().gpk_remove_repeated_points(self.handle, float(tolerance), stream, C.byref(h)))
+        return self._owned_result(h, stream)
+
+    def reverse(self, stream: int = 0) -> "DeviceGeoArray":
+        """Every linestring and ring in reverse coordinate order (gpk_reverse)."""
+        h = C.c_void_p()
+        _abi.check(_abi.lib().gpk_reverse(self.handle, stream, C.byref(h)))
+        return self._owned_result(h, stream)
+
+    def orient_polygons(self, exterior_cw: bool = False, stream: int = 0) -> "DeviceGeoArray":
+        """Shells counter-clockwise and holes clockwise, or the opposite with exterior_cw (gpk_orient_polygons)."""
+        h = C.c_void_p()
+        _abi.check(_abi.lib().gpk_orient_polygons(self.handle, int(exterior_cw), stream, C.byref(h)))
         return self._owned_result(h, stream)
 
     def nbytes(self) -> int:

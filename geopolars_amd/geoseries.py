@@ -698,6 +698,31 @@ class GeoSeries:
                 _abi.GPK_ERR_INVALID_ARGUMENT, f"GeoSeries[{key!r}]: one row is not a series: index with a slice, a bool mask or an integer array")
         return self.filter(k) if k.dtype == np.bool_ else self.take(k)
 
+    # ---- edits of the coordinate sequences (gpk_seqedit.hip) ---------------------------------------------
+    def segmentize(self, max_segment_length) -> "GeoSeries":
+        """Every segment longer than `max_segment_length` split into ceil(len / max) equal pieces (gpk_segmentize; GeoPandas'
+        segmentize, geo's Densify), as a device-resident series of the same type.  A scalar > 0, or one value per row (a row whose
+        value is NaN or <= 0 stays as it is).  New coordinates are p + (q - p) * (j / n); the original ones are copied bit for bit."""
+        m = segmentize_args("segmentize", self, max_segment_length)
+        return GeoSeries(None, name=self.name, device=self.device().segmentize(m))
+
+    def remove_repeated_points(self, tolerance: float = 0.0) -> "GeoSeries":
+        """Consecutive equal coordinates of every linestring and ring dropped (gpk_remove_repeated_points).  Only tolerance == 0."""
+        if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)) or not float(tolerance) == 0.0:
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"remove_repeated_points: only tolerance == 0 is implemented (found {tolerance!r})")
+        return GeoSeries(None, name=self.name, device=self.device().remove_repeated_points(0.0))
+
+    def reverse(self) -> "GeoSeries":
+        """Every linestring and ring in reverse coordinate order (gpk_reverse); points are unchanged."""
+        return GeoSeries(None, name=self.name, device=self.device().reverse())
+
+    def orient_polygons(self, exterior_cw: bool = False) -> "GeoSeries":
+        """Shells counter-clockwise and holes clockwise (RFC 7946), or the opposite with `exterior_cw` (gpk_orient_polygons): the
+        exact turn at every ring's lexicographically smallest coordinate decides.  Other geometry types are copied."""
+        if not isinstance(exterior_cw, (bool, np.bool_)):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"orient_polygons: `exterior_cw` must be a bool (found {exterior_cw!r})")
+        return GeoSeries(None, name=self.name, device=self.device().orient_polygons(bool(exterior_cw)))
+
     # ---- polygon x polygon union and the grouped union (gpk_polyunion.hip) ---------------------------
     def polygon_union(self, other: "GeoSeries", other_rows=None, return_status: bool = False):
         """The area every row's polygon or other[other_rows[i]] covers (gpk_polygon_union), as a MULTIPOLYGON series: neighbours that
@@ -1299,6 +1324,21 @@ def filter_args(op: str, a: GeoSeries, mask) -> np.ndarray:
     if len(m) != len(a):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {len(m)} mask entries for {len(a)} rows")
     return np.ascontiguousarray(m)
+
+
+def segmentize_args(op: str, a: GeoSeries, max_segment_length):
+    """the checks of segmentize before any device call: a real scalar > 0 (returned as a float), or a 1-D real array with one entry per
+    row (returned as float64; its values are not looked at: NaN or <= 0 leaves a row unchanged)"""
+    m = np.asarray(max_segment_length)
+    if m.dtype.kind not in "iuf":
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: `max_segment_length` must be a number or an array of numbers (found {m.dtype})")
+    if m.ndim == 0:
+        if not float(m) > 0.0:
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: `max_segment_length` must be > 0 (found {float(m)})")
+        return float(m)
+    if m.ndim != 1 or len(m) != len(a):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {m.shape} bounds for {len(a)} rows: one value per row")
+    return np.ascontiguousarray(m, dtype=np.float64)
 
 
 def polygon_clip_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:

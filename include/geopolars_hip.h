@@ -1136,6 +1136,51 @@ int32_t gpk_geoarray_take(const gpk_geoarray* a, const int64_t* idx, int64_t n_i
  * two bitmaps first. */
 int32_t gpk_geoarray_filter(const gpk_geoarray* a, const uint8_t* mask, int32_t mask_bits, int32_t mask_space, void* stream, gpk_geoarray** out, int64_t* n_kept);
 
+/* ---- edits of coordinate sequences (gpk_seqedit.hip, the rule: csrc/gpk_seqedit.h) ------------------------------------------------------
+ * Four operations that rewrite the vertices of a column on the device.  Common to all four:
+ *   - Every geometry type is accepted.  *out is a callee-owned column of the same type and the same number of rows; it does not view a
+ *     and is freed with gpk_geoarray_free; a may be freed first.
+ *   - Every offsets level above the innermost one is copied unchanged; only the innermost offsets and the coordinates are rewritten.
+ *   - Null rows stay null (their children are edited like any others), and the result has a validity bitmap exactly when a has one.
+ *   - Empty rows, parts without rings and sequences without coordinates keep their (empty) slots.
+ *   - A SEQUENCE is a LINESTRING row, a member of a MULTILINESTRING, a ring of a POLYGON or MULTIPOLYGON, or a single coordinate of a
+ *     POINT or MULTIPOINT column: point columns pass through every operation as a bit-for-bit copy.
+ *   - Coordinates that are not computed are moved as 16 bytes: NaN payloads and signed zeros survive.
+ *   - Refusals come before any device work and leave *out untouched: a NULL a, a NULL out, and the argument rules below.
+ *   - A result whose coordinates do not fit i32 offsets returns GPK_ERR_INVALID_ARGUMENT: found after the count, before anything is
+ *     allocated, *out untouched.
+ *   - segmentize and remove_repeated_points wait once, for the coordinate total; reverse and orient_polygons do not wait at all.
+ *     Everything else is stream-ordered. */
+/* segmentize (GeoSeries.segmentize, geo's Densify): a segment p -> q of a sequence is split into n equal pieces.  With dx = qx - px,
+ * dy = qy - py, len = sqrt(dx*dx + dy*dy): n = 1 if !(len > m) or len is not finite, otherwise n = min(ceil(len / m), 2^31).  The new
+ * coordinates are (px + dx * t, py + dy * t), t = (double)j / (double)n, for j = 1 .. n - 1: exactly these operations in this order,
+ * no contraction; the division is j / n, not j * (1 / n) and not a walked sum — the library's own definition (geo and GEOS differ from
+ * it, and from each other, in the last bit).  p and q themselves are copied bit for bit, so closed rings stay closed.
+ * m is max_segment_length when per_row == NULL, else per_row[row]: one f64 per row of a, in per_row_space (GPK_MEM_HOST or
+ * GPK_MEM_DEVICE; max_segment_length is then ignored).  A scalar m that is NaN or <= 0 is refused; a per-row value that is NaN or <= 0
+ * leaves that row unchanged (the array is not read back to check it).  The piece counts are summed in 64 bits: one segment with
+ * len / m = 1e10 is a clean GPK_ERR_INVALID_ARGUMENT, not a wrap. */
+int32_t gpk_segmentize(const gpk_geoarray* a, double max_segment_length, const double* per_row, int32_t per_row_space, void* stream, gpk_geoarray** out);
+/* remove_repeated_points (geo's RemoveRepeatedPoints): coordinate c of a sequence is kept iff it is the sequence's first or
+ * !(x[c] == x[c-1] && y[c] == y[c-1]).  The comparison is numeric: -0.0 == 0.0, and a NaN coordinate is never a repeat.  Repeats
+ * across a sequence boundary are not removed.  A ring that collapses keeps what is left: [A, A, A, A] -> [A].  tolerance must be
+ * exactly 0.0: any other value, NaN included, is refused (a positive tolerance is sequential along the sequence and its end rule
+ * differs between GEOS versions; the argument exists so that the signature need not change). */
+int32_t gpk_remove_repeated_points(const gpk_geoarray* a, double tolerance, void* stream, gpk_geoarray** out);
+/* reverse: every sequence's coordinates in reverse order, out[lo + k] = in[hi - 1 - k]; the order of sequences, parts and rows is
+ * unchanged, and so are POINT and MULTIPOINT columns. */
+int32_t gpk_reverse(const gpk_geoarray* a, void* stream, gpk_geoarray** out);
+/* orient_polygons (geo's Orient): POLYGON and MULTIPOLYGON columns; the first ring of every polygon is the shell, the others are holes.
+ * The turn of a ring is taken at its lexicographically smallest coordinate v — smallest x, then smallest y, the lowest index among
+ * equals; the closing coordinate is not a candidate — between u, the nearest coordinate before v (cyclically) that differs from v, and
+ * w, the nearest after v that differs from v: s is the EXACT sign of orient(u, v, w) (filter + expansion, not the f64 shoelace sum),
+ * s > 0 counter-clockwise.  A ring is reversed, as by gpk_reverse, iff s != 0 and its direction is not the one wanted: shells CCW and
+ * holes CW by default, the opposite with exterior_cw = 1; any other value is refused.  Copied unchanged: rings with s == 0 (a spike at
+ * v, or fewer than three distinct coordinates), rings with a non-finite coordinate, rings of fewer than 4 coordinates.  For every ring
+ * gpk_validity accepts, s is the ring's orientation (v is a convex corner of a simple ring).  The result is identical at any placement
+ * and on every schedule.  Every other geometry type gets a bit-for-bit copy. */
+int32_t gpk_orient_polygons(const gpk_geoarray* a, int32_t exterior_cw, void* stream, gpk_geoarray** out);
+
 /* ---- chunked columns ------------------------------------------------------------------------------------ */
 /* K chunks of one column held by this process -> ONE array (a new handle, gpk_geoarray_free): Arrow's rechunk — the reference turns
  * every Series into a single chunk before it looks at it (py-geopolars/src/ffi.rs:56,73,93).  Device-resident: the chunks' buffers
