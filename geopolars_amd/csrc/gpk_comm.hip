@@ -139,7 +139,11 @@ namespace gpk {
 // The collectives keep RCCL's signatures, so gpk_allgatherv_* run unchanged over it — header all-gather, the agreement, the grouped
 // broadcasts, placement, rebase and validity repack — with W ranks that really are apart in time (each on its own thread and stream).
 // Every call is a rendezvous: the rank makes what it queued visible (a stream sync), posts its pointer, all ranks meet, each copies what
-// it is owed (device to device), all ranks meet again.
+// it is owed (device to device, ON ITS OWN STREAM, and waits for it), all ranks meet again.  (A plain hipMemcpy between device buffers
+// goes to the null stream and need not be complete when it returns; the callers' streams may be non-blocking ones, which the null
+// stream does not order against: the header read that follows on the caller's stream could then see the previous exchange's rows, the
+// ranks disagree on which pieces are empty, issue different numbers of broadcasts, and one of them waits at a rendezvous for ever.
+// And a peer may reuse its send buffer as soon as the second meeting is over.)
 struct MockWorld {
     int W = 0;
     std::mutex mu;
@@ -170,7 +174,8 @@ static ncclResult_t mock_all_gather(const void* send, void* recv, size_t count, 
     bool ok = hipStreamSynchronize(s) == hipSuccess;
     m->w->ptr[m->rank] = send;
     m->w->meet();
-    for (int k = 0; k < m->w->W; ++k) ok = ok && hipMemcpy((char*)recv + (size_t)k * bytes, m->w->ptr[k], bytes, hipMemcpyDeviceToDevice) == hipSuccess;
+    for (int k = 0; k < m->w->W; ++k) ok = ok && hipMemcpyAsync((char*)recv + (size_t)k * bytes, m->w->ptr[k], bytes, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
     m->w->meet();
     return ok ? ncclSuccess : (ncclResult_t)1;
 }
@@ -179,7 +184,8 @@ static ncclResult_t mock_broadcast(const void* send, void* recv, size_t count, n
     bool ok = hipStreamSynchronize(s) == hipSuccess;
     if (m->rank == root) m->w->ptr[root] = send;
     m->w->meet();
-    if (recv != m->w->ptr[root]) ok = ok && hipMemcpy(recv, m->w->ptr[root], count * mock_size(t), hipMemcpyDeviceToDevice) == hipSuccess;
+    if (recv != m->w->ptr[root]) ok = ok && hipMemcpyAsync(recv, m->w->ptr[root], count * mock_size(t), hipMemcpyDeviceToDevice, s) == hipSuccess;
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
     m->w->meet();
     return ok ? ncclSuccess : (ncclResult_t)1;
 }

@@ -161,6 +161,8 @@ int32_t gpk_index_describe(const gpk_index* idx, int64_t out[8]) {
     out[2] = idx->pip.chain_xy != nullptr;
     out[3] = idx->pip.route != nullptr;
     out[4] = idx->pip_list_heavy;
+    out[5] = idx->route_own;
+    out[6] = idx->route_single;
     return GPK_OK;
 }
 

@@ -10,6 +10,7 @@
 #pragma once
 
 #include "gpk_common.h"
+#include "gpk_route.h"
 
 namespace gpk {
 
@@ -97,17 +98,12 @@ struct HalfCell {
 };
 static_assert(sizeof(HalfCell) * 2 == sizeof(SubCell), "two half-cell records overlay one SubCell");
 static_assert(CHAIN_MAX <= (int)HCHAIN_COUNT_MASK, "the edge count of a chain is a 4-bit field");
-// Level-1 routing of a small raster (R <= PIP_ROUTE_RMAX) as an LDS image: one 16-byte word per 32 consecutive cells of a
-// raster row.  A persistent work-group keeps the whole image in LDS (128 KB at R = 512) and a point learns from ONE LDS
-// read whether its cell is empty (nothing to fetch), carries a one-part record (its index = rec0 + rank of the cell's bit:
-// records are numbered in cell order) or needs the level-1 word from memory (interiors, the few list cells).
-constexpr int PIP_ROUTE_RMAX = 512;
-struct RouteWord {
-    uint32_t bmask;  // bit i: cell 32 * w + i carries a one-part level-2 record
-    uint32_t gmask;  // bit i: the cell's level-1 word must be read (interior of a part, list cell, anything else non-empty)
-    uint32_t rec0;   // record index of the first cell set in bmask
-    uint32_t pad;
-};
+// Level-1 routing of a small raster (R <= PIP_ROUTE_RMAX) as an LDS image: one 16-byte word per block of 8 x 4 raster cells
+// (gpk_route.h: RouteWord, the four cell states and the locate arithmetic).  A persistent work-group keeps the whole image in LDS
+// (128 KB at R = 512) and a point learns from ONE LDS read whether its cell is empty (nothing to fetch), carries a one-part record
+// (its index = rec0 + rank of the cell's bit: records are numbered in image order, route_order), lies strictly inside the block's
+// owner part (nothing to fetch either: the word names the part) or needs the level-1 word from memory (list cells, interiors of
+// another part than the owner).
 struct PipView {
     int32_t R;  // 0 = accelerator not built (degenerate extent): kernels use the generic walk
     double rx0, ry0, fw, fh, inv_fw, inv_fh;
@@ -160,6 +156,7 @@ struct gpk_index {
     uint64_t serial;  // unique per built index (never reused): what a cached copy of an index's pointers is keyed with
     int32_t pip_list_heavy;  // 1: more than a list word per four raster cells (overlapping parts, very many small parts): the general tile
                              // kernel runs its one-point-per-lane instance
+    int32_t route_own, route_single;  // of the routing image: cells in state `own`; raster cells strictly inside one part (CELL_TAG_SINGLE)
 };
 
 namespace gpk {

@@ -276,7 +276,8 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
     }
     GPK_SCHED_FENCE();
     FLOW_PHASE(1);  // points here
-    // 2. level 1 from the LDS image (two independent reads per point), then the half-cell record / the level-1 word of an interior
+    // 2. level 1 from the LDS image (two independent reads per point: the word of its block of 8 x 4 cells), then the half-cell record /
+    //    the level-1 word of a `gather` cell — an interior cell of the block's owner part needs neither
     const int logR = h.logR;
     const uint32_t sub_max = ((uint32_t)S << logR) - 1u;
     uint32_t sidx4[(P + 3) / 4], gw[P];
@@ -290,7 +291,7 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
         uint32_t sx = cvt_u32_sat((px[k] - h.rx0) * h.inv_fw_s), sy = cvt_u32_sat((py[k] - h.ry0) * h.inv_fh_s);
         sx = sx < sub_max ? sx : sub_max;
         sy = sy < sub_max ? sy : sub_max;
-        const uint32_t at = ((sy >> 3) << (logR - 5)) + (sx >> 8);
+        const uint32_t at = route_block_sub(sx, sy, logR);  // (the point's block of 8 x 4 raster cells: gpk_route.h)
         ms[k] = s_mask[at];
         r0s[k] = s_rec0[at];
         sxs[k] = sx;
@@ -299,15 +300,19 @@ __device__ __forceinline__ void flow_tile(const ChainHot& h, const uint2* s_mask
     GPK_SCHED_FENCE();
     static_for<P>([&](auto K) {
         constexpr int k = decltype(K)::value;
-        const uint32_t sx = sxs[k], sy = sys_[k], bit = (sx >> 3) & 31u;
+        const uint32_t sx = sxs[k], sy = sys_[k], bit = route_bit_sub(sx, sy);
         const bool real = !__builtin_isunordered(px[k], py[k]);
-        const bool has = real && ((ms[k].x >> bit) & 1u) != 0u;
-        const bool want = real && !has && ((ms[k].y >> bit) & 1u) != 0u;
+        // the cell's two mask bits: record (1, 0), gather (0, 1), own (1, 1) — strictly inside the block's owner part
+        const uint32_t recs = ms[k].x & ~ms[k].y;
+        const bool b = ((ms[k].x >> bit) & 1u) != 0u, g = ((ms[k].y >> bit) & 1u) != 0u;
+        const bool has = real && b && !g;
+        const bool want = real && g && !b;
         sidx4[k / 4] |= (((sy & 3u) << 3) | (sx & 7u)) << (8 * (k % 4));
         rec[k] = u32x4{0u, 0u, 0u, 0u};
-        gw[k] = 0u;
+        // (an `own` cell's level-1 word, as the table holds it, from the image word: no request)
+        gw[k] = real && b && g ? (CELL_TAG_SINGLE << 30) | (route_owner(r0s[k]) << 1) : 0u;
         if (has) {
-            const uint32_t w = r0s[k] + (uint32_t)__popc(__builtin_amdgcn_ubfe(ms[k].x, 0u, bit));
+            const uint32_t w = route_rec0(r0s[k]) + (uint32_t)__popc(__builtin_amdgcn_ubfe(recs, 0u, bit));
             rec[k] = *reinterpret_cast<const u32x4*>(h.half + (2u * w + ((sy >> 2) & 1u)));
         }
         if (want) gw[k] = h.cell[((sy >> 3) << logR) + (sx >> 3)];
@@ -414,8 +419,8 @@ __device__ __forceinline__ void flow_emit_chunk(const ChainHot& h, uint32_t e, u
 template <bool SIMPLE, int P>
 __global__ __launch_bounds__(FLOW_BLOCK) void pip_tile_flow_kernel(ChainHot h, FusedTail tail) {
     constexpr int WORDS = PIP_ROUTE_RMAX * PIP_ROUTE_RMAX / 32, W = FLOW_W, TS = P == 8 ? 9 : (P == 4 ? 8 : (P == 2 ? 7 : 6));
-    __shared__ uint2 s_mask[WORDS];     // RouteWord::bmask, gmask
-    __shared__ uint32_t s_rec0[WORDS];  // RouteWord::rec0
+    __shared__ uint2 s_mask[WORDS];     // RouteWord::bmask, gmask (a block of 8 x 4 cells a word)
+    __shared__ uint32_t s_rec0[WORDS];  // RouteWord::rec0: the block's first record | (owner part + 1) << 18
     __shared__ FlowItem s_items[W][FLOW_ITEMS];
     __shared__ uint32_t s_tcand[FLOW_MAX_TILES], s_ttot[FLOW_MAX_TILES];  // a tile's entries; its pairs (after the scan: the pairs before it)
     __shared__ uint32_t s_next, s_next2, s_wg, s_wgtot, s_gave_up;

@@ -390,13 +390,17 @@ __global__ void cell_build_kernel(DevGeo a, IndexView ix, PipView pv, FineGrid g
 // flag[c] = 1: the cell is crossed by exactly one part and nothing else is there (SubCell); flag2[c] = 1: the cell
 // holds exactly two parts and both cross it (SubCell2).  (A covering part + a crossing one was tried as a second record
 // kind: no gain on the power-law multipolygon column, 12 ms more build time.)
-__global__ void sub_flag_kernel(const uint32_t* __restrict__ cell, const uint32_t* __restrict__ list, int64_t n_cells,
+// route_logR != 0 (a raster small enough for a routing image, R = 1 << route_logR): the one-part flags, and so the records their scan
+// numbers, are addressed in IMAGE order (gpk_route.h: route_order) — a cell's record is then the first record of its block plus the
+// record cells below its bit.  Everything else reaches a record through the payload of cell[c] and does not care.
+__device__ __forceinline__ int64_t sub_slot(int64_t c, int route_logR) { return route_logR ? (int64_t)route_order((uint32_t)c, route_logR) : c; }
+__global__ void sub_flag_kernel(const uint32_t* __restrict__ cell, const uint32_t* __restrict__ list, int64_t n_cells, int route_logR,
                                 int32_t* __restrict__ flag, int32_t* __restrict__ flag2) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_cells) return;
     const uint32_t w = cell[c];
     const uint32_t tag = w >> 30;
-    flag[c] = (tag == CELL_TAG_SINGLE && (w & 1u)) ? 1 : 0;
+    flag[sub_slot(c, route_logR)] = (tag == CELL_TAG_SINGLE && (w & 1u)) ? 1 : 0;
     int f2 = 0;
     if (tag == CELL_TAG_LIST) {
         const uint32_t off = w & 0x3FFFFFFFu;
@@ -683,11 +687,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 1 ?
     store_labels(rec, label);
 }
 __global__ void sub_commit_kernel(const int32_t* __restrict__ flag, const int32_t* __restrict__ pos, const int32_t* __restrict__ flag2,
-                                  const int32_t* __restrict__ pos2, int64_t n_cells, uint32_t* __restrict__ cell) {
+                                  const int32_t* __restrict__ pos2, int64_t n_cells, int route_logR, uint32_t* __restrict__ cell) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_cells) return;
-    if (flag[c])
-        cell[c] = (CELL_TAG_SUB << 30) | (uint32_t)pos[c];
+    const int64_t o = sub_slot(c, route_logR);
+    if (flag[o])
+        cell[c] = (CELL_TAG_SUB << 30) | (uint32_t)pos[o];
     else if (flag2 && flag2[c])
         cell[c] = (CELL_TAG_SUB << 30) | SUB2_BIT | (uint32_t)pos2[c];
 }
@@ -863,44 +868,53 @@ __global__ void half_chain_commit_kernel(SubCell* __restrict__ sub, int64_t n_su
     h[0] = HalfCell{{rc.labels[0], rc.labels[1]}, rc.part_flags & ~SUB_INDIRECT, hword[2 * i]};
     h[1] = HalfCell{{rc.labels[2], rc.labels[3]}, rc.part_flags & ~SUB_INDIRECT, hword[2 * i + 1]};
 }
-// LDS image of the level-1 routing (gpk_index.h: RouteWord): one thread per 32 cells of a raster row, after sub_commit_kernel
-__global__ void route_build_kernel(const uint32_t* __restrict__ cell, int64_t n_words, RouteWord* __restrict__ route) {
+// LDS image of the level-1 routing (gpk_route.h): one thread per block of 8 x 4 raster cells, after sub_commit_kernel.  The block's
+// owner is the part with the most strictly-inside cells (CELL_TAG_SINGLE, boundary bit clear), the lowest part number on a tie; those
+// cells become `own`, every other non-empty cell without a one-part record stays `gather`.  counters[0] += own cells,
+// counters[1] += strictly-inside cells.
+__global__ void route_build_kernel(const uint32_t* __restrict__ cell, int64_t n_words, int logR, RouteWord* __restrict__ route,
+                                   uint32_t* __restrict__ counters) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= n_words) return;
-    RouteWord rw{0u, 0u, 0u, 0u};
-    bool have = false;
-    for (int i = 0; i < 32; ++i) {
-        const uint32_t cw = cell[32 * w + i];
-        const uint32_t tag = cw >> 30, payload = cw & 0x3FFFFFFFu;
+    const uint32_t bx = (uint32_t)w & ((1u << (logR - 3)) - 1u), by = (uint32_t)w >> (logR - 3);
+    uint32_t cw[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) cw[i] = cell[((int64_t)((by << 2) | (uint32_t)(i >> 3)) << logR) + ((bx << 3) | (uint32_t)(i & 7))];
+    uint32_t rec = 0u, other = 0u, inside = 0u, rec0 = 0u;
+#pragma unroll
+    for (int i = 31; i >= 0; --i) {  // (downwards: rec0 ends as the payload of the lowest record cell)
+        const uint32_t tag = cw[i] >> 30, payload = cw[i] & 0x3FFFFFFFu;
         if (tag == CELL_TAG_SUB && !(payload & SUB2_BIT)) {
-            rw.bmask |= 1u << i;
-            if (!have) {
-                rw.rec0 = payload;
-                have = true;
-            }
-        } else if (cw != 0u) {
-            rw.gmask |= 1u << i;
+            rec |= 1u << i;
+            rec0 = payload;
+        } else if ((cw[i] & 0xC0000001u) == (CELL_TAG_SINGLE << 30)) {
+            inside |= 1u << i;
+        } else if (cw[i] != 0u) {
+            other |= 1u << i;
         }
     }
-    route[w] = rw;
-}
-
-// RouteWord::pad = the 16-bit rank of rec0 among its raster row's records (rec0 - the rec0 of the row's first word that has records): the
-// persistent point-join kernels keep 16-bit ranks + one base per row in LDS, and with the rank in the word their image load is one
-// pass of independent 16-byte reads (the row's base = rec0 - pad of any of its words with records).  One thread per raster row.
-__global__ void route_rank_kernel(RouteWord* __restrict__ route, int R) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= R) return;
-    const int per_row = R / 32;
-    RouteWord* rw = route + (int64_t)row * per_row;
-    uint32_t base = 0u;
-    bool have = false;
-    for (int j = 0; j < per_row; ++j) {
-        if (rw[j].bmask && !have) {
-            base = rw[j].rec0;
-            have = true;
+    uint32_t owner = ROUTE_NO_OWNER, own = 0u;
+    if (inside) {  // (a third of the blocks of a right side of disjoint polygons; nearly all of them see one part)
+        uint32_t left = inside;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            if (!((left >> i) & 1u)) continue;
+            const uint32_t p = (cw[i] >> 1) & 0x1FFFFFFFu;
+            uint32_t m = 0u;
+#pragma unroll
+            for (int j = i; j < 32; ++j) m |= (uint32_t)(((cw[j] >> 1) & 0x1FFFFFFFu) == p) << j;
+            m &= left;
+            left &= ~m;
+            if (p < ROUTE_OWNER_MAX && (__popc(m) > __popc(own) || (__popc(m) == __popc(own) && p < owner))) {
+                owner = p;
+                own = m;
+            }
         }
-        rw[j].pad = rw[j].bmask ? rw[j].rec0 - base : 0u;
+    }
+    route[w] = RouteWord{rec | own, other | inside, route_pack(rec0, owner), 0u};
+    if (inside) {
+        if (own) atomicAdd(&counters[0], (uint32_t)__popc(own));
+        atomicAdd(&counters[1], (uint32_t)__popc(inside));
     }
 }
 
@@ -908,11 +922,13 @@ __global__ void route_rank_kernel(RouteWord* __restrict__ route, int R) {
 // RECORD instead of one per raster cell (two thirds of the cells of the C2 raster, nineteen in twenty of a 2048 x 2048 one,
 // carry no record)
 __global__ void sub_work_kernel(const uint32_t* __restrict__ cell, const int32_t* __restrict__ flag, const int32_t* __restrict__ pos,
-                                int64_t n_cells, int32_t* __restrict__ work_cell, uint32_t* __restrict__ work_part) {
+                                int64_t n_cells, int route_logR, int32_t* __restrict__ work_cell, uint32_t* __restrict__ work_part) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_cells || !flag[c]) return;
-    work_cell[pos[c]] = (int32_t)c;
-    work_part[pos[c]] = (cell[c] & 0x3FFFFFFFu) >> 1;
+    if (c >= n_cells) return;
+    const int64_t o = sub_slot(c, route_logR);
+    if (!flag[o]) return;
+    work_cell[pos[o]] = (int32_t)c;
+    work_part[pos[o]] = (cell[c] & 0x3FFFFFFFu) >> 1;
 }
 __global__ void lrec_assign_kernel(const uint32_t* __restrict__ cell, uint32_t* __restrict__ list, int64_t n_cells,
                                    const int32_t* __restrict__ pos, int32_t* __restrict__ work_cell, uint32_t* __restrict__ work_part) {
@@ -1239,6 +1255,9 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
     SubCell* sub = nullptr;
     SubCell2* sub2 = nullptr;
     static_assert(PIP_SLAB_MUL == 2, "SubCell stores exactly two adjacent slab ranges");
+    int route_logR = 0;  // R <= PIP_ROUTE_RMAX: log2 R — the one-part records are numbered in the routing image's order (sub_flag_kernel)
+    if (R <= PIP_ROUTE_RMAX)
+        while ((1 << route_logR) < R) ++route_logR;
     const bool level2_ok = g.pad_x / PIP_SUB > ulp64 && g.pad_y / PIP_SUB > ulp64 && R * PIP_SUB <= 32768;
     if (level2_ok) {
         int32_t *sflag, *spos, *sflag2, *spos2;
@@ -1246,7 +1265,8 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
         GPK_TRY(t.alloc(&spos, (size_t)n_cells + 1));
         GPK_TRY(t.alloc(&sflag2, (size_t)n_cells + 1));
         GPK_TRY(t.alloc(&spos2, (size_t)n_cells + 1));
-        GPK_LAUNCH("gpk_pipidx_sub_flag", sub_flag_kernel, blocks_for(n_cells), dim3(256), 0, s, cell, (const uint32_t*)list, n_cells, sflag, sflag2);
+        GPK_LAUNCH("gpk_pipidx_sub_flag", sub_flag_kernel, blocks_for(n_cells), dim3(256), 0, s, cell, (const uint32_t*)list, n_cells, route_logR, sflag,
+                   sflag2);
         GPK_TRY(exclusive_scan_i32(sflag, n_cells, spos, nullptr, btot, s));
         GPK_TRY(exclusive_scan_i32(sflag2, n_cells, spos2, nullptr, btot, s));
         GPK_HIP(d2h_small(&n_sub, spos + n_cells, sizeof n_sub, s));
@@ -1269,7 +1289,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
             GPK_TRY(t.alloc(&swork_cell, (size_t)n_sub));
             GPK_TRY(t.alloc(&swork_part, (size_t)n_sub));
             GPK_LAUNCH("gpk_pipidx_sub_work", sub_work_kernel, blocks_for(n_cells), dim3(256), 0, s, (const uint32_t*)cell, (const int32_t*)sflag,
-                       (const int32_t*)spos, n_cells, swork_cell, swork_part);
+                       (const int32_t*)spos, n_cells, route_logR, swork_cell, swork_part);
             GPK_LAUNCH("gpk_pipidx_sub_head", sub_head_kernel, blocks_for(n_sub), dim3(256), 0, s, pv, g, (const int32_t*)swork_cell,
                        (const uint32_t*)swork_part, (int64_t)n_sub, sub);
             // no ring with refined rows: nearly every record takes the fast path — its own instance (twice the waves per SIMD), then one
@@ -1297,7 +1317,7 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
         }
         if (n_sub > 0 || n_sub2 > 0) {
             GPK_LAUNCH("gpk_pipidx_sub_commit", sub_commit_kernel, blocks_for(n_cells), dim3(256), 0, s, sflag, spos, n_sub2 > 0 ? sflag2 : nullptr,
-                       spos2, n_cells, cell);
+                       spos2, n_cells, route_logR, cell);
             GPK_HIP(hipStreamSynchronize(s));
         }
     }
@@ -1381,17 +1401,24 @@ int32_t build_pip_index(const gpk_geoarray* a, gpk_index* ix, hipStream_t s, int
         GPK_LAUNCH("gpk_pipidx_chain_commit", half_chain_commit_kernel, blocks_for(n_sub), dim3(256), 0, s, sub, (int64_t)n_sub, (const uint32_t*)hword);
         pv.chain_xy = cxy;
         ix->nbytes += (int64_t)(sizeof(double2) * (size_t)n_ext);
+        uint32_t route_host[2] = {0u, 0u};
         if (R <= PIP_ROUTE_RMAX) {
             RouteWord* route = nullptr;
             const int64_t n_words = n_cells / 32;
             GPK_HIP(cached_malloc((void**)&route, sizeof(RouteWord) * (size_t)n_words));
             keep(route);
-            GPK_LAUNCH("gpk_pipidx_route", route_build_kernel, blocks_for(n_words), dim3(256), 0, s, (const uint32_t*)cell, n_words, route);
-            if (R >= 32) GPK_LAUNCH("gpk_pipidx_route_rank", route_rank_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, s, route, R);
+            uint32_t* route_counts;  // own cells, strictly-inside cells
+            GPK_TRY(t.alloc(&route_counts, 2));
+            GPK_HIP(hipMemsetAsync(route_counts, 0, 2 * sizeof(uint32_t), s));
+            GPK_LAUNCH("gpk_pipidx_route", route_build_kernel, blocks_for(n_words), dim3(256), 0, s, (const uint32_t*)cell, n_words, route_logR, route,
+                       route_counts);
+            GPK_HIP(d2h_small(route_host, route_counts, sizeof route_host, s));
             pv.route = route;
             ix->nbytes += (int64_t)(sizeof(RouteWord) * (size_t)n_words);
         }
-        GPK_HIP(hipStreamSynchronize(s));  // (the temporaries go back to the arena when this function returns)
+        GPK_HIP(sync_small(s));  // (the temporaries go back to the arena when this function returns)
+        ix->route_own = (int32_t)route_host[0];
+        ix->route_single = (int32_t)route_host[1];
         if (getenv("GPK_DEBUG_INDEX")) fprintf(stderr, "[gpk] half-cell chains: %d records, %lld extended coordinates%s\n", n_sub, (long long)n_ext, pv.route ? ", routing image" : "");
         stamp("local chains");
     }
