@@ -47,6 +47,7 @@ SOURCES = [
     "gpk_polyclip.hip",
     "gpk_polyunion.hip",
     "gpk_lineline.hip",
+    "gpk_pointrel.hip",
     "gpk_validity.hip",
     "gpk_triangulate.hip",
     "gpk_interior.hip",

@@ -819,6 +819,51 @@ class GeoSeries:
             raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown line / line predicate {name!r}: one of {sorted(LINE_MASK_PREDICATES)}")
         return line_mask_predicate(self.line_relation(other, other_rows), name)
 
+    # ---- point relations (gpk_pointrel.hip) ------------------------------------------------------
+    def point_relation(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """The exact relation mask (uint8) of every row's point set A against its geometry B (gpk_point_relation): bit 1 — a point of A
+        lies in B's interior, 2 — on B's boundary (a ring of a polygon, a mod-2 end of a line; points have none), 4 — a point of A is
+        no point of B, 8 — B has a point that is no point of A; 0 for a null or empty row, a NaN or infinite coordinate or an invalid
+        ring.  One side is a POINT / MULTIPOINT column, the other any family, in either order; the punctual side is A (`self` when
+        both are).  `other_rows` pairs row i with other[other_rows[i]] and needs `self` to be the punctual side."""
+        points_first = point_relation_sides("point_relation", self._family(), other._family())
+        rows = point_relation_rows_arg("point_relation", self, other, other_rows, points_first)
+        points, geoms = (self, other) if points_first else (other, self)
+        out = np.empty(len(points), dtype=np.uint8)
+        if len(out):
+            _abi.check(
+                _abi.lib().gpk_point_relation(
+                    points.device().handle, geoms.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
+                )
+            )
+        return out
+
+    def point_predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
+        """a named predicate "self[i] NAME other[i]" with a POINT / MULTIPOINT column on either side (POINT_MASK_PREDICATES: intersects,
+        disjoint, within, covered_by, contains, covers, contains_properly, touches, equals, crosses, overlaps), as bool; with the
+        punctual column in `other` the name is transposed (within <-> contains, covered_by <-> covers)"""
+        if name not in POINT_MASK_PREDICATES:
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown point predicate {name!r}: one of {sorted(POINT_MASK_PREDICATES)}")
+        points_first = point_relation_sides("point_predicate", self._family(), other._family())
+        dim_b = family_dim(other._family() if points_first else self._family())
+        return point_mask_predicate(self.point_relation(other, other_rows), name if points_first else point_transposed(name), dim_b)
+
+    def predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
+        """"self[i] NAME other[i]" for any two families, as bool: the relation family that serves the pair decides (predicate_route:
+        point_predicate when either side is punctual, line_predicate for two line columns, the polygon relations for two polygon
+        columns, the line / polygon relations otherwise), with that family's names.  The named methods (touches, crosses, ...) keep
+        their own, narrower family pairs."""
+        route, names = predicate_route(self._family(), other._family())
+        if name not in names:
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"predicate: unknown {route} predicate {name!r}: one of {sorted(names)}")
+        if route == "point":
+            return self.point_predicate(other, name, other_rows)
+        if route == "line":
+            return self.line_predicate(other, name, other_rows)
+        if route == "polygon":
+            return self._polygon_relation(other, name, other_rows)
+        return self._relation(other, name, other_rows)
+
     # ---- validity and simplicity (gpk_validity.hip) ----------------------------------------------
     def _validity(self, op: str, return_where: bool):
         validity_family_arg(op, self._family(), POLYGONAL)
@@ -1075,6 +1120,97 @@ def line_relation_args(op: str, a: "GeoSeries", b: "GeoSeries", rows) -> Optiona
     if len(a) != len(b):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
     return None
+
+
+PUNCTUAL = (GEOM_POINT, GEOM_MULTIPOINT)
+
+
+def family_dim(t: int) -> int:
+    """the dimension of a geometry family: 0 punctual, 1 lineal, 2 polygonal; any other type is refused"""
+    if t in PUNCTUAL:
+        return 0
+    if t in LINEAL:
+        return 1
+    if t in POLYGONAL:
+        return 2
+    raise _mismatch(f"no relation is defined for geometry type {t}")
+
+
+# the point predicates over the point relation mask and the dimension of B's family (include/geopolars_hip.h); mask 0 satisfies none
+POINT_MASK_PREDICATES = {
+    "intersects": lambda m, d: (m & 3) != 0,
+    "disjoint": lambda m, d: (m != 0) & ((m & 3) == 0),
+    "within": lambda m, d: ((m & 1) != 0) & ((m & 4) == 0),
+    "covered_by": lambda m, d: ((m & 3) != 0) & ((m & 4) == 0),
+    "contains": lambda m, d: ((m & 1) != 0) & ((m & 8) == 0),
+    "covers": lambda m, d: ((m & 3) != 0) & ((m & 8) == 0),
+    "touches": lambda m, d: ((m & 2) != 0) & ((m & 1) == 0),
+    "equals": lambda m, d: ((m & 1) != 0) & ((m & 12) == 0),
+    "crosses": lambda m, d: ((m & 1) != 0) & ((m & 4) != 0) if d >= 1 else np.zeros(m.shape, dtype=bool),
+    "overlaps": lambda m, d: (m & 13) == 13 if d == 0 else np.zeros(m.shape, dtype=bool),
+}
+POINT_MASK_PREDICATES["contains_properly"] = POINT_MASK_PREDICATES["contains"]  # a point set has no boundary to touch
+# "B contains_properly A" has no name of its own read from A: every point of A in B's interior, none on its boundary
+POINT_TRANSPOSED = {"within": "contains", "contains": "within", "covered_by": "covers", "covers": "covered_by", "contains_properly": "properly_within"}
+_POINT_TRANSPOSED_ONLY = {"properly_within": lambda m, d: (m & 7) == 1}
+
+
+def point_transposed(name: str) -> str:
+    """"B NAME A" as a predicate of (A, B), A the punctual side: within <-> contains, covered_by <-> covers, the rest read the same"""
+    return POINT_TRANSPOSED.get(name, name)
+
+
+def point_mask_predicate(mask, name: str, dim_b: int) -> np.ndarray:
+    """a named point predicate from relation masks; dim_b: the dimension of B's family (0, 1, 2)"""
+    f = POINT_MASK_PREDICATES.get(name) or _POINT_TRANSPOSED_ONLY.get(name)
+    if f is None:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"unknown point predicate {name!r}: one of {sorted(POINT_MASK_PREDICATES)}")
+    if dim_b not in (0, 1, 2):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"point predicate: the dimension of B's family must be 0, 1 or 2 (found {dim_b!r})")
+    return f(np.asarray(mask, dtype=np.uint8), dim_b)
+
+
+def point_relation_sides(op: str, a: int, b: int) -> bool:
+    """True when family `a` is punctual (A = the left column, also when both are), False when only `b` is; any other pair is refused as
+    the C ABI would"""
+    known = PUNCTUAL + LINEAL + POLYGONAL
+    if a in PUNCTUAL and b in known:
+        return True
+    if b in PUNCTUAL and a in known:
+        return False
+    raise _mismatch(f"{op}: Point | MultiPoint x any family, in either order (found {_abi_name(a)} x {_abi_name(b)})")
+
+
+def point_relation_rows_arg(op: str, a: "GeoSeries", b: "GeoSeries", rows, points_first: bool) -> Optional[np.ndarray]:
+    """the checks of point_relation before any device call: without a row map the row counts match; a row map (returned as uint32) has
+    one entry per row of `a` and needs `a` to be the punctual side unless it is the identity"""
+    if rows is not None:
+        try:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+        except (TypeError, ValueError, OverflowError):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
+        if r.ndim != 1 or len(r) != len(a):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
+        if points_first:
+            return r
+        if not np.array_equal(r, np.arange(len(a), dtype=np.uint32)):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: a row map needs the punctual column on the left (it maps point rows to rows of the other column)")
+    if len(a) != len(b):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+    return None
+
+
+def predicate_route(a: int, b: int):
+    """(the relation family that serves the pair of geometry types — "point", "line", "polygon" or "line_polygon" — and its predicate
+    names): the dispatch table of GeoSeries.predicate and spatial_index.sjoin; an unknown type is refused"""
+    da, db = family_dim(a), family_dim(b)
+    if da == 0 or db == 0:
+        return "point", POINT_MASK_PREDICATES
+    if da == 1 and db == 1:
+        return "line", LINE_MASK_PREDICATES
+    if da == 2 and db == 2:
+        return "polygon", POLYGON_MASK_PREDICATES
+    return "line_polygon", MASK_PREDICATES
 
 
 # the codes of gpk_validity (include/geopolars_hip.h: GPK_VALID, GPK_INVALID_*), by value

@@ -12,6 +12,8 @@
                             overlaps, contains_properly, equals
     spatial_join_line_relation      the same for lines x lines: intersects, within, contains, covers, covered_by, crosses, touches,
                             overlaps, equals
+    spatial_join_point_relation     the same with a point table on either side (or both): the nine names above from the point mask
+    sjoin                           any two families: the one of the four relation joins that serves the pair
     spatial_join_intersection       polygons x polygons or lines x polygons (not in the reference): every pair that shares more than
                             a threshold of area / length, with the shared amount as an f64 `measure` column
 
@@ -41,7 +43,9 @@ from .geoseries import (
     intersection_families_arg,
     intersection_min_measure_arg,
     line_clip_call,
+    point_relation_sides,
     polygon_clip_call,
+    predicate_route,
     relation_sides,
 )
 
@@ -1085,3 +1089,106 @@ def spatial_join_line_relation(lhs, rhs, options: Optional[SpatialJoinRelationAr
     options = options or SpatialJoinRelationArgs()
     return _payload_table_join("line relation join", lhs, rhs, options, lambda: _known_predicate("line relation join", options.predicate, LINE_RELATION_PREDICATES), line_relation_pairs,
                                relation_col=options.relation_col)
+
+# ---- point predicate join (gpk_point_relation_join) --------------------------------------------------------------------------------
+
+# GeoPandas' predicate names (plus `equals`) -> GPK_PT_PRED_*
+POINT_RELATION_PREDICATES = {
+    "intersects": _abi.PT_PRED_INTERSECTS,
+    "within": _abi.PT_PRED_WITHIN,
+    "contains": _abi.PT_PRED_CONTAINS,
+    "covered_by": _abi.PT_PRED_COVERED_BY,
+    "covers": _abi.PT_PRED_COVERS,
+    "crosses": _abi.PT_PRED_CROSSES,
+    "touches": _abi.PT_PRED_TOUCHES,
+    "overlaps": _abi.PT_PRED_OVERLAPS,
+    "equals": _abi.PT_PRED_EQUALS,
+}
+
+
+def point_relation_predicate_arg(predicate: str, left_family: int, right_family: int) -> int:
+    """The GPK_PT_PRED_* id of a predicate name for a join of these two families, checked before any device call and in the C ABI's
+    order: a known name, then a POINT | MULTIPOINT column on at least one side.  The relation is always read "left row <predicate>
+    right row"; the library transposes it when only the right side is punctual."""
+    if predicate not in POINT_RELATION_PREDICATES:
+        raise _abi.GeopolarsHipError(
+            _abi.GPK_ERR_INVALID_ARGUMENT, f"point relation join: unknown predicate {predicate!r}: one of {sorted(POINT_RELATION_PREDICATES)}"
+        )
+    point_relation_sides("point relation join", left_family, right_family)
+    return POINT_RELATION_PREDICATES[predicate]
+
+
+def point_relation_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    predicate: str = "intersects",
+    r_index: Optional[SpatialIndex] = None,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every (l, r) of a point column and a column of any family, in either order (or one point column against itself: duplicates),
+    with "left row <predicate> right row": (pairs (H, 2) uint32 sorted by (l, r), counts (n_left,) uint32, masks (H,) uint8 — the
+    point relation mask of the pair, A = the punctual side, the left one when both are).  Host-buffer variant: the pair buffer is
+    sized like join_pairs'."""
+    pred = point_relation_predicate_arg(predicate, left._family(), right._family())
+    return _payload_pairs("gpk_point_relation_join", left, right, r_index, pred, left_row_base, payload=np.uint8)
+
+
+def point_relation_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    predicate: str,
+    out_counts,
+    out_pairs,
+    out_mask=None,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_mask (cap,) uint8 torch CUDA tensors (any may
+    be None; out_pairs None = count only; without out_mask the work on a pair ends as soon as its predicate is settled) are filled in
+    place on `stream`; returns the number of pairs."""
+    pred = point_relation_predicate_arg(predicate, left.geom_type, right.geom_type)
+    return _payload_pairs_device("gpk_point_relation_join", left, right, r_index, pred, out_counts, out_pairs, out_mask, left_row_base, stream)
+
+
+def spatial_join_point_relation(lhs, rhs, options: Optional[SpatialJoinRelationArgs] = None):
+    """GeoPandas' sjoin(predicate=...) over two pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes
+    them), at least one of them of points: every left row with every right row in the relation, shaped like spatial_join_relation's
+    result — suffixed left columns, suffixed right columns, then `relation_col` (the pair's 4-bit mask) when asked for."""
+    options = options or SpatialJoinRelationArgs()
+    return _payload_table_join("point relation join", lhs, rhs, options, lambda: _known_predicate("point relation join", options.predicate, POINT_RELATION_PREDICATES), point_relation_pairs,
+                               relation_col=options.relation_col)
+
+
+# ---- one join for every pair of families ---------------------------------------------------------------------------------------------
+
+# predicate_route's relation family -> (the predicate names of its join, its pairs function)
+SJOIN_ROUTES = {
+    "point": (POINT_RELATION_PREDICATES, point_relation_pairs),
+    "line": (LINE_RELATION_PREDICATES, line_relation_pairs),
+    "polygon": (POLYGON_RELATION_PREDICATES, polygon_relation_pairs),
+    "line_polygon": (RELATION_PREDICATES, relation_pairs),
+}
+
+
+def sjoin_pairs(left: GeoSeries, right: GeoSeries, predicate: str = "intersects", r_index: Optional[SpatialIndex] = None, left_row_base: int = 0):
+    """(pairs, counts, masks) of "left row <predicate> right row" for any two families: the relation join that serves the pair
+    (predicate_route) with its own predicate names and its own mask.  An unknown geometry type or a name the family does not have is
+    refused before any device call."""
+    route = predicate_route(left._family(), right._family())[0]
+    names, pairs_fn = SJOIN_ROUTES[route]
+    if predicate not in names:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"sjoin: unknown {route} join predicate {predicate!r}: one of {sorted(names)}")
+    return pairs_fn(left, right, predicate, r_index, left_row_base)
+
+
+def sjoin(lhs, rhs, predicate: str = "intersects", join_type: str = "inner", relation_col: Optional[str] = None, l_suffix: Optional[str] = "_left",
+          r_suffix: Optional[str] = "_right", r_index: Optional[SpatialIndex] = None, l_geom_type: int = -1, r_geom_type: int = -1):
+    """GeoPandas' sjoin(lhs, rhs, predicate=...) over two pyarrow Tables with a `geometry` column of any two families: the table join
+    of the relation family that serves the pair (spatial_join_point_relation, _line_relation, _polygon_relation, _relation), chosen
+    once the geometry columns are decoded.  `relation_col`: that family's mask of every pair."""
+    options = SpatialJoinRelationArgs(predicate=predicate, join_type=join_type, relation_col=relation_col, l_suffix=l_suffix, r_suffix=r_suffix,
+                                      r_index=r_index, l_geom_type=l_geom_type, r_geom_type=r_geom_type)
+    every = set().union(*(names for names, _ in SJOIN_ROUTES.values()))
+    return _payload_table_join("sjoin", lhs, rhs, options, lambda: _known_predicate("sjoin", predicate, {k: None for k in every}), sjoin_pairs,
+                               relation_col=relation_col)

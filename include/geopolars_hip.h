@@ -959,6 +959,69 @@ int32_t gpk_line_relation_join(const gpk_geoarray* left, const gpk_geoarray* rig
                                uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask, int64_t pair_capacity,
                                int64_t* n_pairs, int32_t out_space, void* stream);
 
+/* ---- point relations (gpk_pointrel.hip) -----------------------------------------------------------------------------------------------
+ * How a punctual geometry lies to a geometry of any family.  A = a POINT or MULTIPOINT row, the finite set of its points; B = a row of
+ * any of the six families.  The relation is a 4-bit mask: */
+#define GPK_PT_INTERIOR 1  /* a point of A lies in the interior of B */
+#define GPK_PT_BOUNDARY 2  /* a point of A lies on the boundary of B */
+#define GPK_PT_EXTERIOR 4  /* a point of A is no point of B */
+#define GPK_PT_B_OUTSIDE 8 /* B has a point that is no point of A */
+/* Interior and boundary of B are those of the sibling relations:
+ *   punctual B     every point is interior, there is no boundary; bit 8: some point of B equals no point of A (exact coordinate
+ *                  comparison; duplicates and member order do not matter)
+ *   lineal B       the closed point set of its segments and coordinates with the mod-2 boundary of gpk_line_relation; a member of one
+ *                  coordinate or of equal coordinates is a point of the row without a boundary.  Bit 8 unless every member of B is
+ *                  such a point and each of them is a point of A.  Nothing assumes B is simple.
+ *   polygonal B    the point sets of gpk_polygon_relation: interior = inside a part's shell, outside its holes and off every ring;
+ *                  boundary = on a ring; exterior = outside every part or strictly inside a hole.  Exact for OGC-valid rows (rings
+ *                  that touch at points are allowed, and a point of A may sit on such a point: boundary); bit 8 is always set.  For an
+ *                  invalid polygon the mask is unspecified and the call terminates
+ *                  (gpk_validity says which rows are valid).
+ * This is DE-9IM with dim(A) = 0 and an empty boundary of A: II, IB, IE are the bits 1, 2, 4, and bit 8 is "EI or EB non-empty".
+ * Every named predicate is a function of the mask and of the dimension of B's FAMILY (0, 1, 2 by column type, not by degeneracy):
+ *   intersects     mask & 3                               disjoint       mask != 0 && !(mask & 3)
+ *   within         (mask & 1) && !(mask & 4)              covered_by     (mask & 3) && !(mask & 4)
+ *   contains       (mask & 1) && !(mask & 8)              covers         (mask & 3) && !(mask & 8)      (A contains / covers B)
+ *   touches        (mask & 2) && !(mask & 1)              equals         (mask & 1) && !(mask & 12)
+ *   crosses        dim(B) >= 1: (mask & 1) && (mask & 4);  dim(B) == 0: never
+ *   overlaps       dim(B) == 0: (mask & 13) == 13;         dim(B) >= 1: never
+ * For two punctual rows mask(B, A) is mask(A, B) with the bits 4 and 8 swapped.  A usable pair never has mask 0; the masks that occur
+ * are 1, 5, 9, 12, 13 for a punctual B, 9 .. 15 for a polygonal B, 9 .. 15 and (all members degenerate) 1, 5 for a lineal B.  The mask
+ * is EXACT: exact orientation signs and coordinate comparisons only, no tolerance, the same at any placement.  Rows, on either side:
+ *   row unusable           null, no coordinate, a NaN or infinite coordinate (a POINT with NaN is the empty point), a polygon ring that
+ *                          fails the ring rule of `contains`: mask 0, and every predicate is false
+ *   empty members are ignored
+ *
+ * Row-wise: out_mask[i] = mask(points[i], other[other_rows[i]]).  `points` POINT | MULTIPOINT, `other` any of the six families, anything
+ * else GPK_ERR_MISMATCHED_GEOMETRY; `other_rows` (same space as the output) as b_rows of gpk_line_relation: NULL = identity (the row
+ * counts must then match, else GPK_ERR_INVALID_ARGUMENT), an entry >= n_geoms(other) gives mask 0; all before any device work.
+ * Outputs are stream-ordered (host outputs: the call waits for them).  out_mask[n_geoms(points)] bytes. */
+int32_t gpk_point_relation(const gpk_geoarray* points, const gpk_geoarray* other, const uint32_t* other_rows, uint8_t* out_mask,
+                           int32_t out_space, void* stream);
+#define GPK_PT_PRED_INTERSECTS 0
+#define GPK_PT_PRED_WITHIN 1
+#define GPK_PT_PRED_CONTAINS 2
+#define GPK_PT_PRED_COVERED_BY 3
+#define GPK_PT_PRED_COVERS 4
+#define GPK_PT_PRED_CROSSES 5
+#define GPK_PT_PRED_TOUCHES 6
+#define GPK_PT_PRED_OVERLAPS 7
+#define GPK_PT_PRED_EQUALS 8
+/* Point predicate join (GeoPandas sjoin(points, ..., predicate=...)): every (l, r) with "left row PREDICATE right row".  At least one
+ * side must be POINT | MULTIPOINT, else GPK_ERR_MISMATCHED_GEOMETRY (the message names the join of the two families); an unknown
+ * predicate id: GPK_ERR_INVALID_ARGUMENT, checked first.  A is the punctual side — the left one when both are — and out_mask is always
+ * the mask with that A; when only the right side is punctual the transposed predicate is evaluated (within <-> contains, covered_by
+ * <-> covers, the rest read the same both ways).  A predicate that can never hold for the pair of families (overlaps against a line or
+ * a polygon, crosses between points) is a valid call with zero pairs.  Unusable rows never match.  `left` and `right` may be the same
+ * array (duplicates of a point table): pair (i, i) then appears for intersects / equals / within / contains / covered_by / covers.
+ * Outputs (out_counts, out_pairs, out_mask, *n_pairs), the capacity rule, count-only mode, `left_row_base`, `right_index` (NULL: a
+ * GPK_INDEX_BBOX_GRID index is built for the call and freed) and the error order are those of gpk_line_relation_join.  Without
+ * out_mask a pair's work ends as soon as its predicate is settled.  Synchronous.  gpk_spatial_join, gpk_predicate_rowwise and every
+ * other call are unchanged. */
+int32_t gpk_point_relation_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t predicate,
+                                uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, uint8_t* out_mask, int64_t pair_capacity,
+                                int64_t* n_pairs, int32_t out_space, void* stream);
+
 /* ---- validity and simplicity (gpk_validity.hip) -------------------------------------------------------------------------------------
  * Is a polygonal row OGC-valid — the condition under which the relation masks above are exact — and if not, why not and where.
  * `a` is a POLYGON or MULTIPOLYGON column (any other family: GPK_ERR_MISMATCHED_GEOMETRY, before any device work).  Only the non-empty
