@@ -58,6 +58,7 @@ LL_INTERIORS, LL_SHARED_PIECE, LL_INT_BND, LL_BND_INT, LL_BND_BND, LL_A_OUTSIDE,
 (LL_PRED_INTERSECTS, LL_PRED_WITHIN, LL_PRED_CONTAINS, LL_PRED_COVERED_BY, LL_PRED_COVERS, LL_PRED_CROSSES, LL_PRED_TOUCHES, LL_PRED_OVERLAPS,
  LL_PRED_EQUALS) = range(9)  # GPK_LL_PRED_*
 PT_INTERIOR, PT_BOUNDARY, PT_EXTERIOR, PT_B_OUTSIDE = 1, 2, 4, 8  # GPK_PT_*: the bits of the point relation mask
+GPK_KNN_MAX_K, GPK_KNN_EXCLUDE_SELF = 64, 1  # gpk_knn_join: the largest k, its one flag
 (PT_PRED_INTERSECTS, PT_PRED_WITHIN, PT_PRED_CONTAINS, PT_PRED_COVERED_BY, PT_PRED_COVERS, PT_PRED_CROSSES, PT_PRED_TOUCHES, PT_PRED_OVERLAPS,
  PT_PRED_EQUALS) = range(9)  # GPK_PT_PRED_*
 
@@ -194,6 +195,10 @@ _PROTOS = {
     "gpk_nearest_join_any": (
         C.c_int32,
         [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
+    ),
+    "gpk_knn_join": (
+        C.c_int32,
+        [_VP, _VP, _VP, C.c_int32, C.c_double, C.c_uint32, C.c_uint32, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), C.c_int32, _VP],
     ),
     "gpk_dwithin_join": (
         C.c_int32,

@@ -39,6 +39,7 @@ SOURCES = [
     "gpk_nearest.hip",
     "gpk_dwithin.hip",
     "gpk_nearest_any.hip",
+    "gpk_knn.hip",
     "gpk_linref.hip",
     "gpk_linearea.hip",
     "gpk_polyrel.hip",

@@ -497,6 +497,7 @@ int32_t bbox_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk
                    (const uint32_t*)cand_r, (const uint8_t*)hit, counts, (const int32_t*)offsets, left_row_base, (uint2*)pairs_dev,
                    pair_capacity);
     if (want_pairs && refine.emitted) GPK_TRY(refine.emitted(refine.ctx, n, cand_off, hit, offsets, scratch, pair_capacity, s));
+    if (want_pairs && refine.emitted_pairs) GPK_TRY(refine.emitted_pairs(refine.ctx, offsets, left_row_base, pairs_dev, pair_capacity, s));
     unsigned long long total = 0;  // 64-bit grand total of the hit scan (hits <= candidates <= INT32_MAX, checked above)
     hipError_t e = hipMemcpyAsync(&total, btot + nb, sizeof total, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -568,7 +569,8 @@ int32_t payload_join(const PayloadJoin& join, const gpk_index* right_index, uint
     hook.scratch_fixed = 512;
     hook.scratch_per_cand = (cx.payload_out ? cx.payload_elem : 0) + join.extra_per_cand;
     hook.refine = join.refine;
-    hook.emitted = payload_emitted;
+    hook.emitted = join.emitted_pairs ? nullptr : payload_emitted;
+    hook.emitted_pairs = join.emitted_pairs;
     rc = bbox_join(left, right, right_index, left_row_base, out_counts, out_pairs, pair_capacity, n_pairs, out_space, s, other ? other : lbox, hook);
     if (rc != GPK_OK) return finish(rc);
     if (want_payload && host_out && *n_pairs > 0) {

@@ -23,6 +23,10 @@ struct CandRefine {
     // payload is gathered here); nullptr: nothing to gather.  Only called when pairs were asked for.
     int32_t (*emitted)(void* ctx, int64_t n_rows, const int32_t* cand_off, const uint8_t* hit, const int32_t* offsets, void* scratch,
                        int64_t pair_capacity, hipStream_t s);
+    // enqueued last, when pairs were asked for: `pairs` is the DEVICE pair buffer (the caller's, or its staging) holding row i's hits in
+    // candidate order at offsets[i] — a join that orders a row's pairs itself (gpk_knn.hip: by rank) rewrites them here.  nullptr
+    // (every other join): the pairs stay as emitted.
+    int32_t (*emitted_pairs)(void* ctx, const int32_t* offsets, uint32_t left_row_base, uint32_t* pairs, int64_t pair_capacity, hipStream_t s);
 };
 
 // The box-candidate join with the caller's left boxes (device, one per left row; NaN: no candidates; nullptr: the rows' own boxes,
@@ -66,6 +70,9 @@ struct PayloadJoin {
     // nullptr: candidates from the left rows' own boxes.  Otherwise called once `own` (those boxes) is enqueued and the right side's
     // index exists: it fills `other` (n boxes), which take the left boxes' place in the candidate search.
     int32_t (*boxes)(PayloadCtx* ctx, const gpk_index* right_index, const double4* own, double4* other, int64_t n, hipStream_t s);
+    // nullptr: the payload of a row's hits is gathered in candidate order.  Otherwise CandRefine::emitted_pairs of a join that writes
+    // pairs and payload (PayloadCtx::payload_out, nullptr when none was asked for) in an order of its own; the gather does not run.
+    decltype(CandRefine::emitted_pairs) emitted_pairs = nullptr;
 };
 // Everything such a join does once its arguments are validated: the empty cases, a temporary GPK_INDEX_BBOX_GRID index when the caller
 // has none (freed on every path, after a sync), boxes and payload staging in workspace_aux(0), bbox_join, the payload of a host caller.

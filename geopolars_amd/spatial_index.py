@@ -505,6 +505,115 @@ def spatial_join_nearest(lhs, rhs, options: Optional[SpatialJoinNearestArgs] = N
     return _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
 
 
+# ---- k-nearest-neighbours join (gpk_knn_join) -----------------------------------------------------------------------------------
+
+
+@dataclass
+class SpatialJoinKnnArgs:
+    """Options of spatial_join_knn: every left row with its k nearest right rows, nearest first."""
+
+    k: int = 1  # 1 .. GPK_KNN_MAX_K
+    join_type: str = "inner"  # "inner" | "left" (unmatched left rows once, with nulls on the right)
+    max_distance: Optional[float] = None  # None: no limit; else only pairs with distance <= max_distance
+    exclude_self: bool = False  # never pair row i with row i (a table joined against itself)
+    distance_col: Optional[str] = None  # name of a float64 column with each pair's distance (null for unmatched left rows)
+    rank_col: Optional[str] = None  # name of a nullable uint32 column: 0 is the nearest (null for unmatched left rows)
+    l_suffix: Optional[str] = "_left"
+    r_suffix: Optional[str] = "_right"
+    r_index: Optional[SpatialIndex] = None
+    l_geom_type: int = -1  # as in SpatialJoinArgs
+    r_geom_type: int = -1
+
+
+def _knn_k_arg(k) -> int:
+    """k of a knn join, refused here — before any device call — unless it is an integer in 1 .. GPK_KNN_MAX_K"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _abi.GPK_KNN_MAX_K:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"knn join: k must be an integer in 1 .. {_abi.GPK_KNN_MAX_K}, got {k!r}")
+    return int(k)
+
+
+def knn_pairs(
+    left: GeoSeries,
+    right: GeoSeries,
+    k: int,
+    r_index: Optional[SpatialIndex] = None,
+    max_distance: Optional[float] = None,
+    exclude_self: bool = False,
+    left_row_base: int = 0,
+) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """For every row of `left`, its k nearest rows of `right` (gpk_knn_join; any two geometry families; within max_distance when given;
+    exclude_self: never row l + left_row_base itself): (pairs (H, 2) uint32 sorted by (l, distance, r), counts (n_left,) uint32, each at
+    most k, distances (H,) float64 — the doubles GeoSeries.distance returns for the pairs).  A tie at the k-th place goes to the lower
+    right row.  Host-buffer variant: the buffers hold n_left * k pairs, which always suffices."""
+    k = _knn_k_arg(k)
+    md = _max_distance_arg(max_distance)
+    _require_nearest_families(left._family(), right._family())
+    n = len(left)
+    capacity = max(1, n * k)
+    counts = np.zeros(n, dtype=np.uint32)
+    pairs, dist = np.empty((capacity, 2), dtype=np.uint32), np.empty(capacity, dtype=np.float64)
+    n_pairs = C.c_int64(0)
+    _abi.check(_abi.lib().gpk_knn_join(
+        left.device().handle, right.device().handle, r_index.handle if r_index is not None else None, k, md,
+        _abi.GPK_KNN_EXCLUDE_SELF if exclude_self else 0, left_row_base, counts.ctypes.data, pairs.ctypes.data, dist.ctypes.data, capacity,
+        C.byref(n_pairs), MEM_HOST, None))
+    h = int(n_pairs.value)
+    return pairs[:h].copy(), counts, dist[:h].copy()
+
+
+def knn_pairs_device(
+    left: DeviceGeoArray,
+    right: DeviceGeoArray,
+    r_index: Optional[SpatialIndex],
+    k: int,
+    out_counts,
+    out_pairs,
+    out_dist=None,
+    max_distance: Optional[float] = None,
+    exclude_self: bool = False,
+    left_row_base: int = 0,
+    stream: int = 0,
+) -> int:
+    """Device-buffer variant: out_counts (n,) uint32-as-int32, out_pairs (cap, 2) and out_dist (cap,) float64 torch CUDA tensors (any
+    may be None; out_pairs None = count only) are filled in place on `stream`; returns the number of pairs."""
+    k = _knn_k_arg(k)
+    md = _max_distance_arg(max_distance)
+    _require_nearest_families(left.geom_type, right.geom_type)
+    n_pairs = C.c_int64(0)
+    rh, cap = r_index.handle if r_index is not None else None, out_pairs.shape[0] if out_pairs is not None else 0
+    _abi.check(_abi.lib().gpk_knn_join(
+        left.handle, right.handle, rh, k, md, _abi.GPK_KNN_EXCLUDE_SELF if exclude_self else 0, left_row_base, _ptr(out_counts), _ptr(out_pairs),
+        _ptr(out_dist), cap, C.byref(n_pairs), MEM_DEVICE, stream))
+    return int(n_pairs.value)
+
+
+def spatial_join_knn(lhs, rhs, options: Optional[SpatialJoinKnnArgs] = None):
+    """The k-nearest-neighbours join over pyarrow Tables with a `geometry` column (WKB or native GeoArrow, as spatial_join takes them):
+    every left row with its k nearest right geometries, nearest first, shaped like spatial_join's result — suffixed left columns,
+    suffixed right columns, then `distance_col` and `rank_col` when asked for.  Any two of the six geometry families."""
+    options = options or SpatialJoinKnnArgs()
+    if options.join_type not in ("inner", "left"):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"knn join: join_type must be 'inner' or 'left', got {options.join_type!r}")
+    k = _knn_k_arg(options.k)
+    md = _max_distance_arg(options.max_distance)
+    lgeo = GeoSeries.from_arrow(lhs.column("geometry"), _geometry_type_of(lhs, options.l_geom_type, "l_geom_type"))
+    rgeo = GeoSeries.from_arrow(rhs.column("geometry"), _geometry_type_of(rhs, options.r_geom_type, "r_geom_type"))
+    pairs, counts, dist = knn_pairs(lgeo, rgeo, k, options.r_index, md, options.exclude_self)
+    li, ri = join_indices(counts, pairs, options.join_type)  # i64 row indices, r = -1 for unmatched left rows
+    table = _assemble(lhs, rhs, lgeo, rgeo, li, ri, options.l_suffix, options.r_suffix, options.distance_col, dist)
+    if options.rank_col is not None:
+        import pyarrow as pa
+
+        # pair j of a left row has rank j: the pairs come nearest first
+        starts = np.concatenate([[0], np.cumsum(counts.astype(np.int64))[:-1]]) if len(counts) else np.zeros(0, np.int64)
+        rank = (np.arange(len(pairs), dtype=np.int64) - np.repeat(starts, counts.astype(np.int64))).astype(np.uint32)
+        matched = ri >= 0
+        rk = np.zeros(len(ri), dtype=np.uint32)
+        rk[matched] = rank
+        table = table.append_column(options.rank_col, pa.array(rk, type=pa.uint32(), mask=~matched))
+    return table
+
+
 # ---- what the joins with a value per pair share (dwithin, the three relation joins, the intersection measure) --------------------------
 # Their ABI calls have one shape: (left, right, index, <one family argument>, left_row_base, counts, pairs, payload, capacity, n_pairs,
 # space, stream).  The public functions below validate their own argument, then go through these.

@@ -635,6 +635,49 @@ int32_t gpk_nearest_join_any(const gpk_geoarray* left, const gpk_geoarray* right
                              int64_t* n_pairs, int32_t out_space, void* stream);
 
 /*
+ * k-nearest-neighbours join for any two geometry families (spatial weights over a column against itself, inverse-distance
+ * interpolation, "the five nearest roads"): for every left row l, the k usable right rows nearest to it, nearest first.  Left and right
+ * are each any of POINT, MULTIPOINT, LINESTRING, MULTILINESTRING, POLYGON, MULTIPOLYGON — all 36 ordered pairs (anything else:
+ * GPK_ERR_MISMATCHED_GEOMETRY).
+ *   d(l, r)              the library's own row-wise distance of the pair, as in gpk_nearest_join_any: the value the per-row kernel of
+ *                        gpk_distance_rowwise(left, right, ...) computes for these two columns — the same device routine, the same
+ *                        lane-group size, the same lane order, the work-group routine above PD_LARGE_COST — so every returned distance
+ *                        is bit for bit what that call returns for the pair (0 for rows that meet, contained rows included; -0.0 is
+ *                        returned as +0.0).  (Its grouped schedule for LINESTRING right sides with >= 8 rows per target agrees within
+ *                        its 1e-9 contract.)
+ *   key                  (bits(d), r), compared lexicographically.  Distances are non-negative, so the order of the bits is the order
+ *                        of the values; the keys of a left row are distinct.
+ *   result of a row      the min(k, m) smallest keys, m the number of usable right rows with d <= max_distance.  A tie at the k-th
+ *                        place goes to the lower right row: exactly k pairs are returned when k exist — this is NOT the tie-inclusive
+ *                        set of gpk_nearest_join_any (at k = 1 it is that set's lowest right row).
+ *   k                    1 .. GPK_KNN_MAX_K (64), else GPK_ERR_INVALID_ARGUMENT.  The cap is a limit of this version: it lets the
+ *                        per-row state of the search live in LDS.
+ *   max_distance         only pairs with d <= max_distance (closed); INFINITY = no limit; negative or NaN: GPK_ERR_INVALID_ARGUMENT
+ *   flags                GPK_KNN_EXCLUDE_SELF: the pair with r == l + left_row_base is never returned and never counts towards k (a
+ *                        column joined against itself, or a row shard of it against the whole).  Unknown bits: GPK_ERR_INVALID_ARGUMENT.
+ *                        k, max_distance and flags are checked before any device work.
+ *   never matched,       null rows, EMPTY rows (no member has a coordinate) and POINT rows with a NaN coordinate, on either side (the
+ *   never candidates     rule of gpk_dwithin_join): such a left row has count 0, such a right row is nobody's neighbour.  An empty right
+ *                        side, or one of such rows only, gives no pairs.
+ *   out_counts[n_left]   u32 pairs per left row, at most k (may be NULL)
+ *   out_pairs[2*cap]     u32 (l, r) interleaved, sorted by (l, d, r): nearest first within a left row (NULL with cap == 0: count-only
+ *                        mode)
+ *   out_dist[cap]        f64 d(l, r) of each pair (may be NULL)
+ *   *n_pairs             total, always set; GPK_ERR_CAPACITY when > cap and pairs were asked for (cap >= n_left * k always suffices).
+ *                        More than 2^31 - 1 bbox candidates (right boxes meeting a left box grown by the row's search radius):
+ *                        GPK_ERR_CAPACITY, shard the left side.
+ * The result does not depend on scheduling: two calls give identical bytes.  `left_row_base` is added to every emitted l.  All buffers
+ * live in `out_space`.  `right_index`: an index of `right` carrying the bbox grid (else GPK_ERR_INVALID_ARGUMENT), or NULL: a
+ * GPK_INDEX_BBOX_GRID index is built for the call and freed (it is not kept on the handle).  Synchronous, like gpk_spatial_join.
+ * Magnitude range: as gpk_distance_rowwise.
+ */
+#define GPK_KNN_MAX_K 64
+#define GPK_KNN_EXCLUDE_SELF 1u
+int32_t gpk_knn_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t k, double max_distance,
+                     uint32_t flags, uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_dist,
+                     int64_t pair_capacity, int64_t* n_pairs, int32_t out_space, void* stream);
+
+/*
  * Within-distance join (GeoPandas sjoin(predicate="dwithin", distance=d)): every (l, r) with distance(left[l], right[r]) <= distance.
  * Left and right are each any of POINT, MULTIPOINT, LINESTRING, MULTILINESTRING, POLYGON, MULTIPOLYGON — all 36 ordered pairs
  * (anything else: GPK_ERR_MISMATCHED_GEOMETRY).
