@@ -50,6 +50,7 @@ TRI_OK, TRI_EMPTY, TRI_FAILED = 0, 1, 2  # GPK_TRI_*: the row status of gpk_tria
 CLIP_INSIDE, CLIP_OUTSIDE, CLIP_DROP_EMPTY = 0, 1, 1  # GPK_CLIP_*: the two modes of gpk_line_clip and its flag
 PCLIP_INTERSECTION, PCLIP_DIFFERENCE = 0, 1  # GPK_PCLIP_*: the two modes of gpk_polygon_clip
 PCLIP_OK, PCLIP_TOUCH, PCLIP_EMPTY, PCLIP_NULL, PCLIP_UNRESOLVED = 0, 1, 2, 3, 4  # the row status of gpk_polygon_clip
+GEODESIC_AREA_SIGNED = 1  # GPK_GEODESIC_AREA_SIGNED
 PUNION_UNION = 0  # GPK_PUNION_*: the mode of gpk_polygon_union (its row status is PCLIP_*)
 PP_INTERIORS, PP_BOUNDARIES, PP_A_OUTSIDE, PP_B_OUTSIDE = 1, 2, 4, 8  # GPK_PP_*: the bits of the polygon x polygon relation mask
 (PP_PRED_INTERSECTS, PP_PRED_WITHIN, PP_PRED_CONTAINS, PP_PRED_TOUCHES, PP_PRED_OVERLAPS, PP_PRED_EQUALS,
@@ -165,6 +166,9 @@ _PROTOS = {
     "gpk_is_ring": (C.c_int32, [_VP, _VP, C.c_int32, _VP]),
     "gpk_point_xy": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_geodesic_length": (C.c_int32, [_VP, C.c_int32, _VP, C.c_int32, _VP]),
+    "gpk_geodesic_area": (C.c_int32, [_VP, C.c_uint32, _VP, _VP, C.c_int32, _VP]),
+    "gpk_geodesic_inverse": (C.c_int32, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP]),
+    "gpk_geodesic_direct": (C.c_int32, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int32, _VP]),
     "gpk_simplify": (C.c_int32, [_VP, C.c_double, _VP, _VP, C.POINTER(C.c_int64), C.c_int32, _VP]),
     "gpk_convex_hull": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),
     "gpk_minimum_rotated_rectangle": (C.c_int32, [_VP, _VP, _VP, C.c_int32, _VP]),

@@ -63,6 +63,7 @@ SOURCES = [
     "gpk_seqedit.hip",
     "gpk_structural.hip",
     "gpk_lineal_ops.hip",
+    "gpk_geodesic.hip",
     "gpk_comm.hip",
 ]
 

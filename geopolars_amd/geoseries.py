@@ -342,6 +342,58 @@ class GeoSeries:
         _abi.check(_abi.lib().gpk_geodesic_length(self.device().handle, m, out.ctypes.data if len(out) else None, MEM_HOST, None))
         return out
 
+    # ---- geodesic measures on WGS84 (gpk_geodesic.hip; geo's GeodesicArea / Distance / Bearing / Destination) -------------------------
+    def _geodesic_area(self, flags: int, want_area: bool) -> np.ndarray:
+        out = np.empty(len(self), dtype=np.float64)
+        if len(out):
+            ptr = out.ctypes.data
+            _abi.check(_abi.lib().gpk_geodesic_area(self.device().handle, flags, ptr if want_area else None, None if want_area else ptr, MEM_HOST, None))
+        return out
+
+    def geodesic_area(self, signed: bool = False) -> np.ndarray:
+        """Area in m^2 on the WGS84 ellipsoid of (lon, lat) polygons whose edges are shortest geodesics (Karney's order-6 series).
+        signed=False: sum over parts of |shell| - sum |hole| (a ring covering more than half the ellipsoid reports its complement);
+        signed=True: the sum of every ring's signed area as stored, counter-clockwise positive, each in (-A0/2, A0/2].  Rings around a
+        pole or across the antimeridian are handled.  Non-polygonal rows: 0; null rows and rows with a latitude outside [-90, 90]: NaN."""
+        return self._geodesic_area(_abi.GEODESIC_AREA_SIGNED if bool_arg("geodesic_area", "signed", signed) else 0, True)
+
+    def geodesic_perimeter(self) -> np.ndarray:
+        """Metres around EVERY ring of every part of a (lon, lat) polygon column, holes included (geodesic_length counts exterior rings
+        only).  Non-polygonal rows: 0; null rows: NaN."""
+        return self._geodesic_area(0, False)
+
+    def _geodesic_inverse(self, op: str, other: "GeoSeries", other_rows, which: int) -> np.ndarray:
+        geodesic_points_arg(op, self, other)
+        rows = distance_rows_arg(op, self, other, other_rows)
+        out = np.empty(len(self), dtype=np.float64)
+        if len(out):
+            ptrs = [None, None, None]
+            ptrs[which] = out.ctypes.data
+            _abi.check(_abi.lib().gpk_geodesic_inverse(self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, *ptrs,
+                                                       MEM_HOST, None))
+        return out
+
+    def geodesic_distance(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
+        """Metres along the WGS84 ellipsoid between the POINT rows of self and other (row i with other[other_rows[i]] when given);
+        coordinates are (lon, lat) degrees.  NaN for a null or empty row, a NaN coordinate or a latitude outside [-90, 90]."""
+        return self._geodesic_inverse("geodesic_distance", other, other_rows, 0)
+
+    def geodesic_bearing(self, other: "GeoSeries", final: bool = False, other_rows=None) -> np.ndarray:
+        """Forward azimuth in degrees clockwise from north, in [-180, 180], of the geodesic from each POINT of self to the POINT of
+        other: at the start (final=False) or on arrival (final=True)."""
+        return self._geodesic_inverse("geodesic_bearing", other, other_rows, 2 if bool_arg("geodesic_bearing", "final", final) else 1)
+
+    def geodesic_destination(self, bearing, distance) -> "GeoSeries":
+        """The POINT column reached from every POINT row along `bearing` (degrees clockwise from north) for `distance` metres on the
+        WGS84 ellipsoid; each is a scalar or one value per row.  Longitudes come back in [-180, 180]; null rows stay null."""
+        geodesic_points_arg("geodesic_destination", self, self)
+        azi, s12 = (geodesic_values_arg("geodesic_destination", name, v, len(self)) for name, v in (("bearing", bearing), ("distance", distance)))
+        out = np.empty((len(self), 2), dtype=np.float64)
+        if len(out):
+            _abi.check(_abi.lib().gpk_geodesic_direct(self.device().handle, azi.ctypes.data, len(azi), s12.ctypes.data, len(s12), out.ctypes.data, None,
+                                                      MEM_HOST, None))
+        return GeoSeries(GeoArrowArray(GEOM_POINT, out, validity=self.array.validity, n_geoms=len(self)))
+
     def simplify(self, tolerance: float) -> "GeoSeries":
         """geoseries.rs:108-116: Douglas-Peucker with geo 0.27's rules (gpk_simplify); the nesting above the coordinate
         sequences is unchanged."""
@@ -1322,6 +1374,65 @@ def bool_arg(op: str, name: str, value) -> bool:
     if not isinstance(value, (bool, np.bool_)):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {name} must be a bool (found {value!r})")
     return bool(value)
+
+
+def geodesic_points_arg(op: str, a: GeoSeries, b: GeoSeries) -> None:
+    """the geodesic point operators take POINT columns; anything else is refused here, before any device call"""
+    for s in (a, b):
+        if s.array.geom_type != GEOM_POINT:
+            raise _mismatch(f"{op}: POINT columns are needed (found {_abi_name(s.array.geom_type)})")
+
+
+def geodesic_values_arg(op: str, name: str, value, n: int) -> np.ndarray:
+    """a bearing / distance argument as a contiguous f64 array of one value or of n; refused here, before any device call, otherwise"""
+    try:
+        v = np.ascontiguousarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {name} must be a number or an array of numbers") from None
+    if v.ndim == 0:
+        v = v.reshape(1)
+    if v.ndim != 1 or len(v) not in (1, n):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {name} holds {v.size} values for {n} rows (one, or one a row)")
+    return v
+
+
+def geodesic_area_device(dev: DeviceGeoArray, out_area=None, out_perimeter=None, signed: bool = False, stream: int = 0) -> None:
+    """Device-buffer variant of geodesic_area / geodesic_perimeter: out_area and out_perimeter (n,) float64 torch CUDA tensors (either
+    may be None) are filled in place on `stream`."""
+    _device_out_args("geodesic_area_device", dev,
+                     lambda n: (("out_area", out_area, (n,), "torch.float64", False), ("out_perimeter", out_perimeter, (n,), "torch.float64", False)))
+    flags = _abi.GEODESIC_AREA_SIGNED if bool_arg("geodesic_area_device", "signed", signed) else 0
+    if dev.n_geoms:
+        _abi.check(_abi.lib().gpk_geodesic_area(dev.handle, flags, None if out_area is None else out_area.data_ptr(),
+                                                None if out_perimeter is None else out_perimeter.data_ptr(), _abi.MEM_DEVICE, stream))
+
+
+def geodesic_inverse_device(dev: DeviceGeoArray, other: DeviceGeoArray, out_distance=None, out_bearing=None, out_final_bearing=None,
+                            stream: int = 0) -> None:
+    """Device-buffer variant of geodesic_distance / geodesic_bearing over two POINT columns of equally many rows: the (n,) float64 torch
+    CUDA tensors given (any may be None) are filled in place on `stream`."""
+    _device_out_args("geodesic_inverse_device", dev,
+                     lambda n: (("out_distance", out_distance, (n,), "torch.float64", False), ("out_bearing", out_bearing, (n,), "torch.float64", False),
+                                ("out_final_bearing", out_final_bearing, (n,), "torch.float64", False)))
+    if not isinstance(other, DeviceGeoArray):
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, "geodesic_inverse_device: a DeviceGeoArray is needed")
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _abi.check(_abi.lib().gpk_geodesic_inverse(dev.handle, other.handle, None, ptr(out_distance), ptr(out_bearing), ptr(out_final_bearing),
+                                               _abi.MEM_DEVICE, stream))
+
+
+def geodesic_destination_device(dev: DeviceGeoArray, bearing, distance, out_xy, out_bearing=None, stream: int = 0) -> None:
+    """Device-buffer variant of geodesic_destination: bearing and distance are float64 torch CUDA tensors of shape (1,) or (n,), out_xy
+    (n, 2) and out_bearing (n,) (optional: the azimuth on arrival) are filled in place on `stream`."""
+    _device_out_args("geodesic_destination_device", dev,
+                     lambda n: (("out_xy", out_xy, (n, 2), "torch.float64", True), ("out_bearing", out_bearing, (n,), "torch.float64", False)))
+    for name, t in (("bearing", bearing), ("distance", distance)):
+        shape = tuple(getattr(t, "shape", ()))
+        if shape not in ((1,), (dev.n_geoms,)) or str(getattr(t, "dtype", None)) != "torch.float64" or not t.is_cuda or not t.is_contiguous():
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT,
+                                         f"geodesic_destination_device: {name} must be a contiguous CUDA float64 tensor of shape (1,) or ({dev.n_geoms},)")
+    _abi.check(_abi.lib().gpk_geodesic_direct(dev.handle, bearing.data_ptr(), bearing.shape[0], distance.data_ptr(), distance.shape[0], out_xy.data_ptr(),
+                                              None if out_bearing is None else out_bearing.data_ptr(), _abi.MEM_DEVICE, stream))
 
 
 TRIANGULATE_STATUS = ("triangulated", "null or empty", "failed")

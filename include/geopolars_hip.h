@@ -353,6 +353,42 @@ int32_t gpk_point_xy(const gpk_geoarray* a, double* out_x, double* out_y, int32_
 #define GPK_GEODESIC_HAVERSINE 1
 #define GPK_GEODESIC_VINCENTY  2
 int32_t gpk_geodesic_length(const gpk_geoarray* a, int32_t method, double* out, int32_t out_space, void* stream);
+/* Geodesic area and perimeter on WGS84 (geo's GeodesicArea: geodesic_area_signed / geodesic_area_unsigned / geodesic_perimeter; Karney's
+ * order-6 area series, csrc/gpk_geodesic.h).  Coordinates are (lon, lat) in degrees; an EDGE is the shortest geodesic between
+ * consecutive ring coordinates as stored (rings are closed in storage; nothing is closed for the caller).
+ *   - A ring's signed area is the area to the LEFT of its direction of travel, reduced to (-A0/2, A0/2], A0 = 510065621724088.5 m^2 the
+ *     area of the ellipsoid: counter-clockwise rings are positive.  The reduction uses the ring's summed prime-meridian transit count
+ *     (an odd count adds -+A0/2), so rings around a pole and rings across the antimeridian come out right.
+ *   - GPK_GEODESIC_AREA_SIGNED: out_area[row] = the sum of the signed areas of ALL its rings as stored; holes wound opposite to their
+ *     shells subtract themselves.
+ *   - without the flag: out_area[row] = sum over parts of (|shell| - sum |hole|), the shell being a part's first ring.  A ring that
+ *     covers MORE THAN HALF the ellipsoid therefore reports its complement: |.| of a value reduced to (-A0/2, A0/2].
+ *   - out_perimeter[row] = the length in metres of every ring of every part, HOLES INCLUDED — not the exterior-only rule of
+ *     gpk_geodesic_length.
+ *   - LINESTRING / MULTILINESTRING / POINT / MULTIPOINT columns give 0 for both; null rows give NaN; a row holding a latitude outside
+ *     [-90, 90] or a NaN coordinate gives NaN.
+ * out_area[n_geoms], out_perimeter[n_geoms] in out_space; either may be NULL (neither: nothing is done).
+ * Unknown flag bits: GPK_ERR_INVALID_ARGUMENT before any device work.  Sums are error-free pairs in a fixed order, without
+ * floating-point atomics: the same bits from run to run.  Stream-ordered (host outputs are copied on the stream and waited for). */
+#define GPK_GEODESIC_AREA_SIGNED 1u
+int32_t gpk_geodesic_area(const gpk_geoarray* a, uint32_t flags, double* out_area, double* out_perimeter, int32_t out_space,
+                          void* stream);
+/* The inverse geodesic problem row by row (geo's GeodesicDistance and GeodesicBearing): a and b are POINT columns of (lon, lat) degrees.
+ *   out_s12[i]   metres between a[i] and b[b_rows ? b_rows[i] : i] along the WGS84 ellipsoid
+ *   out_azi1[i]  forward azimuth at a[i], degrees clockwise from north in [-180, 180]
+ *   out_azi2[i]  forward azimuth at the b point (the direction of arrival carried on), same convention
+ * Any output may be NULL.  `b_rows` (same space as the outputs) follows gpk_distance_rowwise: NULL = identity (the row counts must then
+ * match, else GPK_ERR_INVALID_ARGUMENT); an entry >= n_geoms(b), a null or empty row on either side, a NaN coordinate or a latitude
+ * outside [-90, 90] gives NaN.  Any other family: GPK_ERR_MISMATCHED_GEOMETRY.  Both refusals come before any device work. */
+int32_t gpk_geodesic_inverse(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* b_rows, double* out_s12, double* out_azi1,
+                             double* out_azi2, int32_t out_space, void* stream);
+/* The direct geodesic problem row by row (geo's GeodesicDestination): from the POINT a[i] along azimuth azi1 (degrees clockwise from
+ * north) for s12 metres (negative: backwards).  n_azi and n_s12 are each 1 (one value for every row, not expanded) or n_geoms(a), else
+ * GPK_ERR_INVALID_ARGUMENT; azi1 and s12 live in out_space.  out_xy[2 * n_geoms] interleaved (lon in [-180, 180], lat); out_azi2
+ * (may be NULL) the forward azimuth at the destination.  Null or empty rows, NaN or infinite inputs and latitudes outside [-90, 90]
+ * give NaN.  Any other family: GPK_ERR_MISMATCHED_GEOMETRY.  Both refusals come before any device work. */
+int32_t gpk_geodesic_direct(const gpk_geoarray* a, const double* azi1, int64_t n_azi, const double* s12, int64_t n_s12, double* out_xy,
+                            double* out_azi2, int32_t out_space, void* stream);
 /* simplify (geoseries.rs:108-116,240-242): Ramer-Douglas-Peucker as geo 0.27 runs it (algorithm/simplify.rs): per
  * coordinate sequence (linestring / ring), the farthest point from the chord decides (the LAST one among equals), a
  * range whose farthest point is within `epsilon` loses its interior unless the sequence would drop below 2 (linestrings)
