@@ -1,16 +1,19 @@
-// gpk_geodesic.h — the full geodesic problems on WGS84, host and device: what geo's GeodesicArea,
-// GeodesicDistance, GeodesicBearing and GeodesicDestination compute through geographiclib-rs.
+// gpk_geodesic.h — the geodesic problems on WGS84, host and device: what geo's GeodesicLength, GeodesicArea,
+// GeodesicDistance, GeodesicBearing and GeodesicDestination compute through geographiclib-rs, and the metres between two points by
+// the two other methods of gpk_geodesic_length.
 //   inverse   (lon1, lat1, lon2, lat2) -> s12 [m], azi1, azi2 [degrees, forward, clockwise from north, in [-180, 180]], the reduced
 //             length m12 [m] and S12 [m^2], the area between the edge and the equator (positive when the edge runs east on the
 //             northern side: the S12 of a counter-clockwise ring sum to MINUS its area)
 //   direct    (lon1, lat1, azi1, s12) -> (lon2, lat2, azi2), lon2 in [-180, 180]
 //   transit   the +-1 / 0 prime-meridian crossing count of an edge, for the area reduction of a ring
+//   haversine_m, vincenty_m   (lon1, lat1, lon2, lat2) -> metres, geo's HaversineLength / VincentyLength per segment
 // Restated from the published algorithm (C. F. F. Karney, "Algorithms for geodesics", J. Geodesy 87, 2013, and GeographicLib's
-// order-6 series): the inverse is the one of gpk_karney.h — the same operations in the same order, so s12 has the bits
-// gpk_geodesic_length gives — carried on to the azimuths and to the area integral I4 (the C4 series by Clenshaw summation; for
-// edges that are not long the c^2 (alp2 - alp1) part comes from the spherical-excess formula, which does not cancel).  The
-// direct problem reverts the distance integral with the C1p series.  gpk_karney.h is left as it is: it is __device__ only and
-// the length kernel is timed against it.
+// order-6 series): reduced latitudes, a starting azimuth (spherical, or the astroid solution near the antipode), Newton's method
+// on lambda12(alp1) with bisection as the fallback, then the distance integral by Clenshaw summation, carried on to the azimuths and
+// to the area integral I4 (the C4 series by Clenshaw summation; for edges that are not long the c^2 (alp2 - alp1) part comes from
+// the spherical-excess formula, which does not cancel).  The direct problem reverts the distance integral with the C1p series.
+// This is the library's one inverse: gpk_geodesic_length(GPK_GEODESIC_KARNEY) sums inverse<false>(...).s12 over the segments
+// (gpk_lineal_ops.hip), so gpk_geodesic_inverse and the perimeter give its bits.
 // Plain C++: no HIP type appears here, so a host program can include the file and run the very code the kernels run
 // (tests/geodesic_host_driver.cpp).  Under hipcc every function is __host__ __device__.
 #pragma once
@@ -622,6 +625,49 @@ KQ Direct direct(double lon1, double lat1, double azi1, double s12) {
     r.azi2 = k_atan2d(salp2, calp2);
     if (r.lat2 != r.lat2 || r.lon2 != r.lon2) r.lon2 = r.lat2 = r.azi2 = NAN;
     return r;
+}
+
+/* ---- the two other methods of gpk_geodesic_length: metres between (lon1, lat1) and (lon2, lat2), degrees ------------------------- */
+// geo 0.27 haversine_distance.rs: mean earth radius 6371008.8 m (IUGG), the half-angle formula
+KQ double haversine_m(double lon1, double lat1, double lon2, double lat2) {
+    const double rad = 0.017453292519943295;  // pi / 180 (f64::to_radians multiplies by this constant)
+    const double t1 = lat1 * rad, t2 = lat2 * rad;
+    const double dt = (lat2 - lat1) * rad, dl = (lon2 - lon1) * rad;
+    const double sh = sin(dt / 2.0), sl = sin(dl / 2.0);
+    const double a = sh * sh + cos(t1) * cos(t2) * (sl * sl);
+    return 6371008.8 * (2.0 * asin(sqrt(a)));
+}
+// geo 0.27 vincenty_distance.rs (Vincenty's inverse formula on WGS84, at most 100 iterations, |d lambda| <= 1e-12):
+// NaN where upstream returns Err(FailedToConvergeError) (nearly antipodal points)
+KQ double vincenty_m(double lon1, double lat1, double lon2, double lat2) {
+    const double rad = 0.017453292519943295;
+    const double a = 6378137.0, b = 6356752.314245, f = 1.0 / 298.257223563;
+    const double L = (lon2 - lon1) * rad;
+    const double U1 = atan((1.0 - f) * tan(lat1 * rad)), U2 = atan((1.0 - f) * tan(lat2 * rad));
+    const double sU1 = sin(U1), cU1 = cos(U1), sU2 = sin(U2), cU2 = cos(U2);
+    double lam = L, lam_p, sS = 0, cS = 0, sig = 0, c2A = 0, c2SM = 0;
+    int it = 100;
+    for (;;) {
+        const double sl = sin(lam), cl = cos(lam);
+        const double t0 = cU2 * sl, t1 = cU1 * sU2 - sU1 * cU2 * cl;
+        sS = sqrt(t0 * t0 + t1 * t1);
+        if (sS == 0.0) return (lon1 == lon2 && lat1 == lat2) ? 0.0 : NAN;  // coincident points: 0
+        cS = sU1 * sU2 + cU1 * cU2 * cl;
+        sig = atan2(sS, cS);
+        const double sA = cU1 * cU2 * sl / sS;
+        c2A = 1.0 - sA * sA;
+        c2SM = c2A == 0.0 ? 0.0 : cS - 2.0 * sU1 * sU2 / c2A;  // equatorial line: cos^2 alpha = 0
+        const double C = f / 16.0 * c2A * (4.0 + f * (4.0 - 3.0 * c2A));
+        lam_p = lam;
+        lam = L + (1.0 - C) * f * sA * (sig + C * sS * (c2SM + C * cS * (-1.0 + 2.0 * c2SM * c2SM)));
+        if (fabs(lam - lam_p) <= 1e-12) break;
+        if (--it == 0) return NAN;
+    }
+    const double uSq = c2A * (a * a - b * b) / (b * b);
+    const double A = 1.0 + uSq / 16384.0 * (4096.0 + uSq * (-768.0 + uSq * (320.0 - 175.0 * uSq)));
+    const double B = uSq / 1024.0 * (256.0 + uSq * (-128.0 + uSq * (74.0 - 47.0 * uSq)));
+    const double dS = B * sS * (c2SM + B / 4.0 * (cS * (-1.0 + 2.0 * c2SM * c2SM) - B / 6.0 * c2SM * (-3.0 + 4.0 * sS * sS) * (-3.0 + 4.0 * c2SM * c2SM)));
+    return b * A * (sig - dS);
 }
 
 /* ---- error-free sums: the area of a ring is a sum of terms up to 1e13 m^2 that cancel ------------------------------------------ */

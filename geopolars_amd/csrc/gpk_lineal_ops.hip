@@ -1,6 +1,6 @@
 // gpk_lineal_ops.hip — the two remaining operators of `trait GeoSeries` that walk coordinate sequences:
-//   geodesic_length   geoseries.rs:52-58,216-218   (methods of py-geopolars/src/geo.rs:61-78: geodesic (Karney, gpk_karney.h) |
-//                                                   haversine | vincenty)
+//   geodesic_length   geoseries.rs:52-58,216-218   (methods of py-geopolars/src/geo.rs:61-78: geodesic (Karney) | haversine |
+//                                                   vincenty; the metres between two points are gpk_geodesic.h's, per method)
 //   simplify          geoseries.rs:108-116,240-242  Ramer-Douglas-Peucker, geo 0.27 algorithm/simplify.rs
 // Both follow the upstream crate's published behaviour (the bodies in the reference are todo!()); what each restates is said
 // at the function.  Coordinates are (lon, lat) degrees for the geodesic lengths, like geo's HaversineLength / VincentyLength.
@@ -8,7 +8,7 @@
 #include <cmath>
 
 #include "gpk_device.h"
-#include "gpk_karney.h"
+#include "gpk_geodesic.h"
 #include "gpk_index.h"
 #include "gpk_scan.h"
 
@@ -35,48 +35,7 @@ static void seq_level(const DevGeo& a, const int32_t** off, int64_t* n) {
 }
 
 // ---- geodesic lengths -----------------------------------------------------------------------------------------------
-// geo 0.27 haversine_distance.rs: mean earth radius 6371008.8 m (IUGG), the half-angle formula
-__device__ __forceinline__ double haversine_m(double lon1, double lat1, double lon2, double lat2) {
-    const double rad = 0.017453292519943295;  // pi / 180 (f64::to_radians multiplies by this constant)
-    const double t1 = lat1 * rad, t2 = lat2 * rad;
-    const double dt = (lat2 - lat1) * rad, dl = (lon2 - lon1) * rad;
-    const double sh = sin(dt / 2.0), sl = sin(dl / 2.0);
-    const double a = sh * sh + cos(t1) * cos(t2) * (sl * sl);
-    return 6371008.8 * (2.0 * asin(sqrt(a)));
-}
-// geo 0.27 vincenty_distance.rs (Vincenty's inverse formula on WGS84, at most 100 iterations, |d lambda| <= 1e-12):
-// NaN where upstream returns Err(FailedToConvergeError) (nearly antipodal points)
-__device__ inline double vincenty_m(double lon1, double lat1, double lon2, double lat2) {
-    const double rad = 0.017453292519943295;
-    const double a = 6378137.0, b = 6356752.314245, f = 1.0 / 298.257223563;
-    const double L = (lon2 - lon1) * rad;
-    const double U1 = atan((1.0 - f) * tan(lat1 * rad)), U2 = atan((1.0 - f) * tan(lat2 * rad));
-    const double sU1 = sin(U1), cU1 = cos(U1), sU2 = sin(U2), cU2 = cos(U2);
-    double lam = L, lam_p, sS = 0, cS = 0, sig = 0, c2A = 0, c2SM = 0;
-    int it = 100;
-    for (;;) {
-        const double sl = sin(lam), cl = cos(lam);
-        const double t0 = cU2 * sl, t1 = cU1 * sU2 - sU1 * cU2 * cl;
-        sS = sqrt(t0 * t0 + t1 * t1);
-        if (sS == 0.0) return (lon1 == lon2 && lat1 == lat2) ? 0.0 : NAN;  // coincident points: 0
-        cS = sU1 * sU2 + cU1 * cU2 * cl;
-        sig = atan2(sS, cS);
-        const double sA = cU1 * cU2 * sl / sS;
-        c2A = 1.0 - sA * sA;
-        c2SM = c2A == 0.0 ? 0.0 : cS - 2.0 * sU1 * sU2 / c2A;  // equatorial line: cos^2 alpha = 0
-        const double C = f / 16.0 * c2A * (4.0 + f * (4.0 - 3.0 * c2A));
-        lam_p = lam;
-        lam = L + (1.0 - C) * f * sA * (sig + C * sS * (c2SM + C * cS * (-1.0 + 2.0 * c2SM * c2SM)));
-        if (fabs(lam - lam_p) <= 1e-12) break;
-        if (--it == 0) return NAN;
-    }
-    const double uSq = c2A * (a * a - b * b) / (b * b);
-    const double A = 1.0 + uSq / 16384.0 * (4096.0 + uSq * (-768.0 + uSq * (320.0 - 175.0 * uSq)));
-    const double B = uSq / 1024.0 * (256.0 + uSq * (-128.0 + uSq * (74.0 - 47.0 * uSq)));
-    const double dS = B * sS * (c2SM + B / 4.0 * (cS * (-1.0 + 2.0 * c2SM * c2SM) - B / 6.0 * c2SM * (-3.0 + 4.0 * sS * sS) * (-3.0 + 4.0 * c2SM * c2SM)));
-    return b * A * (sig - dS);
-}
-
+// A segment's metres are geodesic::inverse, haversine_m or vincenty_m of gpk_geodesic.h, by METHOD.
 // G lanes per sequence: lane k takes segments k, k + G, ...; the partial sums fold with DPP row operations
 template <int G, int METHOD>
 __global__ __launch_bounds__(256) void geodesic_seq_kernel(const double2* __restrict__ xy, const int32_t* __restrict__ seq_off, int64_t n_seq,
@@ -88,9 +47,9 @@ __global__ __launch_bounds__(256) void geodesic_seq_kernel(const double2* __rest
         double v = 0.0;
         for (int i = c0 + lane; i + 1 < c1; i += G) {
             const double2 p = xy[i], q = xy[i + 1];
-            v += METHOD == GPK_GEODESIC_HAVERSINE ? haversine_m(p.x, p.y, q.x, q.y)
-                 : METHOD == GPK_GEODESIC_VINCENTY ? vincenty_m(p.x, p.y, q.x, q.y)
-                                                   : karney::k_geodesic_m(p.x, p.y, q.x, q.y);
+            v += METHOD == GPK_GEODESIC_HAVERSINE ? geodesic::haversine_m(p.x, p.y, q.x, q.y)
+                 : METHOD == GPK_GEODESIC_VINCENTY ? geodesic::vincenty_m(p.x, p.y, q.x, q.y)
+                                                   : geodesic::inverse<false>(p.x, p.y, q.x, q.y).s12;
         }
         v = dev::group_sum<G>(v);
         if (lane == 0) seq_len[s] = v;

@@ -334,7 +334,8 @@ class GeoSeries:
 
     def geodesic_length(self, method: str = "geodesic") -> np.ndarray:
         """geoseries.rs:52-58 / georust/geoseries.py: metres, coordinates in (lon, lat) degrees; all three methods run on the
-        GPU — 'geodesic' (the default) is Karney's algorithm (csrc/gpk_karney.h), as in geo's GeodesicLength."""
+        GPU — 'geodesic' (the default) is Karney's algorithm, as in geo's GeodesicLength: the inverse of csrc/gpk_geodesic.h, which
+        geodesic_distance runs too (the same bits); that header also holds the haversine and Vincenty formulas."""
         m = self.GEODESIC_METHODS.get(method.lower())
         if m is None:
             raise ValueError("Geodesic calculation method not valid. Use one of geodesic, haversine or vincenty")  # geo.rs:68-71

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE (like everything under oracle/): an INDEPENDENT solution of the geodesic inverse problem on WGS84, used to
-arbitrate between the HIP kernel (geopolars_amd/csrc/gpk_karney.h) and the C restatement (oracle/gpk_oracle.c), which are the same
+arbitrate between the library's inverse (geopolars_amd/csrc/gpk_geodesic.h) and the C restatement (oracle/gpk_oracle.c), which are the same
 algorithm written twice — Karney's series expansions with his Newton iteration (geographiclib-rs, what geo 0.27's
 GeodesicLength / `georust/geoseries.py:128-146`, `py-geopolars/src/geo.rs:61-78` call).
 

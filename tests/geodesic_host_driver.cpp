@@ -4,7 +4,8 @@
 // in.bin   int64 n_edges, n_direct, n_rings, n_ring_coords; edge_xy[n_edges][4]; edge_expected[n_edges][5] (s12, azi1, azi2, m12, S12);
 //          edge_regime[n_edges] (int32); direct_in[n_direct][4]; direct_expected[n_direct][3]; ring_off[n_rings + 1] (int32);
 //          ring_regime[n_rings] (int32); ring_xy[n_ring_coords][2]; ring_expected[n_rings][2] (signed area, perimeter)
-// out.bin  edges[n_edges][5]; direct[n_direct][3]; rings[n_rings][2] — what the header computed
+// out.bin  edges[n_edges][7] (s12, azi1, azi2, m12, S12, then the haversine and the Vincenty metres of the same edge); direct[n_direct][3];
+//          rings[n_rings][2] — what the header computed
 // stdout   the worst error per regime: distances in metres, azimuths as |d azi| * |m12| in metres, areas in m^2 (per edge for rings)
 #include <algorithm>
 #include <cmath>
@@ -36,15 +37,16 @@ int main(int argc, char** argv) {
         !read_n(f, roff, nr + 1) || !read_n(f, rreg, nr) || !read_n(f, rxy, 2 * nc) || !read_n(f, rexp, 2 * nr))
         return 5;
     fclose(f);
-    std::vector<double> eout(5 * ne), dout(3 * nd), rout(2 * nr);
+    std::vector<double> eout(7 * ne), dout(3 * nd), rout(2 * nr);
     constexpr int MAXREG = 16;
     double w_s[MAXREG] = {0}, w_azi[MAXREG] = {0}, w_S[MAXREG] = {0}, w_plain[MAXREG] = {0};
     for (size_t i = 0; i < ne; ++i) {
         const double* p = &exy[4 * i];
         const geo::Inverse r = geo::inverse<true>(p[0], p[1], p[2], p[3]);
         const geo::Inverse r0 = geo::inverse<false>(p[0], p[1], p[2], p[3]);
-        double* o = &eout[5 * i];
+        double* o = &eout[7 * i];
         o[0] = r.s12, o[1] = r.azi1, o[2] = r.azi2, o[3] = r.m12, o[4] = r.S12;
+        o[5] = geo::haversine_m(p[0], p[1], p[2], p[3]), o[6] = geo::vincenty_m(p[0], p[1], p[2], p[3]);
         const double* x = &eexp[5 * i];
         const int k = ereg[i] & (MAXREG - 1);
         w_s[k] = std::max(w_s[k], std::fabs(r.s12 - x[0]) / (1e-9 * std::fabs(x[0]) + 2e-8));  // in units of the project's Karney bound

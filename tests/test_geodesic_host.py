@@ -118,8 +118,9 @@ def run_driver(exe, workdir, fx):
     r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     raw = np.fromfile(fout, dtype=np.float64)
-    assert len(raw) == 5 * ne + 3 * nd + 2 * nr
-    return raw[: 5 * ne].reshape(ne, 5), raw[5 * ne: 5 * ne + 3 * nd].reshape(nd, 3), raw[5 * ne + 3 * nd:].reshape(nr, 2), r.stdout
+    assert len(raw) == 7 * ne + 3 * nd + 2 * nr
+    # an edge's record: s12, azi1, azi2, m12, S12 of inverse<true>, then haversine_m and vincenty_m of the same edge
+    return raw[: 7 * ne].reshape(ne, 7), raw[7 * ne: 7 * ne + 3 * nd].reshape(nd, 3), raw[7 * ne + 3 * nd:].reshape(nr, 2), r.stdout
 
 
 @pytest.fixture(scope="module")
@@ -127,10 +128,17 @@ def fixture():
     return R.load_fixture(FIXTURE)
 
 
+def same_bits(got, want):
+    """the same NaN positions, and the same bits everywhere else"""
+    nan = np.isnan(want)
+    return np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan].view(np.uint64), want[~nan].view(np.uint64))
+
+
 @pytest.mark.parametrize("build", ["plain", "sanitized"])
-def test_host_driver_against_the_fixture(drivers, fixture, build):
+def test_host_driver_against_the_fixture(drivers, fixture, oracle, build):
     """the header on the CPU against the mp fixture, every regime, within the MEASURED tolerances (no GPU_FACTOR here); the driver prints
-    the worst error per regime"""
+    the worst error per regime.  The three length functions of gpk_geodesic_length (inverse's s12, haversine_m, vincenty_m) are the
+    operations of oracle/gpk_oracle.c in the same order: on the host they give its bits, edge by edge"""
     built, workdir = drivers
     edges, direct, rings, text = run_driver(built[build], workdir, fixture)
     print(text)
@@ -138,10 +146,19 @@ def test_host_driver_against_the_fixture(drivers, fixture, build):
     R.check_direct(fixture, direct[:, :2], direct[:, 2], factor=1)
     R.check_rings(fixture, rings[:, 0], rings[:, 1], factor=1)
     assert "differs: 1" not in text  # inverse<false> gives the distance and azimuths of inverse<true>, bit for bit
+    n = len(fixture["edge_xy"])
+    lines = GeoArrowArray(_abi.GEOM_LINESTRING, np.ascontiguousarray(fixture["edge_xy"], dtype=np.float64).reshape(2 * n, 2),
+                          geom_offsets=np.arange(0, 2 * n + 1, 2, dtype=np.int32))
+    for column, method in ((0, "geodesic"), (5, "haversine"), (6, "vincenty")):
+        want = oracle.geodesic_length(lines, method)
+        assert same_bits(np.ascontiguousarray(edges[:, column]), want), method
+        assert method != "vincenty" or 0 < np.isnan(want).sum() < n  # the fixture has edges Vincenty's iteration gives up on
 
 
-def test_host_driver_refusals_and_reduction(drivers):
-    """NaN and out-of-range latitudes give NaN in every field; the transit count and the area reduction on hand-made rings"""
+def test_host_driver_refusals_and_reduction(drivers, oracle):
+    """NaN and out-of-range latitudes give NaN in every field; the transit count and the area reduction on hand-made rings.  The length
+    functions on the same edges: NaN for a NaN coordinate and zero for identical points like inverse; haversine and Vincenty, like geo's,
+    do not look at the latitude's range, so there they are held to the oracle's bits instead"""
     built, workdir = drivers
     nan = np.nan
     fx = {"edge_xy": np.array([[0.0, 90.0001, 1.0, 0.0], [0.0, 0.0, 1.0, -91.0], [nan, 0.0, 1.0, 1.0], [0.0, 0.0, 1.0, nan], [5.0, 5.0, 5.0, 5.0]]),
@@ -154,9 +171,13 @@ def test_host_driver_refusals_and_reduction(drivers):
     fx.update(edge_s12=np.zeros(n), edge_azi1=np.zeros(n), edge_azi2=np.zeros(n), edge_m12=np.zeros(n, dtype=np.float32), edge_S12=np.zeros(n),
               edge_regime=np.zeros(n, dtype=np.int32), direct_out=np.zeros((m, 3)), ring_regime=np.zeros(2, dtype=np.int32), ring_area=np.zeros(2),
               ring_perimeter=np.zeros(2))
+    lines = GeoArrowArray(_abi.GEOM_LINESTRING, fx["edge_xy"].reshape(2 * n, 2), geom_offsets=np.arange(0, 2 * n + 1, 2, dtype=np.int32))
     for exe in built.values():
         edges, direct, rings, _ = run_driver(exe, workdir, fx)
-        assert np.isnan(edges[:4]).all() and np.array_equal(edges[4, [0, 3, 4]], [0.0, 0.0, 0.0])
+        assert np.isnan(edges[:4, :5]).all() and np.array_equal(edges[4, [0, 3, 4]], [0.0, 0.0, 0.0])
+        assert np.isnan(edges[2:4, 5:]).all() and np.array_equal(edges[4, 5:], [0.0, 0.0])
+        for column, method in ((0, "geodesic"), (5, "haversine"), (6, "vincenty")):
+            assert same_bits(np.ascontiguousarray(edges[:, column]), oracle.geodesic_length(lines, method)), method
         assert np.isnan(direct[:4]).all()
         assert -180.0 <= direct[4, 0] < -178.0 and abs(direct[4, 1]) < 1e-9  # across the antimeridian: wrapped
         assert np.abs(direct[5] - [12.0, 34.0, 56.0]).max() < 1e-12  # no distance: the point itself

@@ -41,6 +41,27 @@ def test_inverse_fixture_edges(gpk, fx):
     assert np.array_equal(out, np.stack([s12, azi1, azi2]))
 
 
+def test_geodesic_length_and_distance_are_one_inverse(gpk, fx):
+    """geodesic_length("geodesic") of two-point linestrings and geodesic_distance of the same end points run the same inverse
+    (csrc/gpk_geodesic.h): the same bits and the same NaN rows, on the fixture's edges and on the hand-made ones"""
+    nan = np.nan
+    hand = np.array([[12.5, -33.25, 12.5, -33.25],  # identical points
+                     [0.0, 90.0, 0.0, -90.0],  # pole to pole
+                     [0.0, 0.0, 179.5, 0.5],  # Karney 2013's nearly antipodal pair
+                     [0.0, 0.0, 180.0, 0.0],  # antipodal on the equator
+                     [0.0, 90.0001, 1.0, 0.0],  # a latitude out of range
+                     [nan, 0.0, 1.0, 1.0]])  # a NaN coordinate
+    e = np.concatenate([fx["edge_xy"], hand])
+    n = len(e)
+    lines = GeoSeries(GeoArrowArray(_abi.GEOM_LINESTRING, np.ascontiguousarray(e).reshape(2 * n, 2), geom_offsets=np.arange(0, 2 * n + 1, 2, dtype=np.int32)))
+    length = lines.geodesic_length("geodesic")
+    s12 = points(e[:, :2]).geodesic_distance(points(e[:, 2:]))
+    bad = np.isnan(length)
+    assert np.array_equal(np.isnan(s12), bad) and np.array_equal(np.flatnonzero(bad), [n - 2, n - 1])
+    assert np.array_equal(length[~bad].view(np.uint64), s12[~bad].view(np.uint64))
+    assert length[n - 6] == 0.0 and np.all(length[n - 5:n - 2] > 1.99e7)
+
+
 def test_direct_fixture_and_round_trip(gpk, fx):
     din = fx["direct_in"]
     a = points(din[:, :2])

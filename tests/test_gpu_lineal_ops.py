@@ -50,7 +50,7 @@ def _pairs_as_lines(l1, p1, l2, p2):
 
 
 def test_karney_kernel_against_an_independent_solver(gpk):
-    """the HIP kernel (csrc/gpk_karney.h) against oracle/geodesic_quadrature.py — Bessel's reduction evaluated by Gauss-Legendre
+    """the HIP kernel (the inverse of csrc/gpk_geodesic.h) against oracle/geodesic_quadrature.py — Bessel's reduction evaluated by Gauss-Legendre
     quadrature, the azimuth found by bisection: no series, no Newton step, nothing shared with the kernel or with the C oracle
     (which is the kernel's algorithm written a second time).  Random pairs over the whole ellipsoid, nearly antipodal pairs at
     three scales, short lines, meridians, the equator, the poles."""
