@@ -62,6 +62,11 @@ def _ring_usable(r) -> bool:
 
 
 def _int_ring(r):
+    """integer coordinates as int64; Python ints that a double cannot hold stay Python ints (object dtype): that is how rows of
+    arbitrary doubles arrive, brought to one integer grid by an exact power of two (tests/hard_orient.on_integer_grid)"""
+    flat = [v for p in r for v in p]
+    if flat and all(isinstance(v, int) for v in flat) and max(abs(v) for v in flat) >= 2**53:
+        return np.array([[int(x), int(y)] for x, y in r], dtype=object).reshape(-1, 2)
     a = np.asarray(r, dtype=np.float64).reshape(-1, 2)
     assert (a == np.round(a)).all(), "the reference works on integer coordinates"
     return a.astype(np.int64)
@@ -101,8 +106,9 @@ def _positions(points, polys):
 def sample_points(seqs, polys):
     """every coordinate, cut point and piece midpoint of the line's sequences (integer) against the polygons' rings"""
     edges = E._edges([r for p in polys for r in p])
-    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
-    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
+    dt = object if any(abs(v) >= 2**62 for e in edges for p in e for v in p) else np.int64
+    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=dt).reshape(-1, 2)
+    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=dt).reshape(-1, 2)
     pts = []
     for s in seqs:
         c = [(int(x), int(y)) for x, y in s]
