@@ -126,6 +126,15 @@ class GeoSeries:
             self._dev = DeviceGeoArray.upload(self.array)
         return self._dev
 
+    @staticmethod
+    def _rowwise(entry: str, a: "GeoSeries", b: "GeoSeries", rows: Optional[np.ndarray], out: np.ndarray, *mid) -> np.ndarray:
+        """One row-wise call of the C ABI, entry(a, b, b_rows, *mid, out, MEM_HOST, stream), that fills `out` with one value per row; an
+        empty column makes no call.  The callers have checked families and row pairing (the *_args functions below) before."""
+        if len(out):
+            _abi.check(getattr(_abi.lib(), entry)(a.device().handle, b.device().handle, None if rows is None else rows.ctypes.data, *mid,
+                                                  out.ctypes.data, MEM_HOST, None))
+        return out
+
     # ---- structural operators (gpk_structural.hip: maps over rows / offset surgery on the device) ---------------
     def _row_map(self, fn, dtype) -> np.ndarray:
         out = np.empty(len(self), dtype=dtype)
@@ -488,9 +497,7 @@ class GeoSeries:
             return out
         n = len(self) if self.array.geom_type == GEOM_POINT or other_rows is not None else len(other)
         out = np.empty(n, dtype=np.float64)
-        rows = None
-        if other_rows is not None:
-            rows = np.ascontiguousarray(other_rows, dtype=np.uint32)
+        rows = None if other_rows is None else row_map_arg("distance", other_rows, len(self))
         _abi.check(
             _abi.lib().gpk_distance_rowwise(
                 self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
@@ -505,15 +512,7 @@ class GeoSeries:
         row; identical rows give exactly 0.0; hausdorff_distance(a, b) and (b, a) are the same doubles."""
         k = densify_arg("hausdorff_distance", densify)
         rows = distance_rows_arg("hausdorff_distance", self, other, other_rows)
-        out = np.empty(len(self), dtype=np.float64)
-        if len(out) == 0:
-            return out
-        _abi.check(
-            _abi.lib().gpk_hausdorff_distance(
-                self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, k, out.ctypes.data, MEM_HOST, None
-            )
-        )
-        return out
+        return self._rowwise("gpk_hausdorff_distance", self, other, rows, np.empty(len(self), dtype=np.float64), k)
 
     def frechet_distance(self, other: "GeoSeries", densify=None, other_rows=None, errors: str = "raise") -> np.ndarray:
         """GeoPandas' GeoSeries.frechet_distance: the discrete Frechet distance of row i and other[other_rows[i]] over the samples that
@@ -545,7 +544,7 @@ class GeoSeries:
 
     def _predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         out = np.empty(len(self), dtype=np.uint8)
-        rows = None if other_rows is None else np.ascontiguousarray(other_rows, dtype=np.uint32)
+        rows = None if other_rows is None else row_map_arg(name, other_rows, len(self))
         _abi.check(
             _abi.lib().gpk_predicate_rowwise(
                 self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, PREDICATES[name], out.ctypes.data, MEM_HOST, None
@@ -568,7 +567,7 @@ class GeoSeries:
         Every pair of families (gpk_dwithin_rowwise); `distance` must be finite and >= 0."""
         d = dwithin_distance_arg(distance)
         out = np.empty(len(self), dtype=np.uint8)
-        rows = None if other_rows is None else np.ascontiguousarray(other_rows, dtype=np.uint32)
+        rows = None if other_rows is None else row_map_arg("dwithin", other_rows, len(self))
         _abi.check(
             _abi.lib().gpk_dwithin_rowwise(
                 self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, d, out.ctypes.data, MEM_HOST, None
@@ -585,14 +584,7 @@ class GeoSeries:
         line_first = relation_sides("line_polygon_relation", self._family(), other._family())
         rows = relation_rows_arg("line_polygon_relation", self, other, other_rows, line_first)
         lines, polys = (self, other) if line_first else (other, self)
-        out = np.empty(len(lines), dtype=np.uint8)
-        if len(out):
-            _abi.check(
-                _abi.lib().gpk_line_polygon_relation(
-                    lines.device().handle, polys.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
-                )
-            )
-        return out
+        return self._rowwise("gpk_line_polygon_relation", lines, polys, rows, np.empty(len(lines), dtype=np.uint8))
 
     def _relation(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         a, b = self._family(), other._family()
@@ -633,14 +625,7 @@ class GeoSeries:
         a point outside B, 8 — B's interior has a point outside A; 0 for a null or empty row or an invalid ring on either side.  Both
         columns are POLYGON / MULTIPOLYGON.  crosses, touches, covers, covered_by and disjoint take two such columns too."""
         rows = polygon_relation_args("polygon_relation", self, other, other_rows)
-        out = np.empty(len(self), dtype=np.uint8)
-        if len(out):
-            _abi.check(
-                _abi.lib().gpk_polygon_relation(
-                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
-                )
-            )
-        return out
+        return self._rowwise("gpk_polygon_relation", self, other, rows, np.empty(len(self), dtype=np.uint8))
 
     def _polygon_relation(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         a, b = self._family(), other._family()
@@ -664,14 +649,7 @@ class GeoSeries:
     # ---- intersection area and length (gpk_overlay.hip) ------------------------------------------
     def _intersection_measure(self, op: str, first, other: "GeoSeries", other_rows) -> np.ndarray:
         rows = intersection_measure_args(op, first, self, other, other_rows)
-        out = np.empty(len(self), dtype=np.float64)
-        if len(out):
-            _abi.check(
-                _abi.lib().gpk_intersection_measure(
-                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
-                )
-            )
-        return out
+        return self._rowwise("gpk_intersection_measure", self, other, rows, np.empty(len(self), dtype=np.float64))
 
     def intersection_area(self, other: "GeoSeries", other_rows=None) -> np.ndarray:
         """The area (float64) every row's polygon shares with its polygon other[other_rows[i]] (gpk_intersection_measure), without
@@ -856,14 +834,7 @@ class GeoSeries:
         coordinate.  Both columns are LINESTRING / MULTILINESTRING.  The named methods (crosses, touches, ...) do not take two lineal
         columns: line_predicate does."""
         rows = line_relation_args("line_relation", self, other, other_rows)
-        out = np.empty(len(self), dtype=np.uint8)
-        if len(out):
-            _abi.check(
-                _abi.lib().gpk_line_relation(
-                    self.device().handle, other.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
-                )
-            )
-        return out
+        return self._rowwise("gpk_line_relation", self, other, rows, np.empty(len(self), dtype=np.uint8))
 
     def line_predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         """a named line / line predicate (LINE_MASK_PREDICATES: intersects, disjoint, touches, crosses, overlaps, within, contains,
@@ -882,14 +853,7 @@ class GeoSeries:
         points_first = point_relation_sides("point_relation", self._family(), other._family())
         rows = point_relation_rows_arg("point_relation", self, other, other_rows, points_first)
         points, geoms = (self, other) if points_first else (other, self)
-        out = np.empty(len(points), dtype=np.uint8)
-        if len(out):
-            _abi.check(
-                _abi.lib().gpk_point_relation(
-                    points.device().handle, geoms.device().handle, None if rows is None else rows.ctypes.data, out.ctypes.data, MEM_HOST, None
-                )
-            )
-        return out
+        return self._rowwise("gpk_point_relation", points, geoms, rows, np.empty(len(points), dtype=np.uint8))
 
     def point_predicate(self, other: "GeoSeries", name: str, other_rows=None) -> np.ndarray:
         """a named predicate "self[i] NAME other[i]" with a POINT / MULTIPOINT column on either side (POINT_MASK_PREDICATES: intersects,
@@ -1026,14 +990,7 @@ class GeoSeries:
         fraction of the line's length with `normalized`.  A MULTILINESTRING's members are measured one after the other.  NaN for
         null and empty rows and NaN points."""
         r = linref_args("project", other, self, rows, lineal_only=True)
-        out = np.empty(len(other), dtype=np.float64)
-        if len(out):
-            _abi.check(
-                _abi.lib().gpk_line_locate_point(
-                    other.device().handle, self.device().handle, None if r is None else r.ctypes.data, int(bool(normalized)), out.ctypes.data, MEM_HOST, None
-                )
-            )
-        return out
+        return self._rowwise("gpk_line_locate_point", other, self, r, np.empty(len(other), dtype=np.float64), int(bool(normalized)))
 
     def interpolate(self, distance, normalized: bool = False) -> "GeoSeries":
         """GeoPandas' GeoSeries.interpolate / geo's LineInterpolatePoint: the point at `distance` (a number, or one per row) along each
@@ -1064,17 +1021,41 @@ def linref_args(op: str, points: GeoSeries, other: GeoSeries, rows, lineal_only:
         raise _mismatch(f"{op}: the point side must be POINT (found {_abi_name(points._family())})")
     if lineal_only and other._family() not in (GEOM_LINESTRING, GEOM_MULTILINESTRING):
         raise _mismatch(f"{op}: expected LineString or MultiLineString (found {_abi_name(other._family())})")
-    if rows is None:
-        if len(points) != len(other):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(points)} vs {len(other)})")
-        return None
+    return paired_rows_arg(op, points, other, rows, "points")
+
+
+def row_map_arg(op: str, rows, n: int, what: str = "rows") -> np.ndarray:
+    """a caller's row map as the library gets it: a contiguous 1-D uint32 array of `n` row numbers, one per row (`what`: the noun of the
+    message) of the mapped side; anything else is refused here, before any device call"""
     try:
         r = np.ascontiguousarray(rows, dtype=np.uint32)
     except (TypeError, ValueError, OverflowError):
         raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-    if r.ndim != 1 or len(r) != len(points):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(points)} points")
+    if r.ndim != 1 or len(r) != n:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {n} {what}")
     return r
+
+
+def paired_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows, what: str = "rows") -> Optional[np.ndarray]:
+    """the row pairing of a row-wise operator before any device call: without a row map the row counts match (None); a row map has one
+    entry per row of `a` (row_map_arg)"""
+    if rows is None:
+        if len(a) != len(b):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
+        return None
+    return row_map_arg(op, rows, len(a), what)
+
+
+def either_order_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows, mapped_first: bool, needs: str) -> Optional[np.ndarray]:
+    """the row pairing of a relation that takes its two families in either order: as paired_rows_arg, but a row map needs the side it
+    maps from on the left (`mapped_first`) unless it is the identity, which then counts as no map; `needs` says so in the refusal"""
+    if rows is not None:
+        r = row_map_arg(op, rows, len(a))
+        if mapped_first:
+            return r
+        if not np.array_equal(r, np.arange(len(a), dtype=np.uint32)):
+            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {needs}")
+    return paired_rows_arg(op, a, b, None)
 
 
 def interpolate_distance_arg(lines: GeoSeries, distance) -> np.ndarray:
@@ -1162,17 +1143,7 @@ def line_relation_args(op: str, a: "GeoSeries", b: "GeoSeries", rows) -> Optiona
     fa, fb = a._family(), b._family()
     if fa not in LINEAL or fb not in LINEAL:
         raise _mismatch(f"{op}: LineString | MultiLineString x LineString | MultiLineString (found {_abi_name(fa)} x {_abi_name(fb)})")
-    if rows is not None:
-        try:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-        except (TypeError, ValueError, OverflowError):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-        if r.ndim != 1 or len(r) != len(a):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
-        return r
-    if len(a) != len(b):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
-    return None
+    return paired_rows_arg(op, a, b, rows)
 
 
 PUNCTUAL = (GEOM_POINT, GEOM_MULTIPOINT)
@@ -1237,20 +1208,7 @@ def point_relation_sides(op: str, a: int, b: int) -> bool:
 def point_relation_rows_arg(op: str, a: "GeoSeries", b: "GeoSeries", rows, points_first: bool) -> Optional[np.ndarray]:
     """the checks of point_relation before any device call: without a row map the row counts match; a row map (returned as uint32) has
     one entry per row of `a` and needs `a` to be the punctual side unless it is the identity"""
-    if rows is not None:
-        try:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-        except (TypeError, ValueError, OverflowError):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-        if r.ndim != 1 or len(r) != len(a):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
-        if points_first:
-            return r
-        if not np.array_equal(r, np.arange(len(a), dtype=np.uint32)):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: a row map needs the punctual column on the left (it maps point rows to rows of the other column)")
-    if len(a) != len(b):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
-    return None
+    return either_order_rows_arg(op, a, b, rows, points_first, "a row map needs the punctual column on the left (it maps point rows to rows of the other column)")
 
 
 def predicate_route(a: int, b: int):
@@ -1490,17 +1448,7 @@ def polygon_relation_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional
     fa, fb = a._family(), b._family()
     if fa not in POLYGONAL or fb not in POLYGONAL:
         raise _mismatch(f"{op}: Polygon | MultiPolygon x Polygon | MultiPolygon (found {_abi_name(fa)} x {_abi_name(fb)})")
-    if rows is not None:
-        try:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-        except (TypeError, ValueError, OverflowError):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-        if r.ndim != 1 or len(r) != len(a):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
-        return r
-    if len(a) != len(b):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
-    return None
+    return paired_rows_arg(op, a, b, rows)
 
 
 def intersection_measure_args(op: str, first, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
@@ -1512,17 +1460,7 @@ def intersection_measure_args(op: str, first, a: GeoSeries, b: GeoSeries, rows) 
         want = "Polygon | MultiPolygon" if first is POLYGONAL else "LineString | MultiLineString"
         swap = ": the lines come first, swap the arguments" if first is LINEAL and fa in POLYGONAL and fb in LINEAL else ""
         raise _mismatch(f"{op}: {want} x Polygon | MultiPolygon (found {_abi_name(fa)} x {_abi_name(fb)}){swap}")
-    if rows is not None:
-        try:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-        except (TypeError, ValueError, OverflowError):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-        if r.ndim != 1 or len(r) != len(a):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
-        return r
-    if len(a) != len(b):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
-    return None
+    return paired_rows_arg(op, a, b, rows)
 
 
 def line_clip_args(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
@@ -1678,20 +1616,7 @@ def relation_sides(op: str, a: int, b: int) -> bool:
 def relation_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows, line_first: bool) -> Optional[np.ndarray]:
     """the checks of line_polygon_relation before any device call: without a row map the row counts match; a row map (returned as
     uint32) has one entry per row of `a` and needs `a` to be the lineal side unless it is the identity"""
-    if rows is not None:
-        try:
-            r = np.ascontiguousarray(rows, dtype=np.uint32)
-        except (TypeError, ValueError, OverflowError):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-        if r.ndim != 1 or len(r) != len(a):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
-        if line_first:
-            return r
-        if not np.array_equal(r, np.arange(len(a), dtype=np.uint32)):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: a row map needs the lineal column on the left (it maps line rows to polygon rows)")
-    if len(a) != len(b):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
-    return None
+    return either_order_rows_arg(op, a, b, rows, line_first, "a row map needs the lineal column on the left (it maps line rows to polygon rows)")
 
 
 FRECHET_MAX_SHORT = 16384  # GPK_FRECHET_MAX_SHORT of include/geopolars_hip.h
@@ -1719,17 +1644,7 @@ def densify_arg(op: str, densify) -> int:
 def distance_rows_arg(op: str, a: GeoSeries, b: GeoSeries, rows) -> Optional[np.ndarray]:
     """the row pairing of hausdorff_distance / frechet_distance before any device call: without a row map the row counts match; a row
     map (returned as uint32) has one entry per row of `a`"""
-    if rows is None:
-        if len(a) != len(b):
-            raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: row counts differ ({len(a)} vs {len(b)})")
-        return None
-    try:
-        r = np.ascontiguousarray(rows, dtype=np.uint32)
-    except (TypeError, ValueError, OverflowError):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: the row map must be an array of row numbers") from None
-    if r.ndim != 1 or len(r) != len(a):
-        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT, f"{op}: {r.size} row numbers for {len(a)} rows")
-    return r
+    return paired_rows_arg(op, a, b, rows)
 
 
 def dwithin_distance_arg(distance) -> float:

@@ -3,7 +3,6 @@ kernel's own math (csrc/gpk_crs.h) run on the CPU by a stand-alone program again
 AddressSanitizer + UBSan."""
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -14,6 +13,7 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries, crs_supported, parse_crs, utm_crs_of_bounds
 from tests import crs_ref as R
+from tests.host_build import build_host_drivers, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -45,14 +45,6 @@ def test_unsupported_code_is_refused_by_the_library_before_any_device_work():
         rc = lib.gpk_reproject(None, src, dst, None, None, _abi.MEM_HOST, None)  # not even a handle: the codes are looked at first
         assert rc == _abi.GPK_ERR_INVALID_ARGUMENT
         assert f"EPSG:{named}" in _abi.last_error()
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def test_crs_argument_forms():
@@ -109,34 +101,9 @@ def test_estimate_utm_crs_refuses_what_is_not_lon_lat():
 
 
 # ---- the kernel's math on the CPU --------------------------------------------------------------------------------------------------
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/crs_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("crs_driver")
-    src = os.path.join(HERE, "crs_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"crs_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "crs", fp_contract_off=True)
 
 
 def _run_driver(exe, workdir, jobs):

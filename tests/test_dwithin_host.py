@@ -2,7 +2,6 @@
 checks that refuse a call before the library is opened."""
 import math
 import os
-import subprocess
 
 import pytest
 
@@ -10,6 +9,7 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries, dwithin_distance_arg
 from geopolars_amd.spatial_index import SpatialJoinDWithinArgs, dwithin_pairs, dwithin_pairs_device, spatial_join_dwithin
+from tests.host_build import exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 
 def test_exported_symbols_name_the_dwithin_calls():
@@ -22,11 +22,8 @@ def test_exported_symbols_name_the_dwithin_calls():
 def test_built_library_exports_the_dwithin_calls():
     from geopolars_amd import build
 
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    assert {"gpk_dwithin_join", "gpk_dwithin_rowwise"} <= names
-    assert os.path.samefile(lib, _abi.LIB_PATH) or os.environ.get("GPK_LIB_PATH")
+    assert {"gpk_dwithin_join", "gpk_dwithin_rowwise"} <= exported_symbols()
+    assert os.path.samefile(build.build(), _abi.LIB_PATH) or os.environ.get("GPK_LIB_PATH")
 
 
 def test_dwithin_args_defaults():
@@ -34,16 +31,6 @@ def test_dwithin_args_defaults():
     assert a.distance is None and a.join_type == "inner" and a.distance_col is None
     assert a.l_suffix == "_left" and a.r_suffix == "_right" and a.r_index is None
     assert a.l_geom_type == -1 and a.r_geom_type == -1
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():

@@ -4,7 +4,6 @@ UBSan.  The program's worst errors per regime are what the named tolerances of t
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -15,6 +14,7 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from tests import geodesic_measure_ref as R
+from tests.host_build import build_host_drivers, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -43,14 +43,6 @@ def test_null_handles_are_refused_by_the_library():
     assert lib.gpk_geodesic_direct(None, None, 1, None, 1, None, None, _abi.MEM_HOST, None) == _abi.GPK_ERR_INVALID_ARGUMENT
 
 
-@pytest.fixture
-def no_device(monkeypatch):
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def test_python_refusals_come_before_the_device(no_device):
     pts = GeoSeries(GeoArrowArray.from_points([(0.0, 0.0), (1.0, 1.0)]))
     three = GeoSeries(GeoArrowArray.from_points([(0.0, 0.0), (1.0, 1.0), (2.0, 2.0)]))
@@ -69,34 +61,9 @@ def test_python_refusals_come_before_the_device(no_device):
 
 
 # ---- the kernels' math on the CPU --------------------------------------------------------------------------------------------------
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/geodesic_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("geodesic_driver")
-    src = os.path.join(HERE, "geodesic_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"geodesic_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "geodesic", fp_contract_off=True)
 
 
 def run_driver(exe, workdir, fx):

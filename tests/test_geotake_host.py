@@ -5,7 +5,6 @@ the C ABI symbols, the header's text, the refusals of the library that come befo
 before the library is opened."""
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
 
@@ -18,39 +17,15 @@ from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import SpatialJoinArgs, spatial_join
 from tests import geotake_cases as K
 from tests.second_pass import same_bits
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/geotake_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("geotake_driver")
-    src = os.path.join(HERE, "geotake_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"geotake_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "geotake", fp_contract_off=False)
 
 
 def _levels(a: GeoArrowArray):
@@ -126,9 +101,7 @@ def test_exported_symbols_name_both_calls():
 def test_built_library_exports_both_calls():
     from geopolars_amd import build
 
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_symbols()
     assert "gpk_geoarray_take" in names and "gpk_geoarray_filter" in names
     assert "gpk_geotake.hip" in build.SOURCES
 
@@ -172,16 +145,6 @@ def test_bad_arguments_are_refused_by_the_library_before_any_device_work():
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def _refused(call):
     with pytest.raises(_abi.GeopolarsHipError) as e:
         call()

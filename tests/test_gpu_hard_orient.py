@@ -407,12 +407,13 @@ def test_validity_and_simplicity(gpk, gen, long):
 def host_answers(tmp_path_factory):
     """tests/triangulate_host_driver.cpp built with the host compiler, as tests/test_triangulate_host.py builds it: a function
     (kind, rows) -> [(status, row-local triangles)]"""
-    from tests.test_triangulate_host import _compilers, run
+    from tests.host_build import compilers
+    from tests.test_triangulate_host import run
 
     out = tmp_path_factory.mktemp("hard_orient_driver")
     exe = str(out / "triangulate_driver")
     log = []
-    for cxx in _compilers():
+    for cxx in compilers():
         r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", "-O2", f"-I{os.path.join(ROOT, 'geopolars_amd', 'csrc')}",
                             os.path.join(ROOT, "tests", "triangulate_host_driver.cpp"), "-o", exe], capture_output=True, text=True)
         if r.returncode == 0:

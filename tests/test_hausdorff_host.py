@@ -4,7 +4,6 @@ and at the georeferenced placements — and the checks that need no device: the 
 the library is opened."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,40 +14,16 @@ from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import FRECHET_MAX_SHORT, MAX_SUBDIVISIONS, GeoSeries, densify_arg, distance_rows_arg
 from tests import exact_ref as X
 from tests import hausdorff_ref as H
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 KS = (1, 2, 3, 7)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/hausdorff_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases; nothing is preloaded and nothing is loaded into Python)"""
-    out = tmp_path_factory.mktemp("hausdorff_driver")
-    src = os.path.join(HERE, "hausdorff_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"hausdorff_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "hausdorff", fp_contract_off=True)
 
 
 @pytest.fixture(scope="module")
@@ -115,10 +90,7 @@ def test_host_driver_known_answers(drivers):
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_declared_exported_and_documented():
-    from geopolars_amd import build
-
-    out = subprocess.run(["nm", "-D", "--defined-only", build.build()], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     flat = " ".join(open(os.path.join(ROOT, "include", "geopolars_hip.h")).read().split())
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name, n_args in (("gpk_hausdorff_distance", 7), ("gpk_frechet_distance", 8)):
@@ -145,14 +117,6 @@ def test_null_and_out_of_range_arguments_are_refused_before_any_device_work():
 
 
 # ---- Python: refusals before the library is opened ----------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def test_densify_to_k_and_its_errors(no_device):
     assert [densify_arg("op", d) for d in (None, 1, 1.0, 0.5, 0.25, 1 / 3, 1 / 7, 0.4, 1 / 4096)] == [1, 1, 1, 2, 4, 3, 7, 2, 4096]
     assert all(densify_arg("op", d) == H.densify_k(d) for d in (0.9, 0.6, 0.35, 0.2, 0.13, 0.01, 0.003))

@@ -4,7 +4,6 @@ device: the C ABI symbol, the header's rules, the library's refusal of NULL argu
 library is opened."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,39 +13,15 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import DeviceGeoArray, GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries, representative_point_device, return_width_arg
 from tests import interior_ref as I
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/interior_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("interior_driver")
-    src = os.path.join(HERE, "interior_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"interior_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "interior", fp_contract_off=True)
 
 
 @pytest.fixture(scope="module")
@@ -139,10 +114,7 @@ def test_host_driver_non_finite_rows(drivers):
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_symbol_is_declared_exported_and_documented():
     assert "gpk_representative_point" in _abi.EXPORTED_SYMBOLS and len(_abi._PROTOS["gpk_representative_point"][1]) == 6
-    from geopolars_amd import build
-
-    out = subprocess.run(["nm", "-D", "--defined-only", build.build()], capture_output=True, text=True, check=True).stdout
-    assert "gpk_representative_point" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert "gpk_representative_point" in exported_symbols()
     flat = " ".join(open(os.path.join(ROOT, "include", "geopolars_hip.h")).read().split())
     assert ("int32_t gpk_representative_point(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, double* out_width, int32_t out_space, "
             "void* stream);") in flat
@@ -162,14 +134,6 @@ def test_null_arguments_are_refused_by_the_library_before_any_device_work():
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def test_bad_arguments_come_before_the_device(no_device):
     s = GeoSeries(GeoArrowArray.from_polygons([[I.rect(0.0, 0.0, 4.0, 4.0)]]))
     for bad in ("yes", 1, None, 0.5, [True]):

@@ -11,7 +11,8 @@ from geopolars_amd import _abi
 from geopolars_amd.spatial_index import SpatialJoinKnnArgs, knn_pairs, knn_pairs_device, spatial_join_knn
 from tests import knn_ref as K
 from tests import nearest_any_ref as N
-from tests.test_nearest_any_host import GEOMETRYCOLLECTION, _Column, _compilers, _Dev, _series, no_device  # noqa: F401  (no_device: a fixture)
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
+from tests.test_nearest_any_host import GEOMETRYCOLLECTION, _Column, _Dev, _series
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -19,12 +20,9 @@ ROOT = os.path.dirname(HERE)
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_symbol_is_declared_exported_and_documented():
-    from geopolars_amd import build
-
     assert "gpk_knn_join" in _abi.EXPORTED_SYMBOLS and len(_abi._PROTOS["gpk_knn_join"][1]) == 14
     assert _abi.GPK_KNN_MAX_K == 64 and _abi.GPK_KNN_EXCLUDE_SELF == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", build.build()], capture_output=True, text=True, check=True).stdout
-    assert "gpk_knn_join" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert "gpk_knn_join" in exported_symbols()
     flat = " ".join(open(os.path.join(ROOT, "include", "geopolars_hip.h")).read().split())
     assert ("int32_t gpk_knn_join(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, int32_t k, double max_distance, "
             "uint32_t flags, uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_dist, int64_t pair_capacity, "
@@ -82,22 +80,13 @@ CASES = ["grid_1x1", "grid_7x5", "grid_23x19", "lattice_points", "long_boxes", "
          "few_rights"]
 
 
-@pytest.mark.parametrize("name,extra", [("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])])
-def test_k_seed_walk_finds_the_k_lowest_keys(tmp_path, name, extra):
+@pytest.mark.parametrize("name", ["plain", "sanitized"], ids=["plain-extra0", "sanitized-extra1"])  # (the ids these cases have had)
+def test_k_seed_walk_finds_the_k_lowest_keys(tmp_path_factory, name):
     """tests/knnwalk_host_driver.cpp, a stand-alone executable built with the host compiler (nothing is preloaded, nothing is loaded
     into Python): per grid case, 360 left boxes whose K slots must be the brute-force K lowest (far distance, row) keys within max_d —
     same rows, same distance bits, no row twice"""
-    src = os.path.join(HERE, "knnwalk_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    exe, log = str(tmp_path / f"knnwalk_driver_{name}"), []
-    for cxx in _compilers():
-        r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        log.append(f"{cxx}: {r.stderr[-400:]}")
-    else:
-        raise AssertionError(f"no host compiler built the {name} driver:\n" + "\n".join(log))
-    r = subprocess.run([exe], capture_output=True, text=True)
+    built, _ = build_host_drivers(tmp_path_factory, "knnwalk", fp_contract_off=True, builds=(name,))
+    r = subprocess.run([built[name]], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     lines = [ln.split() for ln in r.stdout.splitlines()]
     assert [ln[0] for ln in lines] == CASES

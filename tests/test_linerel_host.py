@@ -22,6 +22,7 @@ from geopolars_amd.spatial_index import (
     spatial_join_line_relation,
 )
 from tests import linerel_ref as L
+from tests.host_build import no_device  # noqa: F401  (no_device: a fixture)
 
 LS, MLS, PG, PT = _abi.GEOM_LINESTRING, _abi.GEOM_MULTILINESTRING, _abi.GEOM_POLYGON, _abi.GEOM_POINT
 
@@ -71,16 +72,6 @@ def test_predicate_names_of_the_join():
         with pytest.raises(_abi.GeopolarsHipError) as e:
             line_relation_predicate_arg(name, PG, PG)  # the ABI's order: the predicate first
         assert e.value.code == _abi.GPK_ERR_INVALID_ARGUMENT and not isinstance(e.value, _abi.MismatchedGeometry)
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():

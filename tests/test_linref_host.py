@@ -7,6 +7,7 @@ import pytest
 from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries, interpolate_distance_arg
+from tests.host_build import no_device  # noqa: F401  (no_device: a fixture)
 
 
 @pytest.mark.parametrize("name,n_args", [("gpk_closest_point_rowwise", 7), ("gpk_line_locate_point", 7), ("gpk_line_interpolate_point", 8)])
@@ -14,16 +15,6 @@ def test_exported_symbols_name_the_linear_referencing_calls(name, n_args):
     assert name in _abi.EXPORTED_SYMBOLS
     restype, argtypes = _abi._PROTOS[name]
     assert len(argtypes) == n_args
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():

@@ -4,7 +4,6 @@ one — and the checks that need no device: the C ABI symbols, the header's rule
 Python refusals that come before the library is opened."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,39 +14,15 @@ from geopolars_amd.geoarrow import DeviceGeoArray, GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries, minimum_bounding_circle_device, minimum_rotated_rectangle_device, quad_segs_arg
 from tests import exact_ref as X
 from tests import minbound_ref as M
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/minbound_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("minbound_driver")
-    src = os.path.join(HERE, "minbound_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"minbound_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "minbound", fp_contract_off=True)
 
 
 @pytest.fixture(scope="module")
@@ -181,10 +156,7 @@ def test_host_driver_non_finite_rows(drivers):
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_declared_exported_and_documented():
     assert len(_abi._PROTOS["gpk_minimum_rotated_rectangle"][1]) == 5 and len(_abi._PROTOS["gpk_minimum_bounding_circle"][1]) == 6
-    from geopolars_amd import build
-
-    out = subprocess.run(["nm", "-D", "--defined-only", build.build()], capture_output=True, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    exported = exported_symbols()
     assert {"gpk_minimum_rotated_rectangle", "gpk_minimum_bounding_circle"} <= exported
     flat = " ".join(open(os.path.join(ROOT, "include", "geopolars_hip.h")).read().split())
     assert "int32_t gpk_minimum_rotated_rectangle(const gpk_geoarray* a, double* out_xy, uint8_t* out_valid, int32_t out_space, void* stream);" in flat
@@ -213,14 +185,6 @@ def test_null_arguments_are_refused_by_the_library_before_any_device_work():
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def test_bad_arguments_come_before_the_device(no_device):
     s = GeoSeries(GeoArrowArray.from_polygons([[[(0.0, 0.0), (4.0, 0.0), (4.0, 4.0), (0.0, 0.0)]]]))
     for bad in ("8", 0, 257, -1, 2.0, None, True, [8]):

@@ -3,7 +3,6 @@ ABI symbol, the seed walk's rule (csrc/gpk_nearwalk.h) run on the CPU by a stand
 and under AddressSanitizer + UBSan — and the condition on the fixtures of the exact-reference GPU test."""
 import math
 import os
-import shutil
 import subprocess
 
 import pytest
@@ -20,6 +19,7 @@ from geopolars_amd.spatial_index import (
     spatial_join_nearest,
 )
 from tests import nearest_any_ref as N
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -27,12 +27,9 @@ ROOT = os.path.dirname(HERE)
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_symbol_is_declared_exported_and_documented():
-    from geopolars_amd import build
-
     assert "gpk_nearest_join_any" in _abi.EXPORTED_SYMBOLS and len(_abi._PROTOS["gpk_nearest_join_any"][1]) == 12
     assert _abi._PROTOS["gpk_nearest_join_any"] == _abi._PROTOS["gpk_nearest_join"]
-    out = subprocess.run(["nm", "-D", "--defined-only", build.build()], capture_output=True, text=True, check=True).stdout
-    assert "gpk_nearest_join_any" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert "gpk_nearest_join_any" in exported_symbols()
     flat = " ".join(open(os.path.join(ROOT, "include", "geopolars_hip.h")).read().split())
     assert ("int32_t gpk_nearest_join_any(const gpk_geoarray* left, const gpk_geoarray* right, const gpk_index* right_index, double max_distance, "
             "uint32_t left_row_base, uint32_t* out_counts, uint32_t* out_pairs, double* out_dist, int64_t pair_capacity, int64_t* n_pairs, "
@@ -43,16 +40,6 @@ def test_symbol_is_declared_exported_and_documented():
 
 
 # ---- Python: refusals before the library is opened ----------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def _series():
     pts = GeoSeries(GeoArrowArray.from_points([[0.0, 0.0], [1.0, 1.0]]))
     lines = GeoSeries(GeoArrowArray.from_linestrings([[(0.0, 0.0), (1.0, 1.0)], [(2.0, 0.0), (3.0, 1.0)]]))
@@ -128,30 +115,12 @@ CASES = ["grid_1x1", "grid_7x5", "lattice_borders", "zero_width_axis", "zero_ext
          "right_spans_cells_sparse"]
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
-@pytest.mark.parametrize("name,extra", [("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])])
-def test_seed_walk_finds_the_nearest_box(tmp_path, name, extra):
+@pytest.mark.parametrize("name", ["plain", "sanitized"], ids=["plain-extra0", "sanitized-extra1"])  # (the ids these cases have had)
+def test_seed_walk_finds_the_nearest_box(tmp_path_factory, name):
     """tests/nearwalk_host_driver.cpp, a stand-alone executable built with the host compiler (nothing is preloaded, nothing is loaded
     into Python): per grid case, a few hundred left boxes whose seed must be the brute-force nearest box — same row, same distance bits"""
-    src = os.path.join(HERE, "nearwalk_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    exe, log = str(tmp_path / f"nearwalk_driver_{name}"), []
-    for cxx in _compilers():
-        r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        log.append(f"{cxx}: {r.stderr[-400:]}")
-    else:
-        raise AssertionError(f"no host compiler built the {name} driver:\n" + "\n".join(log))
-    r = subprocess.run([exe], capture_output=True, text=True)
+    built, _ = build_host_drivers(tmp_path_factory, "nearwalk", fp_contract_off=True, builds=(name,))
+    r = subprocess.run([built[name]], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     lines = [ln.split() for ln in r.stdout.splitlines()]
     assert [ln[0] for ln in lines] == CASES

@@ -8,6 +8,7 @@ from geopolars_amd import _abi, spatial_index
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import SpatialJoinNearestArgs, nearest_pairs, spatial_join_nearest
+from tests.host_build import no_device  # noqa: F401  (no_device: a fixture)
 
 
 def test_exported_symbols_name_the_nearest_join():
@@ -21,16 +22,6 @@ def test_nearest_args_defaults():
     assert a.join_type == "inner" and a.max_distance is None and a.distance_col is None
     assert a.l_suffix == "_left" and a.r_suffix == "_right" and a.r_index is None
     assert a.l_geom_type == -1 and a.r_geom_type == -1
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():

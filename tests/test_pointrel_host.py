@@ -5,7 +5,6 @@ table, and the older methods that must keep refusing."""
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -41,6 +40,7 @@ from geopolars_amd.spatial_index import (
     spatial_join_point_relation,
 )
 from tests import pointrel_ref as P
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -49,34 +49,9 @@ FAMILY_IDS = [f"{P.NAMES[a]}-{P.NAMES[b]}" for a, b in P.FAMILIES]
 BUILDS = ["plain", "sanitized"]
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/pointrel_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("pointrel_driver")
-    src = os.path.join(HERE, "pointrel_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"pointrel_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "pointrel", fp_contract_off=False)
 
 
 def _record(ka, row_a, kb, row_b) -> bytes:
@@ -162,9 +137,7 @@ def test_exported_symbols_name_the_point_relation_calls():
 def test_built_library_exports_the_calls():
     from geopolars_amd import build
 
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_symbols()
     assert set(NAMES) <= names
     assert "gpk_pointrel.hip" in build.SOURCES
 
@@ -252,16 +225,6 @@ def test_bad_arguments_are_refused_by_the_library_before_any_device_work():
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def _series():
     pts = GeoSeries(GeoArrowArray.from_points([[0.0, 0.0], [1.0, 1.0], [2.0, 2.0]]))
     two = GeoSeries(GeoArrowArray.from_points([[0.0, 0.0], [1.0, 1.0]]))

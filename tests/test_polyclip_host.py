@@ -5,7 +5,6 @@ no device: the C ABI symbol, the header's text, the refusals of the library that
 that come before the library is opened."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,39 +15,15 @@ from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import polygon_clip_pairs, spatial_join_overlay
 from tests import polyclip_ref as L
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/polyclip_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("polyclip_driver")
-    src = os.path.join(HERE, "polyclip_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"polyclip_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "polyclip", fp_contract_off=True)
 
 
 @pytest.fixture(scope="module")
@@ -101,9 +76,7 @@ def test_exported_symbols_name_the_clip_call():
 def test_built_library_exports_the_clip_call():
     from geopolars_amd import build
 
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    assert "gpk_polygon_clip" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert "gpk_polygon_clip" in exported_symbols()
     assert "gpk_polyclip.hip" in build.SOURCES
 
 
@@ -126,16 +99,6 @@ def test_bad_plain_arguments_are_refused_by_the_library_before_any_device_work(m
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def _series():
     pts = GeoSeries(GeoArrowArray.from_points([[0.0, 0.0], [1.0, 1.0], [2.0, 2.0]]))
     lines = GeoSeries(GeoArrowArray.from_linestrings([[(0.0, 0.0), (1.0, 1.0)], [(2.0, 0.0), (3.0, 1.0)], [(2.0, 0.0), (3.0, 1.0)]]))

@@ -2,7 +2,6 @@
 the argument checks that refuse a call before the library is opened, and the older surfaces that must not move."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ from geopolars_amd.spatial_index import (
     relation_pairs,
     spatial_join_polygon_relation,
 )
+from tests.host_build import exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 LS, PG, MPG, PT = _abi.GEOM_LINESTRING, _abi.GEOM_POLYGON, _abi.GEOM_MULTIPOLYGON, _abi.GEOM_POINT
 
@@ -33,11 +33,7 @@ def test_exported_symbols_name_the_polygon_relation_calls():
 
 
 def test_built_library_exports_the_polygon_relation_calls():
-    from geopolars_amd import build
-
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_symbols()
     assert {"gpk_polygon_relation", "gpk_polygon_relation_join"} <= names
 
 
@@ -98,16 +94,6 @@ def test_predicate_names_of_the_join():
         with pytest.raises(_abi.GeopolarsHipError) as e:
             polygon_relation_predicate_arg(name, PG, PG)
         assert e.value.code == _abi.GPK_ERR_INVALID_ARGUMENT
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():

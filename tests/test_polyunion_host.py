@@ -5,7 +5,6 @@ that need no device: the C ABI symbols, the headers' text, the refusals of the l
 refusals that come before the library is opened."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,39 +15,15 @@ from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries
 from geopolars_amd.spatial_index import polygon_union_pairs
 from tests import polyunion_ref as U
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/polyunion_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("polyunion_driver")
-    src = os.path.join(HERE, "polyunion_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"polyunion_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "polyunion", fp_contract_off=True)
 
 
 @pytest.fixture(scope="module")
@@ -103,9 +78,7 @@ def test_exported_symbols_name_the_union_calls():
 def test_built_library_exports_the_union_calls():
     from geopolars_amd import build
 
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_symbols()
     assert {"gpk_polygon_union", "gpk_union_all_pairs", "gpk_polygon_clip"} <= names
     assert "gpk_polyunion.hip" in build.SOURCES and "gpk_polyclip.hip" in build.SOURCES
 
@@ -140,16 +113,6 @@ def test_the_pairing_refuses_bad_sizes_and_needs_no_device_for_no_row():
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def _series():
     pts = GeoSeries(GeoArrowArray.from_points([[0.0, 0.0], [1.0, 1.0], [2.0, 2.0]]))
     lines = GeoSeries(GeoArrowArray.from_linestrings([[(0.0, 0.0), (1.0, 1.0)], [(2.0, 0.0), (3.0, 1.0)], [(2.0, 0.0), (3.0, 1.0)]]))

@@ -1,6 +1,5 @@
 """Line x polygon relations, host side: the C ABI symbols, the mask -> predicate table, the predicate-name / side rules of the join and
 the argument checks that refuse a call before the library is opened."""
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from geopolars_amd.spatial_index import (
     relation_predicate_arg,
     spatial_join_relation,
 )
+from tests.host_build import exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 LS, MLS, PG, MPG, PT = _abi.GEOM_LINESTRING, _abi.GEOM_MULTILINESTRING, _abi.GEOM_POLYGON, _abi.GEOM_MULTIPOLYGON, _abi.GEOM_POINT
 
@@ -29,11 +29,7 @@ def test_exported_symbols_name_the_relation_calls():
 
 
 def test_built_library_exports_the_relation_calls():
-    from geopolars_amd import build
-
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_symbols()
     assert {"gpk_line_polygon_relation", "gpk_line_polygon_join"} <= names
 
 
@@ -96,16 +92,6 @@ def test_relation_args_defaults():
     a = SpatialJoinRelationArgs()
     assert a.predicate == "intersects" and a.join_type == "inner" and a.relation_col is None
     assert a.l_suffix == "_left" and a.r_suffix == "_right" and a.r_index is None and a.l_geom_type == -1 and a.r_geom_type == -1
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():

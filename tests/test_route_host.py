@@ -3,43 +3,19 @@ bit a point derives from its sub-cell coordinates are the ones of its cell, and 
 the CPU by a stand-alone program, plain and under AddressSanitizer + UBSan.  And what the header promises the callers of
 gpk_index_describe."""
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from tests.host_build import build_host_drivers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/route_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("route_driver")
-    src = os.path.join(HERE, "route_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"route_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built
+    return build_host_drivers(tmp_path_factory, "route", fp_contract_off=False)[0]
 
 
 @pytest.mark.parametrize("build", ["plain", "sanitized"])

@@ -3,43 +3,20 @@ run on the CPU by a stand-alone program — plain and under AddressSanitizer + U
 arena, and the checks of the source tree that need no device: nobody but the planner carves."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
+
+from tests.host_build import build_host_drivers
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "geopolars_amd", "csrc")
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/scratch_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("scratch_driver")
-    src = os.path.join(HERE, "scratch_host_driver.cpp")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"scratch_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", *extra, f"-I{CSRC}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built
+    return build_host_drivers(tmp_path_factory, "scratch", fp_contract_off=False)[0]
 
 
 @pytest.mark.parametrize("build", ["plain", "sanitized"])

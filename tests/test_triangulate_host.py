@@ -4,7 +4,6 @@ tests/triangulate_ref.py; and the checks that need no device: the C ABI symbol, 
 device work and the Python refusals that come before the library is opened."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ from geopolars_amd.geoarrow import DeviceGeoArray, GeoArrowArray
 from geopolars_amd.geoseries import GeoSeries, triangulate_device
 from tests import triangulate_ref as T
 from tests import validity_ref as V
+from tests.host_build import build_host_drivers, exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -22,34 +22,9 @@ PG, MPG = V.PG, V.MPG
 NAN, INF = float("nan"), float("inf")
 
 
-def _compilers():
-    seen = []
-    for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        p = shutil.which(c) if c else None
-        if p and p not in seen:
-            seen.append(p)
-    return seen
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    """tests/triangulate_host_driver.cpp built twice with the host compiler: plain, and with -fsanitize=address,undefined (a stand-alone
-    executable in both cases)"""
-    out = tmp_path_factory.mktemp("triangulate_driver")
-    src = os.path.join(HERE, "triangulate_host_driver.cpp")
-    inc = os.path.join(ROOT, "geopolars_amd", "csrc")
-    built = {}
-    for name, extra in (("plain", ["-O2"]), ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        log = []
-        for cxx in _compilers():
-            exe = str(out / f"triangulate_driver_{name}")
-            r = subprocess.run([cxx, "-std=c++17", "-ffp-contract=off", *extra, f"-I{inc}", src, "-o", exe], capture_output=True, text=True)
-            if r.returncode == 0:
-                built[name] = exe
-                break
-            log.append(f"{cxx}: {r.stderr[-400:]}")
-        assert name in built, f"no host compiler built the {name} driver:\n" + "\n".join(log)
-    return built, out
+    return build_host_drivers(tmp_path_factory, "triangulate", fp_contract_off=True)
 
 
 def run(exe, workdir, kind, rows, valid=None):
@@ -155,10 +130,7 @@ def test_countries(drivers):
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------
 def test_symbol_is_declared_exported_and_documented():
     assert len(_abi._PROTOS["gpk_triangulate"][1]) == 8
-    from geopolars_amd import build
-
-    out = subprocess.run(["nm", "-D", "--defined-only", build.build()], capture_output=True, text=True, check=True).stdout
-    assert "gpk_triangulate" in {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert "gpk_triangulate" in exported_symbols()
     flat = " ".join(open(os.path.join(ROOT, "include", "geopolars_hip.h")).read().split())
     assert ("int32_t gpk_triangulate(const gpk_geoarray* a, uint32_t* out_index, int64_t tri_capacity, int32_t* out_tri_offsets, uint8_t* out_status, "
             "int64_t* n_triangles, int32_t out_space, void* stream);") in flat
@@ -195,14 +167,6 @@ def test_refusals_come_before_any_device_work():
 
 
 # ---- Python: refusals before the library is opened -------------------------------------------------------------------------------------
-@pytest.fixture
-def no_device(monkeypatch):
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
-
-
 def test_bad_arguments_come_before_the_device(no_device):
     s = GeoSeries(GeoArrowArray.from_polygons([[[(0.0, 0.0), (4.0, 0.0), (4.0, 4.0), (0.0, 0.0)]]]))
     for bad in ("yes", 1, 0, None, 2.0, [True]):

@@ -2,7 +2,6 @@
 opened, and the older surfaces that must not move."""
 import os
 import re
-import subprocess
 
 import pytest
 
@@ -10,6 +9,7 @@ from geopolars_amd import _abi
 from geopolars_amd.geoarrow import GeoArrowArray
 from geopolars_amd.geoseries import VALIDITY_NAMES, GeoSeries
 from tests import validity_ref as V
+from tests.host_build import exported_symbols, no_device  # noqa: F401  (no_device: a fixture)
 
 
 def test_exported_symbols_name_the_validity_calls():
@@ -19,11 +19,7 @@ def test_exported_symbols_name_the_validity_calls():
 
 
 def test_built_library_exports_the_validity_calls():
-    from geopolars_amd import build
-
-    lib = build.build()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
-    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    names = exported_symbols()
     assert {"gpk_validity", "gpk_is_simple"} <= names
 
 
@@ -49,16 +45,6 @@ def test_kernel_constants_are_the_ones_the_tests_mirror():
                        ("VAL_SEGS_PER_STRIP", V.VAL_SEGS_PER_STRIP), ("VAL_STRIPS_MAX", V.VAL_STRIPS_MAX), ("VAL_ENTRIES", V.VAL_ENTRIES)):
         assert re.search(rf"\b{name} = {want}\b", text), name
     assert re.search(r"VAL_G_MEAN = 32\.0", text) and V.VAL_G_MEAN == 32.0
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """any call into the library fails the test: the checks below must happen first"""
-
-    def boom():
-        raise AssertionError("the library was opened")
-
-    monkeypatch.setattr(_abi, "lib", boom)
 
 
 def _series():
