@@ -24,7 +24,9 @@
 // named by the number of its first coordinate in its column.  A crossing has ONE coordinate value wherever it is emitted:
 // lc::point_at along the edge of a in storage order with lc::crossing_t against the edge of b in storage order (crossing_point), in
 // both walks — the walk over ∂b orders its events by the parameter along b's edge but emits a's value — moved by ulps onto the closed
-// inner side of a's edge, so that the exact relation of a result to a is covered-by.  Arcs are linked by identity,
+// inner side of a's edge, so that the exact relation of a result to a is covered-by, and where an end of one edge lies within ulps of
+// the other edge to a double that leaves every end on its own side of the emitted half edges (crossing_keeps_sides): the ring does
+// not fold over an ulp at a vertex next to a crossing.  Arcs are linked by identity,
 // never by comparing computed coordinates; a ring is closed when the walk returns to its first arc.
 //
 // Rule 4, junctions.  More than one arc can end at the same point only at an input coordinate, where rings touch.  There the
@@ -41,7 +43,8 @@
 //     twice through that point).
 //
 // Rule 5, rings to polygons.  The sign of a ring is exact: at its lexicographically lowest point the lowest-lying incident edge is an
-// outgoing one for a counter-clockwise ring (ring_sign), in orientation signs of the ring's own coordinates; positive: a shell,
+// outgoing one for a counter-clockwise ring (ring_sign), in orientation signs of INPUT coordinates only — the directions of the
+// edges at that point are taken from the ends of their carrying segments, never from a computed crossing; positive: a shell,
 // negative: a hole; a degenerate sign gives status 4 and cannot occur above the gap.  A ring starts at its arc with the smallest key
 // (walk of a before walk of b, then the number of the segment its arc starts on, an arc that starts at the segment's first coordinate
 // before one that starts inside it).  Parts are ordered by their shell's key; each hole goes to the first shell in key order that
@@ -114,9 +117,36 @@ GPK_LC_FN int crossing_type_by(int side_q, int ccw, bool hole, int walk, int mod
 }
 GPK_LC_FN int crossing_type(int side_q, int ccw, bool hole, int walk, int mode) { return crossing_type_by<ClipRule>(side_q, ccw, hole, walk, mode); }
 
+// Does the emitted crossing x leave every end of either edge on the side it is on?  The result's edges at a crossing are the halves
+// x -> end of the two crossing edges.  An end of the OTHER edge that lies an ulp from this edge's carrier (a vertex next to the
+// crossing) can come to lie on the wrong side of an emitted half although it is on the right side of the edge itself: the ring then
+// folds over that ulp and is no valid polygon.  Exact signs of doubles.
+template <class Orient>
+GPK_LC_FN bool crossing_keeps_sides(P2 x, P2 a0, P2 a1, P2 b0, P2 b1, Orient orient) {
+    const P2 u[2] = {a0, b0}, v[2] = {a1, b1}, e0[2] = {b0, a0}, e1[2] = {b1, a1};
+    for (int k = 0; k < 2; ++k)
+        for (int j = 0; j < 2; ++j) {
+            const P2 e = j ? e1[k] : e0[k];
+            const bool ex = e.x == x.x && e.y == x.y;
+            const int s = orient(u[k], v[k], e);
+            if (!ex && !(x.x == v[k].x && x.y == v[k].y) && !(e.x == v[k].x && e.y == v[k].y) && orient(x, v[k], e) != s) return false;
+            if (!ex && !(x.x == u[k].x && x.y == u[k].y) && !(e.x == u[k].x && e.y == u[k].y) && orient(u[k], x, e) != s) return false;
+        }
+    return true;
+}
+GPK_LC_FN double ulps_away(double v, int k) {
+    for (; k > 0; --k) v = nextafter(v, INFINITY);
+    for (; k < 0; ++k) v = nextafter(v, -INFINITY);
+    return v;
+}
+
 // The one coordinate value of the crossing of edge a0 -> a1 of a with edge b0 -> b1 of b (storage order both), around the origin o.
 // a_left: a's interior lies left of a0 -> a1.  The rounded point is then moved, an ulp of one coordinate at a time, onto the closed
-// inner side of a's edge (exact signs; it starts within a few ulps of the edge), so that no vertex of a result lies outside a.
+// inner side of a's edge (exact signs; it starts within a few ulps of the edge), so that no vertex of a result lies outside a.  Where
+// that point fails crossing_keeps_sides — only when an end of one edge lies within ulps of the other edge — the doubles up to
+// CROSSING_SEARCH ulps around it are tried, nearest ring first, for one on a's closed inner side and in a's box that keeps the sides;
+// without one the point stays (the row is then within 1e-9 d all the same, and may be no valid polygon).
+constexpr int CROSSING_SEARCH = 3;
 template <class Orient>
 GPK_LC_FN P2 crossing_point(P2 a0, P2 a1, P2 b0, P2 b1, P2 o, bool a_left, Orient orient) {
     P2 x = lc::point_at(a0, a1, lc::crossing_t(a0, a1, b0, b1, o));
@@ -130,6 +160,17 @@ GPK_LC_FN P2 crossing_point(P2 a0, P2 a1, P2 b0, P2 b1, P2 o, bool a_left, Orien
         else
             x.y = nextafter(x.y, ny > 0.0 ? INFINITY : -INFINITY);
     }
+    if (crossing_keeps_sides(x, a0, a1, b0, b1, orient)) return x;
+    const double lx = fmin(a0.x, a1.x), hx = fmax(a0.x, a1.x), ly = fmin(a0.y, a1.y), hy = fmax(a0.y, a1.y);
+    for (int r = 1; r <= CROSSING_SEARCH; ++r)
+        for (int dx = -r; dx <= r; ++dx)
+            for (int dy = -r; dy <= r; ++dy) {
+                if (dx != -r && dx != r && dy != -r && dy != r) continue;
+                const P2 y{ulps_away(x.x, dx), ulps_away(x.y, dy)};
+                if (y.x < lx || y.x > hx || y.y < ly || y.y > hy) continue;
+                const int s = orient(a0, a1, y);
+                if ((s == 0 || s == want) && crossing_keeps_sides(y, a0, a1, b0, b1, orient)) return y;
+            }
     return x;
 }
 
@@ -137,8 +178,16 @@ GPK_LC_FN P2 crossing_point(P2 a0, P2 a1, P2 b0, P2 b1, P2 o, bool a_left, Orien
 struct End {
     double x, y;  // the coordinate that is emitted
     int ea, eb;   // ea < 0: an input coordinate, identified by (x, y); else the crossing of edge ea of a with edge eb of b
+    P2 far;       // an end INSIDE a segment p -> q of its walk (a crossing, a vertex of the other row): the segment's other end — p
+                  // behind the start of an arc, q beyond its end, in the emitted direction; set by the run routines below, which know
+                  // the segment.  (An end at a coordinate of the walked ring holds its own value here; ring_corners copies it and
+                  // nothing reads the copy, since such a corner is not `computed`.)
 };
-GPK_LC_FN End end_at_coord(P2 v) { return End{v.x, v.y, -1, -1}; }
+GPK_LC_FN End end_at_coord(P2 v) { return End{v.x, v.y, -1, -1, v}; }
+GPK_LC_FN End with_far(End id, P2 far) {
+    id.far = far;
+    return id;
+}
 GPK_LC_FN bool same_end(const End& u, const End& v) {
     return u.ea < 0 ? (v.ea < 0 && u.x == v.x && u.y == v.y) : (u.ea == v.ea && u.eb == v.eb);
 }
@@ -186,7 +235,7 @@ GPK_LC_FN void run_cut(Run& r, End id, bool inside, P2 p, P2 q, int seg, int wal
     if (!r.open) return;
     if (r.emit) {
         if (inside) out.coord(P2{id.x, id.y});
-        out.end_arc(id, inside ? p : r.prev_p, 0);
+        out.end_arc(with_far(id, q), inside ? p : r.prev_p, 0);
     }
     r.any_break = true;
     r.emit = false;
@@ -194,7 +243,7 @@ GPK_LC_FN void run_cut(Run& r, End id, bool inside, P2 p, P2 q, int seg, int wal
         r.open = false;
         return;
     }
-    out.begin_arc(id, q, (walk == WALK_B ? KEY_WALK_B : 0) | (2 * seg + (inside ? 1 : 0)));
+    out.begin_arc(with_far(id, p), q, (walk == WALK_B ? KEY_WALK_B : 0) | (2 * seg + (inside ? 1 : 0)));
     out.coord(P2{id.x, id.y});
     r.emit = true;
 }
@@ -229,13 +278,13 @@ GPK_LC_FN void run_transition(Run& r, int type, End id, P2 p, P2 q, int seg, int
     r.depth += type;
     const bool after = r.depth > 0;
     if (!before && after) {
-        out.begin_arc(id, q, (walk == WALK_B ? KEY_WALK_B : 0) | (2 * seg + 1));
+        out.begin_arc(with_far(id, p), q, (walk == WALK_B ? KEY_WALK_B : 0) | (2 * seg + 1));
         out.coord(P2{id.x, id.y});
         r.emit = true;
     } else if (before && !after) {
         if (r.emit) {
             out.coord(P2{id.x, id.y});
-            out.end_arc(id, p, 0);
+            out.end_arc(with_far(id, q), p, 0);
         }
         r.any_break = true;
         r.emit = false;
@@ -285,21 +334,74 @@ GPK_LC_FN void ring_points(const Arc* arcs, const int* next, const P2* xy, int f
 
 GPK_LC_FN bool lex_less(P2 u, P2 v) { return u.x < v.x || (u.x == v.x && u.y < v.y); }
 
-// +1: counter-clockwise, -1: clockwise, 0: degenerate.  At the lexicographically lowest point M every incident edge leaves into the
-// closed right half plane; the ring is counter-clockwise iff the lowest-lying of them is an outgoing one — whatever else touches M.
+// A coordinate of a ring with the EXACT directions in which the ring reaches and leaves it, as input coordinates: `in` lies on the
+// carrier of the edge that arrives at v, behind v; `out` on the carrier of the edge that leaves it, ahead of v.  A computed crossing
+// lies inside both carrying segments; it also gets their other ends: in_far ahead of v on the arriving carrier, out_far behind v on
+// the leaving one.  The neighbouring COORDINATES are not used where one of the two is computed: a crossing is emitted within ulps of
+// the end of its segment when it lies that close to it, and the direction between the two doubles is then noise.
+struct Corner {
+    P2 v;
+    bool computed;
+    P2 in, out, in_far, out_far;
+};
+// f(const Corner&) for every coordinate of the ring that starts at arc `first`, the closing one left out
+template <class F>
+GPK_LC_FN void ring_corners(const Arc* arcs, const int* next, const P2* xy, int first, int n_arcs, F f) {
+    int prev = first;
+    for (int it = 0; it < n_arcs && next[prev] != first; ++it) prev = next[prev];
+    int a = first;
+    for (int it = 0; it < n_arcs; ++it) {
+        const Arc &A = arcs[a], &B = arcs[prev];
+        for (int j = 0; j + 1 < A.len; ++j) {
+            Corner c;
+            c.v = arc_coord(A, xy, j);
+            if (j == 0) {
+                c.computed = A.s.ea >= 0;
+                c.in = B.e_nb;
+                c.out = A.s_nb;
+                c.in_far = B.e.far;
+                c.out_far = A.s.far;
+            } else {
+                c.computed = false;
+                c.in = (j == 1 && A.s.ea >= 0) ? A.s.far : arc_coord(A, xy, j - 1);
+                c.out = (j + 2 == A.len && A.e.ea >= 0) ? A.e.far : arc_coord(A, xy, j + 1);
+                c.in_far = c.out_far = c.v;
+            }
+            f(c);
+        }
+        prev = a;
+        a = next[a];
+        if (a == first) break;
+    }
+}
+
+// +1: counter-clockwise, -1: clockwise, 0: degenerate.  A corner is a local minimum of the lexicographic order when the ring reaches
+// it from above and leaves it upwards: decided exactly, for an input coordinate by its two direction coordinates, for a crossing by
+// the ends of its two carrying segments (the order is monotone along a segment).  M is the lowest of the local minima — of two
+// coordinates ulps apart on one carrier exactly one is a local minimum, so the noise between them does not choose.  At an input
+// coordinate M every incident edge leaves into the closed right half plane and the ring is counter-clockwise iff the lowest-lying of
+// them is an outgoing one, whatever else touches M; the rays are the exact directions.  At a crossing M (no other ring passes through
+// it) the ring turns from the carrier p1 -> q1 to the carrier p2 -> q2, and the turn is the side of q2 against p1 -> q1: exact, and
+// independent of the rounded crossing.
 template <class Orient>
 GPK_LC_FN int ring_sign(const Arc* arcs, const int* next, const P2* xy, int first, int n_arcs, Orient orient) {
+    auto local_min = [](const Corner& c) {
+        if (c.computed) return lex_less(c.in_far, c.in) && lex_less(c.out_far, c.out);  // (arriving downwards, leaving upwards)
+        return lex_less(c.v, c.in) && lex_less(c.v, c.out);
+    };
     P2 M{0.0, 0.0};
-    int n = 0;
-    ring_points(arcs, next, xy, first, n_arcs, [&](P2 v, bool) {
-        if (n == 0 || lex_less(v, M)) M = v;
+    int n = 0, have_m = 0;
+    ring_corners(arcs, next, xy, first, n_arcs, [&](const Corner& c) {
         ++n;
+        if (local_min(c) && (!have_m || lex_less(c.v, M))) {
+            M = c.v;
+            have_m = 1;
+        }
     });
-    if (n < 3) return 0;
+    if (n < 3 || !have_m) return 0;
     P2 low{0.0, 0.0};
-    int low_out = 0, tie = 0, have = 0;
+    int low_out = 0, tie = 0, have = 0, turn = 0, at_input = 0;
     auto ray = [&](P2 d, int is_out) {
-        if (d.x == M.x && d.y == M.y) return;
         const int s = have ? orient(M, low, d) : -1;  // < 0: d lies clockwise of (below) the lowest so far
         if (s < 0) {
             low = d;
@@ -310,27 +412,17 @@ GPK_LC_FN int ring_sign(const Arc* arcs, const int* next, const P2* xy, int firs
             tie = 1;
         }
     };
-    P2 p0{0.0, 0.0}, p1{0.0, 0.0}, pp{0.0, 0.0}, pc{0.0, 0.0};
-    int i = 0;
-    ring_points(arcs, next, xy, first, n_arcs, [&](P2 v, bool) {
-        if (i == 0) p0 = v;
-        if (i == 1) p1 = v;
-        if (i >= 2 && pc.x == M.x && pc.y == M.y) {
-            ray(pp, 0);
-            ray(v, 1);
+    ring_corners(arcs, next, xy, first, n_arcs, [&](const Corner& c) {
+        if (c.v.x != M.x || c.v.y != M.y || !local_min(c)) return;
+        if (c.computed) {
+            turn = orient(c.in, c.in_far, c.out);
+        } else {
+            at_input = 1;
+            ray(c.in, 0);
+            ray(c.out, 1);
         }
-        pp = pc;
-        pc = v;
-        ++i;
     });
-    if (pc.x == M.x && pc.y == M.y) {  // the last coordinate: before it pp, after it the first
-        ray(pp, 0);
-        ray(p0, 1);
-    }
-    if (p0.x == M.x && p0.y == M.y) {  // the first: before it the last, after it the second
-        ray(pc, 0);
-        ray(p1, 1);
-    }
+    if (!at_input) return turn;
     if (!have || tie) return 0;
     return low_out ? 1 : -1;
 }
@@ -621,7 +713,7 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                         // (a vertex of ANOTHER ring of the walked row at the crossing point — rings of a valid row may touch there — is what
                         // the other walk sees as a vertex on its open segment: the same identity and value here)
                         const int own = vertex_at_crossing_index<G>(W.xy, w.c0, w.c1, p, q, lx, hx, ly, hy, a, b, lane);
-                        const End id = own != 0x7fffffff ? end_at_coord(lc::p2(W.xy[own])) : End{x.x, x.y, ea, eb};
+                        const End id = own != 0x7fffffff ? end_at_coord(lc::p2(W.xy[own])) : End{x.x, x.y, ea, eb, x};
                         run_transition(run, crossing_type_by<Rule>(cont::orient(a, b, q), ccw, hole, walk, mode), id, lc::p2(p), lc::p2(q), seg, walk, out);
                     }
                     if (lap == 1 && !run.open) return;

@@ -35,7 +35,7 @@ namespace gpk {
 
 namespace {
 
-// a pair with at most this many arcs per lane of its group is stitched from LDS (96-byte records: 48 KB a block at either group size)
+// a pair with at most this many arcs per lane of its group is stitched from LDS (128-byte records: 64 KB a block at either group size)
 constexpr int STITCH_LDS_ARCS_PER_LANE = 2;
 
 struct CountSink {
@@ -133,6 +133,7 @@ __global__ __launch_bounds__(256) void polygon_clip_stitch_kernel(int64_t n, int
                                                                   int32_t* __restrict__ n_parts, int32_t* __restrict__ n_rings, int32_t* __restrict__ n_coords,
                                                                   int32_t* __restrict__ keep, uint8_t* __restrict__ status) {
     constexpr int SLICE = STITCH_LDS_ARCS_PER_LANE * G;
+    static_assert(sizeof(pc::Arc) == 128, "the LDS slice below is 64 KB, the static limit: a larger record needs fewer arcs a lane");
     __shared__ pc::Arc lds[256 * STITCH_LDS_ARCS_PER_LANE];
     const int lane = threadIdx.x & (G - 1), group = threadIdx.x / G;
     const int64_t k = (int64_t)blockIdx.x * (256 / G) + group;

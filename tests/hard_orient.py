@@ -24,6 +24,12 @@ point); tests/test_hard_orient.py::test_census_of_earlier_fixtures prints it:
     test_gpu_validity: the three slope-1/3 rows                             93       2       87     4     0
     hard_orient.triples(gen), each of the three: planted, six orders      1152     144      144   288   576
 
+The constructive kernels — gpk_line_clip, gpk_polygon_clip, gpk_polygon_union with union_all, gpk_intersection_measure and
+gpk_orient_polygons — take these rows through the figures at the end of "the figure around a triple" (pass, spike ring, nested hole,
+hinge), as columns in tests/hard_clip.py and on the GPU in tests/test_gpu_hard_clip.py.  Two families need no such rows, because they
+hold no orientation predicate at all: representative_point (gpk_interior.h) is floating arithmetic defined bit for bit, and
+segmentize only divides segments.
+
 For point probes an evaluation is an edge whose closed box holds the point (what coord_pos_relative_to_ring asks); for pairs of rows it
 is every segment of one row against every vertex of the other.  The W evaluations of the nudged pairs reach `contains` only; the
 georeferenced probes hold none at all, although they lie 1 - 2 ulps off their edges: at UTM magnitudes with metre-sized features the
@@ -451,6 +457,142 @@ def hull_row(t: Triple):
     return [t.a, t.b, t.c, far_left(t)]  # MULTIPOINT: c is a hull vertex only when it is right of a -> b
 
 
+# ---- figures for the constructive kernels: line clip, polygon clip, union, overlay measure, orient_polygons ---------------------------------
+#
+# A constructive kernel returns geometry, so a wrong sign shows as another SHAPE (parts, rings, coordinates per ring, which input
+# coordinate stands where), not as another mask.  tests/test_hard_orient.py holds every figure to: COMPOSITION kept, only the planted
+# triple uncertain, transitions apart by the headers' own definition (transition_gap of the references), one shape per exact sign,
+# and the shapes of + and - different for every operation.
+
+
+def rot90(t: Triple) -> Triple:
+    """(x, y) -> (-y, x), exact: swap_xy then mirror_x.  Two mirrors: every class AND the kind stay"""
+    return mirror_x(swap_xy(t))
+
+
+def rot180(t: Triple) -> Triple:
+    return rot90(rot90(t))
+
+
+def pass_points(t: Triple):
+    """w inside (a, b, r) — and inside the arc of the long ring —, q1 and q2 outside, on the right of a -> b"""
+    u = along(t)
+    return at(t, u - 0.05, 0.1), at(t, u + 0.05, -0.2), at(t, u - 0.10, -0.2)
+
+
+def pass_polygon(t: Triple):
+    """POLYGON (w, c, q1, q2), stored clockwise: its boundary passes through the vertex c from the inside of A = polygon_row(t) to its
+    outside.  c left of a -> b: c is inside A and c -> q1 crosses ab right after c; c right of it: w -> c crosses ab right before c;
+    collinear: c is a vertex of B on the open edge ab.  gpk_lineclip.h / gpk_polyclip.h decide it in lp::side_bits at c, in the
+    crossing tests of w -> c and c -> q1 against ab, in crossing_type (orient(a, b, q) of the crossing segment's far end) and, walking
+    the edge ab of A, in event_before's "(b) against (c)" rule: the vertex c of B against the crossings of B's two edges at c"""
+    w, q1, q2 = pass_points(t)
+    return [[w, t.c, q1, q2, w]]
+
+
+def pass_line(t: Triple):
+    """LINESTRING w, c, q1: the two edges of pass_polygon that meet at c.  Inside A it is [w, c, x] with a crossing x after c when c is
+    left of a -> b, [w, c] when collinear, [w, x] with x before c when right; outside A the rest"""
+    w, q1, _q2 = pass_points(t)
+    return [w, t.c, q1]
+
+
+def far_triangle(t: Triple, k: int = 0):
+    """a counter-clockwise triangle three edge lengths away from the figure: the first member of the MULTIPOLYGON forms (k = 0 beside
+    A, on the left; k = 1 beside B, on the right)"""
+    u, v = (3.0, 3.0) if k == 0 else (-2.7, -3.3)  # (no edge of one in line with a vertex of the other)
+    p, q, r = at(t, u, v), at(t, u + 0.5, v + 0.1), at(t, u + 0.1, v + 0.5)
+    return [[p, q, r, p]]
+
+
+def far_line(t: Triple):
+    return [at(t, -4.1, 2.2), at(t, -4.7, 2.6)]  # the first member of the MULTILINESTRING form: outside everything
+
+
+def pass_rows(t: Triple, long: bool = False, multi: bool = False):
+    """(A, B, line) of the pass figure.  long: A is the 48-coordinate ring; multi: MULTIPOLYGON / MULTILINESTRING rows with the figure
+    as the second member"""
+    A, B, line = polygon_row(t, long), pass_polygon(t), pass_line(t)
+    return ([far_triangle(t, 0), A], [far_triangle(t, 1), B], [far_line(t), line]) if multi else (A, B, line)
+
+
+SPIKE_X = (0.7, 0.3)  # the far point of the spike ring: 0.7 along the edge, 0.3 off it
+LONG_ARC = 300  # arc points of the long spike ring: past SHORT_RING = 256 of gpk_seqedit.hip (the work-group kernel)
+
+
+def _spike_ring(t: Triple, long: bool):
+    side = 1.0 if t.sign >= 0 else -1.0  # (a collinear row: either side gives a ring that touches itself)
+    X = at(t, SPIKE_X[0], SPIKE_X[1] * side)
+    mid = []
+    if long:  # a half ellipse from X to b that bulges away from a
+        m, h = ((X[0] + t.b[0]) / 2, (X[1] + t.b[1]) / 2), ((X[0] - t.b[0]) / 2, (X[1] - t.b[1]) / 2)
+        o = (0.5 * side * h[1], -0.5 * side * h[0])
+        if (m[0] + o[0] - t.a[0]) ** 2 + (m[1] + o[1] - t.a[1]) ** 2 < (m[0] - o[0] - t.a[0]) ** 2 + (m[1] - o[1] - t.a[1]) ** 2:
+            o = (-o[0], -o[1])
+        th = [math.pi * (j + 1) / (LONG_ARC + 1) for j in range(LONG_ARC)]
+        mid = [(m[0] + math.cos(x) * h[0] + math.sin(x) * o[0], m[1] + math.cos(x) * h[1] + math.sin(x) * o[1]) for x in th]
+    return [t.a, t.c, X] + mid + [t.b, t.a]
+
+
+@lru_cache(maxsize=None)
+def spike_triple(t: Triple, long: bool = False) -> Triple:
+    """t turned by a multiple of 90 degrees (exact; classes and kind stay) so that a is the lexicographically smallest coordinate of
+    the spike ring by a margin: the directions from a to every other coordinate span less than 90 degrees, so one of the four quarter
+    turns puts them all at a larger x.  tests/test_hard_orient.py asserts the placement with seqedit_ref.ring_turn"""
+    for _ in range(4):
+        ring = _spike_ring(t, long)
+        L = math.hypot(t.b[0] - t.a[0], t.b[1] - t.a[1])
+        if min(p[0] for p in ring[1:-1]) > t.a[0] + 0.02 * L:
+            return t
+        t = rot90(t)
+    raise AssertionError(t)
+
+
+def spike_row(t: Triple, long: bool = False):
+    """POLYGON [a, c, X, b, a] around spike_triple(t), X far on c's side of a -> b: the triangle (c, X, b) with the spike a - c, whose
+    returning edge b -> a passes c an ulp away.  The turn at the lexicographically smallest coordinate a is orient(b, a, c), the
+    planted triple: c left of a -> b gives a clockwise ring, c right a counter-clockwise one, collinear a ring that touches itself
+    (s == 0: gpk_orient_polygons copies it unchanged; for the clip an invalid row).  se::ring_turn of gpk_seqedit.h decides
+    gpk_orient_polygons, pc::ring_sign of gpk_polyclip.h the sign of the ring when a box that contains it keeps it whole.
+    long: LONG_ARC more coordinates between X and b (gpk_orient_polygons only)"""
+    return [_spike_ring(spike_triple(t, long), long)]
+
+
+def box_around(row, margin: float = 1.0):
+    """POLYGON: a counter-clockwise box around every coordinate of the row, about `margin` times the row's larger extent away from it
+    (another distance on every side: no corner in line with a diagonal of the row's own box)"""
+    pts = [p for ring in row for p in ring]
+    lo, hi = (min(p[0] for p in pts), min(p[1] for p in pts)), (max(p[0] for p in pts), max(p[1] for p in pts))
+    m = margin * max(hi[0] - lo[0], hi[1] - lo[1])
+    x0, y0, x1, y1 = lo[0] - m, lo[1] - 1.3 * m, hi[0] + 0.9 * m, hi[1] + 1.1 * m
+    return [[(x0, y0), (x1, y0), (x1, y1), (x0, y1), (x0, y0)]]
+
+
+def nested_triple(t: Triple) -> Triple:
+    """t, or t turned by 180 degrees (exact; classes and kind stay), whichever has c on the side of a -> b with the larger x — the
+    side hole_row puts the shell on: no row is lost to a hole that lies outside its shell"""
+    s = 1 if -(t.b[1] - t.a[1]) > 0 else -1  # +1: hole_row's shell is left of a -> b
+    return t if t.sign * s >= 0 else rot180(t)
+
+
+def nested_row(t: Triple, long: bool = False):
+    """POLYGON hole_row(nested_triple(t)): the hole's lowest vertex c lies strictly inside the shell, an ulp from its edge ab (on it
+    for a collinear row, which the clip is not given).  Intersected with a box that contains it, both rings are kept whole and the
+    result is the row itself, one part of two rings: the hole finds its shell in pc::ring_encloses (gpk_polyclip.h), the crossing
+    number of c against the shell, where only the edge ab is in doubt"""
+    return hole_row(nested_triple(t), long)
+
+
+def hinge_rows(t: Triple):
+    """(P, Q): P = (a, b, r) and Q = (a, X, c), X far on the right of a -> b, both counter-clockwise and hinged at a.  c right of
+    a -> b: they touch at a only; c left of it: X -> c crosses ab right before c and they overlap in the sliver (a, x, c); collinear:
+    they share the stretch a - c of ab.  At a four arcs meet: pc::cw_before (gpk_polyclip.h, and the union's stitch in
+    gpk_polyunion.h) orders a -> b against a -> c there, and the crossing test of X -> c against ab decides whether there is an overlap
+    at all"""
+    X = at(t, along(t) - 0.2, -0.5)
+    return polygon_row(t), [[t.a, X, t.c, t.a]]
+
+
 # ---- a fan of disjoint slivers for the point join -------------------------------------------------------------------------------------------
 #
 # A lean index with chains wants DISJOINT polygons, and a translation would destroy what makes a triple hard: the filter gives up only
@@ -597,9 +739,9 @@ def ring_evaluations(ring, points):
 # ---- rows for the references that work on integers ------------------------------------------------------------------------------------------
 
 
-def on_integer_grid(*rows):
-    """the rows (nested lists of (x, y) doubles) with every coordinate multiplied by one power of two that makes all of them
-    integers (Python ints): relation_ref and polyrel_ref take integer coordinates, and a common exact scale changes no relation"""
+def integer_grid_scale(*rows) -> int:
+    """the power of two on_integer_grid multiplies these rows by: a reference result on the grid, divided by it, is the result on the
+    doubles (polyclip_ref.scaled_back, lineclip_ref.scaled_back)"""
     flat = []
 
     def walk(r):
@@ -611,7 +753,13 @@ def on_integer_grid(*rows):
 
     for r in rows:
         walk(r)
-    den = max(f.denominator for f in flat)  # (denominators are powers of two)
+    return max(f.denominator for f in flat)  # (denominators are powers of two)
+
+
+def on_integer_grid(*rows):
+    """the rows (nested lists of (x, y) doubles) with every coordinate multiplied by one power of two that makes all of them
+    integers (Python ints): relation_ref and polyrel_ref take integer coordinates, and a common exact scale changes no relation"""
+    den = integer_grid_scale(*rows)
 
     def conv(r):
         if isinstance(r, tuple) and len(r) == 2 and not isinstance(r[0], (tuple, list)):

@@ -76,8 +76,9 @@ def analyse(kl, row_l, kp, row_p, l_valid=True, p_valid=True):
     if seqs_ok is None or polys is None:
         return None
     edges = E._edges([r for p in polys for r in p])
-    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
-    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
+    dt = O.int_dtype(edges)  # (Python ints of any size: rows of arbitrary doubles on one integer grid, tests/hard_orient.on_integer_grid)
+    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=dt).reshape(-1, 2)
+    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=dt).reshape(-1, 2)
     out = []
     for first, s in _flat_line(kl, row_l):
         c = [(int(x), int(y)) for x, y in s]
@@ -142,6 +143,86 @@ def clip(kl, row_l, kp, row_p, mode, l_valid=True, p_valid=True, pieces=None):
             for t0, t1 in zip(trans, trans[1:]):
                 min_gap = t1 - t0 if min_gap is None else min(min_gap, t1 - t0)
     return parts, crossings, min_gap
+
+
+def transition_gap(kl, row_l, kp, row_p, mode, l_valid=True, p_valid=True, pieces=None):
+    """What the contract of gpk_lineclip.h conditions on, by the header's own definition: a transition is a touch point or a vertex of
+    L where the kept-ness of the piece before differs from that of the piece after (the first and the last coordinate of a sequence
+    have one piece only and are none).  Returns the least distance between two distinct transition points of one segment, as a share
+    of the segment (a Fraction), None when no segment carries two.  Unlike `clip`'s min_gap it counts a transition at a vertex of L for
+    both segments that meet there."""
+    pieces = analyse(kl, row_l, kp, row_p, l_valid, p_valid) if pieces is None else pieces
+    if pieces is None:
+        return None
+    best = None
+    for _first, segs in pieces:
+        trans, prev = [], None
+        for _ip, _iq, _p, _q, pcs in segs:
+            ks = [kept(cls, mode) for _t0, _t1, cls in pcs]
+            here = {pcs[k][0] for k in range(1, len(pcs)) if ks[k] != ks[k - 1]}
+            if prev is not None and prev != ks[0]:
+                here.add(Fraction(0))
+                trans[-1].add(Fraction(1))
+            trans.append(here)
+            prev = ks[-1]
+        for here in trans:
+            ts = sorted(here)
+            for t0, t1 in zip(ts, ts[1:]):
+                best = t1 - t0 if best is None else min(best, t1 - t0)
+    return best
+
+
+def scaled_back(result, scale):
+    """A result of `clip` on rows that tests/hard_orient.on_integer_grid brought to an integer grid, in the units of the doubles
+    (scale = hard_orient.integer_grid_scale of the same rows, a power of two).  The parts name coordinates of the two rows by number
+    and need nothing: those come back bit for bit from the columns.  The crossings become (x, y, p, q, a) with Fractions x, y."""
+    if result is None:
+        return None
+    parts, crossings, _gap = result
+    return parts, [(Fraction(x) / scale, Fraction(y) / scale, ip, iq, ia) for x, y, ip, iq, ia in crossings]
+
+
+def check_rows(want, cl, cp, got):
+    """check_result for rows that are in no fixture file: `want[i]` is None (a null row) or (parts, crossings) of scaled_back for row
+    i of the columns cl, cp, `got` the downloaded MULTILINESTRING column.  Offsets and validity exactly, (a) / (b) coordinates bit for
+    bit, (c) within REL_TOL * d of the segment and of the ring edge.  Returns (the worst ratio of a (c) distance to its bound, the
+    number of (c) coordinates)."""
+    n = len(want)
+    assert got.n_geoms == n == cl.n_geoms
+    gv = np.ones(n, dtype=bool) if got.validity is None else np.unpackbits(got.validity, bitorder="little")[:n].astype(bool)
+    wv = np.array([w is not None for w in want])
+    assert (gv == wv).all(), np.nonzero(gv != wv)[0][:10]
+    n_parts = np.array([0 if w is None else len(w[0]) for w in want])
+    assert (np.diff(got.geom_offsets) == n_parts).all(), np.nonzero(np.diff(got.geom_offsets) != n_parts)[0][:10]
+    sizes = np.array([len(pt) for w in want if w is not None for pt in w[0]], dtype=np.int64)
+    assert (np.diff(got.ring_offsets) == sizes).all(), np.nonzero(np.diff(got.ring_offsets) != sizes)[0][:10]
+    ls, ps, diag = _row_starts(cl), _row_starts(cp), pair_diagonals(cl, cp)
+    at, worst, n_x = 0, 0.0, 0
+    for i, w in enumerate(want):
+        if w is None:
+            continue
+        for pt in w[0]:
+            for tag, k in pt:
+                g = got.xy[at]
+                if tag == TAG_L:
+                    assert g.tobytes() == cl.xy[ls[i] + k].tobytes(), (i, "a coordinate of the line is not returned bit for bit")
+                elif tag == TAG_P:
+                    assert g.tobytes() == cp.xy[ps[i] + k].tobytes(), (i, "a vertex of the polygon is not returned bit for bit")
+                else:
+                    _x, _y, ip, iq, ia = w[1][k]
+                    far = max(_off_segment(g, cl.xy[ls[i] + ip], cl.xy[ls[i] + iq]), _off_segment(g, cp.xy[ps[i] + ia], cp.xy[ps[i] + ia + 1]))
+                    worst, n_x = max(worst, far / (REL_TOL * diag[i])), n_x + 1
+                    assert far <= REL_TOL * diag[i], (i, far, diag[i])
+                at += 1
+    assert at == len(got.xy)
+    return worst, n_x
+
+
+def _off_segment(pt, u, v):
+    """distance of the point pt to the closed segment uv, around u"""
+    e, w = v - u, pt - u
+    s = min(1.0, max(0.0, float(w @ e) / float(e @ e)))
+    return float(np.hypot(*(w - s * e)))
 
 
 def measures(pieces, mode):

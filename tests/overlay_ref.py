@@ -87,6 +87,11 @@ def exact_area(ka, row_a, kb, row_b, a_valid=True, b_valid=True):
     return area_of_polys(pa, pb)
 
 
+def int_dtype(edges):
+    """int64 for the lattice fixtures, object (Python ints) where a coordinate of these edges is too wide for int64 arithmetic"""
+    return object if any(abs(v) >= 2**62 for e in edges for p in e for v in p) else np.int64
+
+
 def _line_seqs(kl, row, valid=True):
     """the integer sequences of a usable line row, else None"""
     if not valid or row is None:
@@ -105,8 +110,9 @@ def exact_length(kl, row_l, kp, row_p, l_valid=True, p_valid=True):
     if seqs is None or polys is None:
         return None
     edges = E._edges([r for p in polys for r in p])
-    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
-    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=np.int64).reshape(-1, 2)
+    dt = int_dtype(edges)
+    elo = np.array([[min(a[0], b[0]), min(a[1], b[1])] for a, b in edges], dtype=dt).reshape(-1, 2)
+    ehi = np.array([[max(a[0], b[0]), max(a[1], b[1])] for a, b in edges], dtype=dt).reshape(-1, 2)
     with mp.workdps(40):
         total = mp.mpf(0)
         for s in seqs:

@@ -55,7 +55,7 @@ def _shoelace2(ring):
 
 
 def _on_segment(t, a, b):
-    return _cross(a, b, t) == 0 and min(a[0], b[0]) <= t[0] <= max(a[0], b[0]) and min(a[1], b[1]) <= t[1] <= max(a[1], b[1])
+    return min(a[0], b[0]) <= t[0] <= max(a[0], b[0]) and min(a[1], b[1]) <= t[1] <= max(a[1], b[1]) and _cross(a, b, t) == 0  # (the cheap test first)
 
 
 def ring_position(t, ring):
@@ -278,6 +278,132 @@ def clip(ka, row_a, kb, row_b, mode, a_valid=True, b_valid=True):
     arcs = _walk_arcs(ra, rb, WALK_A, mode, gaps) + _walk_arcs(rb, ra, WALK_B, mode, gaps)
     parts, status = stitch(arcs)
     return parts, status, (min(gaps) if gaps else None)
+
+
+def transition_gap(ka, row_a, kb, row_b, mode, kept_fn=None):
+    """What Rule 6 of gpk_polyclip.h conditions on, by the headers' own definition: a transition is a touch point, or a vertex of the
+    walked ring, where the kept-ness of the piece before differs from that of the piece after (a cut of rule 4, kept on both hands, is
+    none).  Returns the least distance between two distinct transition points of one segment of either walk, as a share of the segment
+    (a Fraction), None when no segment carries two.  `clip`'s third value is another thing: the least distance between ANY two cuts of a
+    segment, its own ends included.  kept_fn: the kept table (default: this module's)."""
+    kept_fn = kept if kept_fn is None else kept_fn
+    ra, rb = row_rings(ka, row_a), row_rings(kb, row_b)
+    best = None
+    for rings_w, rings_o, walk in ((ra, rb, WALK_A), (rb, ra, WALK_B)):
+        edges_o = _edges(rings_o)
+        for _m, hole, _c0, c in rings_w:
+            w = c if (_shoelace2(c) > 0) != hole else c[::-1]
+            segs, ip = [], 0  # per non-degenerate segment: [(t0, kept)] of its pieces
+            for iq in range(1, len(w)):
+                p, q = w[ip], w[iq]
+                if p == q:
+                    continue
+                ts = _cuts(p, q, edges_o)
+                pcs = []
+                for t0, t1 in zip(ts, ts[1:]):
+                    tm = (t0 + t1) / 2
+                    mid = (p[0] + tm * (q[0] - p[0]), p[1] + tm * (q[1] - p[1]))
+                    pcs.append((t0, kept_fn(_piece_class(mid, p, q, rings_o, edges_o), walk, mode)))
+                segs.append(pcs)
+                ip = iq
+            trans = [{pcs[k][0] for k in range(1, len(pcs)) if pcs[k][1] != pcs[k - 1][1]} for pcs in segs]
+            for s, pcs in enumerate(segs):  # the ring is closed: segment s - 1 ends where segment s begins
+                if segs[s - 1][-1][1] != pcs[0][1]:
+                    trans[s].add(Fraction(0))
+                    trans[s - 1].add(Fraction(1))
+            for here in trans:
+                ts = sorted(here)
+                for t0, t1 in zip(ts, ts[1:]):
+                    best = t1 - t0 if best is None else min(best, t1 - t0)
+    return best
+
+
+def scaled_back(parts, ka, row_a, kb, row_b, scale):
+    """A result of `clip` (or polyunion_ref.union) on rows that tests/hard_orient.on_integer_grid brought to an integer grid, in the
+    units of the doubles (scale = hard_orient.integer_grid_scale of the same rows, a power of two): parts -> rings -> coordinates
+    (TAG_IN, x, y, -1, -1) with x, y the doubles of the input coordinate, exactly — to be compared bit for bit — or
+    (TAG_X, x, y, edge of a, edge of b) with Fractions x, y and the two carrying edges as tag_point names them."""
+    if parts is None:
+        return None
+    ra, rb = row_rings(ka, row_a), row_rings(kb, row_b)
+    out = []
+    for p in parts:
+        rings = []
+        for r in p:
+            pts = []
+            for pt in r:
+                t, e0, e1 = tag_point((Fraction(pt[0]), Fraction(pt[1])), ra, rb)
+                x, y = Fraction(pt[0]) / scale, Fraction(pt[1]) / scale
+                if t == TAG_IN:
+                    assert Fraction(float(x)) == x and Fraction(float(y)) == y
+                    x, y = float(x), float(y)
+                pts.append((t, x, y, e0, e1))
+            rings.append(pts)
+        out.append(rings)
+    return out
+
+
+def shape_of(parts, ka, row_a, kb, row_b):
+    """what a wrong orientation sign changes in a result, as a hashable value: per part, per ring, per coordinate the number of the
+    input coordinate that stands there ("a" or "b" and its row-relative number), or "x" for a computed crossing"""
+    if parts is None:
+        return None
+    ra, rb = row_rings(ka, row_a), row_rings(kb, row_b)
+    where = {}
+    for name, rings in (("a", ra), ("b", rb)):
+        for _m, _h, c0, c in rings:
+            for k, v in enumerate(c[:-1]):
+                where.setdefault(v, (name, c0 + k))
+
+    def label(pt):
+        if pt[0].denominator == 1 and pt[1].denominator == 1 and (int(pt[0]), int(pt[1])) in where:
+            return where[(int(pt[0]), int(pt[1]))]
+        return "x"
+
+    return tuple(tuple(tuple(label(pt) for pt in r) for r in p) for p in parts)
+
+
+def counts_of(parts):
+    """(parts, rings, coordinates per ring with the closing one) of a result"""
+    return None if parts is None else (len(parts), sum(len(p) for p in parts), tuple(len(r) for p in parts for r in p))
+
+
+def check_rows(want, status_want, ca, cb, got, status=None):
+    """check_result for rows that are in no fixture file: `want[i]` is None (a null row) or the rings of scaled_back for row i of the
+    columns ca, cb, `got` the downloaded MULTIPOLYGON column.  Offsets, validity, status and ring starts exactly, input coordinates bit
+    for bit, crossings within REL_TOL * d of both carrying edges.  Returns (the worst ratio of a crossing's distance to its bound, the
+    number of crossings)."""
+    n = len(want)
+    assert got.n_geoms == n
+    gv = np.ones(n, dtype=bool) if got.validity is None else np.unpackbits(got.validity, bitorder="little")[:n].astype(bool)
+    wv = np.array([w is not None for w in want])
+    assert (gv == wv).all(), np.nonzero(gv != wv)[0][:10]
+    if status is not None:
+        assert (np.asarray(status) == np.asarray(status_want)).all(), np.nonzero(np.asarray(status) != np.asarray(status_want))[0][:10]
+    live = [w for w in want if w is not None]
+    n_parts = np.array([0 if w is None else len(w) for w in want])
+    assert (np.diff(got.geom_offsets) == n_parts).all(), np.nonzero(np.diff(got.geom_offsets) != n_parts)[0][:10]
+    n_rings = np.array([len(p) for w in live for p in w], dtype=np.int64)
+    assert (np.diff(got.part_offsets) == n_rings).all(), np.nonzero(np.diff(got.part_offsets) != n_rings)[0][:10]
+    sizes = np.array([len(r) for w in live for p in w for r in p], dtype=np.int64)
+    assert (np.diff(got.ring_offsets) == sizes).all(), np.nonzero(np.diff(got.ring_offsets) != sizes)[0][:10]
+    sa, sb, diag = _row_starts(ca), _row_starts(cb), pair_diagonals(ca, cb)
+    at, worst, n_x = 0, 0.0, 0
+    for i, w in enumerate(want):
+        for p in w or []:
+            for r in p:
+                for t, x, y, e0, e1 in r:
+                    g = got.xy[at]
+                    if t == TAG_IN:
+                        assert g.tobytes() == np.array([x, y], dtype=np.float64).tobytes(), (i, "an input coordinate is not returned bit for bit", g, (x, y))
+                    else:
+                        ia, ib = int(sa[i]) + e0, int(sb[i]) + e1
+                        far = max(float(_off_segment(g[None], ca.xy[ia][None], ca.xy[ia + 1][None])[0]), float(_off_segment(g[None], cb.xy[ib][None], cb.xy[ib + 1][None])[0]))
+                        worst, n_x = max(worst, far / (REL_TOL * diag[i])), n_x + 1
+                        assert far <= REL_TOL * diag[i], (i, far, diag[i])
+                    at += 1
+    assert at == len(got.xy)
+    return worst, n_x
 
 
 def area_of(parts) -> Fraction:

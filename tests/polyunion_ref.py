@@ -146,7 +146,14 @@ def union(ka, row_a, kb, row_b, mode=UNION, a_valid=True, b_valid=True):
     return parts, status, (min(gaps) if gaps else None)
 
 
+def transition_gap(ka, row_a, kb, row_b, mode=UNION):
+    """polyclip_ref.transition_gap with the kept table of the union: the least distance between two distinct transition points of one
+    segment, as a share of the segment; None when no segment carries two"""
+    return L.transition_gap(ka, row_a, kb, row_b, mode, kept_fn=kept)
+
+
 area_of, row_area = L.area_of, L.row_area
+scaled_back, shape_of, counts_of, check_rows = L.scaled_back, L.shape_of, L.counts_of, L.check_rows
 
 
 # ---- hand cases: (name, a, b, {mode: (rings per part, coordinates per ring — the closing one included —, status)}), stated by hand; None: what

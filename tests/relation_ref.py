@@ -58,6 +58,18 @@ def _ring_usable(r) -> bool:
     q = next((v[(k + j) % m] for j in range(1, m) if (v[(k + j) % m] != v[k]).any()), None)
     if p is None or q is None:
         return False
+    if any(abs(c) >= 2.0**26 for c in a.ravel()) and all(isinstance(c, int) for pt in r for c in pt):
+        # wide Python ints (rows of arbitrary doubles on one integer grid, tests/hard_orient.on_integer_grid): the doubles above round
+        # them, and the kernel's turn is exact — the same rule on the ints themselves
+        w = [(int(x), int(y)) for x, y in r][:-1]
+        if w[0] != (int(r[-1][0]), int(r[-1][1])):
+            return False
+        k = min(range(m), key=lambda i: (w[i][0], w[i][1], i))
+        p = next((w[(k - j) % m] for j in range(1, m) if w[(k - j) % m] != w[k]), None)
+        q = next((w[(k + j) % m] for j in range(1, m) if w[(k + j) % m] != w[k]), None)
+        if p is None or q is None:
+            return False
+        return (p[0] - w[k][0]) * (q[1] - w[k][1]) != (p[1] - w[k][1]) * (q[0] - w[k][0])
     return (p[0] - v[k][0]) * (q[1] - v[k][1]) != (p[1] - v[k][1]) * (q[0] - v[k][0])
 
 

@@ -7,7 +7,9 @@ device's CU count and fill it with a shuffled tiling of a small base column whos
 
 INVENTORY lists every capped launch site of geopolars_amd/csrc — a `cu_count()` written at the launch, or a call of the shared
 `group_grid` helper (gpk_common.h: 256 / G units a block, cu_count() * 32 blocks) — with the test that takes it past its cap;
-tests/test_second_pass_inventory.py (no GPU) fails when a source file gains or loses a site without the list following."""
+tests/test_second_pass_inventory.py (no GPU) fails when a source file gains or loses a site without the list following.
+FIXED_GRID_SITES lists the kernels launched on a fixed number of work-groups that loop over a device-side list, held to the sources
+in the same way."""
 from __future__ import annotations
 
 import os
@@ -153,6 +155,57 @@ INVENTORY = [
          "left out: its own stride needs more than cus * 16 * 64 (262 144 at 256 CUs) rows above 128 points; the kernel keeps nothing "
          "between rows (registers only, scratch addressed by the row)", exempt=True),
 ]
+
+
+class FixedSite(NamedTuple):
+    file: str  # where the constant is defined
+    constant: str  # the fixed number of work-groups the kernel is launched on
+    kernel: str
+    unit: str  # what one trip of the loop processes
+    test: str  # the test that lists more units than the grid has work-groups
+
+
+# Kernels on a FIXED grid (the device's CU count is not asked) that loop over a list whose length they read on the device: invisible to
+# the count above, the same gap — with up to `constant` listed units every work-group takes one and the loop's second trip, with whatever
+# the work-group carries in LDS from one unit to the next, never runs.
+FIXED_GRID_SITES = [
+    FixedSite("gpk_hausdorff.hip", "HD_LIST_BLOCKS", "hausdorff_large_kernel", "listed row (cost above HD_LARGE_COST)",
+              "tests/test_gpu_hausdorff.py::test_hausdorff_list_loop_past_its_first_pass"),
+    FixedSite("gpk_frechet.hip", "FR_LIST_BLOCKS", "frechet_large_kernel", "listed row (a table past the lane group's registers)",
+              "tests/test_gpu_hausdorff.py::test_frechet_list_loop_past_its_first_pass"),
+    FixedSite("gpk_knn.hip", "KNN_LIST_BLOCKS", "knn_select_list_kernel", "listed left row (candidates past the wave's keys)",
+              "tests/test_gpu_knn.py::test_list_kernel_past_its_first_pass"),
+    FixedSite("gpk_minbound.h", "MBG_BIG_BLOCKS", "the work-group kernels of gpk_minbound.hip", "listed row (a hull above MBG_SMALL_HULL vertices)",
+              "tests/test_gpu_minbound.py::test_work_group_loop_second_trip"),
+    FixedSite("gpk_pointrel.hip", "PT_LIST_BLOCKS", "point_relation_large_kernel", "listed unit (n_A * n_B above PT_LARGE_COST)",
+              "tests/test_gpu_pointrel.py::test_list_kernel_past_its_first_pass"),
+]
+
+
+def counted_fixed_sites() -> dict:
+    """{source file: [the fixed-grid constants it defines]} over geopolars_amd/csrc: every `constexpr ... X_LIST_BLOCKS | X_BIG_BLOCKS`"""
+    out = {}
+    for fn in sorted(os.listdir(CSRC)):
+        if fn.endswith((".hip", ".h", ".cpp")):
+            with open(os.path.join(CSRC, fn)) as f:
+                names = re.findall(r"constexpr\s+(?:unsigned|int)\s+(\w+_(?:LIST|BIG)_BLOCKS)\s*=", f.read())
+            if names:
+                out[fn] = sorted(names)
+    return out
+
+
+def fixed_inventory() -> dict:
+    out = {}
+    for s in FIXED_GRID_SITES:
+        out.setdefault(s.file, []).append(s.constant)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def fixed_grid(constant: str) -> int:
+    """the value of a fixed-grid constant, read from the source"""
+    site = next(s for s in FIXED_GRID_SITES if s.constant == constant)
+    with open(os.path.join(CSRC, site.file)) as f:
+        return int(re.search(rf"constexpr\s+(?:unsigned|int)\s+{constant}\s*=\s*(\d+)\s*;", f.read()).group(1))
 
 
 def counted_sites() -> dict:

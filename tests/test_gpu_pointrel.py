@@ -5,7 +5,7 @@ reference (tests/pointrel_ref.py; tests/test_pointrel_ref.py pins it).  Masks an
      ten names; 2. placements; 3. random lattice columns; 4. agreement with dwithin at 0, distance 0, gpk_predicate_rowwise, the line
      relation of [p, p], gpk_spatial_join and the dwithin join; 5. unusable rows and refused calls; 6. the join: nine predicates,
      count-only, pairs, masks, prebuilt and NULL index, left_row_base, capacity, device buffers, the punctual side on the right, both
-     sides punctual, a self-join; 7. pairs for the work-group schedule; 8. the table join and the sjoin router; 9. the older calls."""
+     sides punctual, a self-join; 7. pairs for the work-group schedule, and its list loop past the first pass; 8. the table join and the sjoin router; 9. the older calls."""
 import ctypes as C
 import os
 import re
@@ -437,6 +437,72 @@ def test_pairs_at_the_threshold(gpk):
     assert want.tolist() == [15, 9, 12, 10]  # (the last of the 256 points is the line's end)
     assert np.array_equal(series(MPT, A).point_relation(series(LS, B)), want)
     assert np.array_equal(series(PT, [a[0] for a in A[1:]]).point_relation(series(LS, B[1:])), want[1:])  # a POINT column lists nothing
+
+
+def list_loop_base():
+    """(A rows, B rows, base pairs as (row of A, row of B)) for test_list_kernel_past_its_first_pass: MULTIPOINT rows of 300, 280 and
+    257 points — no multiple of the 256 threads — against MULTILINESTRING rows: a zigzag of 400 coordinates (one chunk), one of 1100
+    (more than PT_CHUNK = 1024: staged in two chunks), and finite sets written as degenerate members [p, p] — a subset, a disjoint set,
+    an overlapping set of 150 points (300 coordinates) and all 300 points twice (1200 coordinates: a finite B in two chunks)"""
+    a = sorted(set(_cloud(400, 5)))[:300]
+    other = [p for p in sorted(set(_cloud(500, 6))) if p not in set(a)][:150]
+    assert len(a) == 300 and len(other) == 150
+    A = [a, _cloud(280, 21), a[:200] + _cloud(57, 22)]
+    as_members = lambda pts: [[p, p] for p in pts]  # noqa: E731
+    B = [[P.zigzag(400)], [P.zigzag(1100)], as_members(a[::2]), as_members(other), as_members(a[:149] + other[:1]), as_members(a + a)]
+    pairs = [(0, 0), (0, 1), (0, 2), (0, 3), (0, 4), (0, 5), (1, 0), (1, 1), (2, 1), (2, 5), (1, 3), (2, 2)]
+    return A, B, pairs
+
+
+def test_list_kernel_past_its_first_pass(gpk):
+    """point_relation_large_kernel runs on a fixed grid of PT_LIST_BLOCKS = 1024 work-groups and loops `e += gridDim.x` over the listed
+    units, with its PtLds (the staged chunk of B, its ends, the word the threads OR their bits into) carried from one unit to the
+    next; no other test lists more than ten units, so the loop's second trip never ran.  Here PT_LIST_BLOCKS + 293 units are listed,
+    ordered by second_pass.rotating_tiling over twelve base pairs.  The list is filled by atomic appends of the first kernel, so its
+    order is not the unit order and the tiling cannot promise that a work-group's second unit differs from its first: with twelve
+    mixed base pairs it is only very likely for nearly all of the 293.  Expected masks come from pointrel_ref on the twelve base
+    pairs alone.  That the units are listed rests on the reasoning below: the list's length stays on the device, no counter shows it.
+
+    Why pt::prepare settles none of them before listing (gpk_pointrel.h): both rows have finite coordinates; B is no polygon (no ring
+    rule); the boxes overlap (all of it lies in the cloud's square); and done(pre.mask, st) is false — pre.mask is 0 for a finite B
+    and B_OUTSIDE for the zigzags, and the stop is that of the full mask for the row-wise call and for a join that returns masks, and
+    {3, ALL} / {4, ALL} for the count-only `intersects` and `within`, which B_OUTSIDE = 8 does not meet.  n_A * n_B is above
+    PT_LARGE_COST for every pair (asserted), and the column is a MULTIPOINT column, so every unit is listed.  A finite B leaves the
+    first launch PENDING and makes two classify_workgroup calls in one trip."""
+    from tests import second_pass as SP
+
+    blocks = SP.fixed_grid("PT_LIST_BLOCKS")
+    assert blocks == 1024 and "constexpr int PT_CHUNK = 1024;" in open(os.path.join(ROOT, "geopolars_amd", "csrc", "gpk_pointrel.hip")).read()
+    cost = large_cost()
+    A, B, pairs = list_loop_base()
+    n_coords = lambda row: sum(len(m) for m in row)  # noqa: E731
+    assert all(len(A[i]) * n_coords(B[j]) > cost for i, j in pairs) and all(len(a) % 256 for a in A)
+    assert sorted(n_coords(b) for b in B) == [300, 300, 300, 400, 1100, 1200] and len(pairs) >= 8
+    table = np.array([[P.mask(MPT, a, MLS, b) for b in B] for a in A], dtype=np.uint8)
+    base = np.array([table[i, j] for i, j in pairs], dtype=np.uint8)
+    assert len(set(base.tolist())) >= 4, base.tolist()
+    n = SP.second_trip_rows(blocks, 1, 1)
+    assert n > blocks and n == 1317
+    order = SP.rotating_tiling(len(pairs), n, blocks)
+    ia, ib = np.array([pairs[k][0] for k in order]), np.array([pairs[k][1] for k in order], dtype=np.uint32)
+    ca, cb = X.column(MPT, A), X.column(MLS, B)
+    sa, sb = GeoSeries(ca.take(ia.astype(np.int64))), GeoSeries(cb)
+    got = sa.point_relation(sb, other_rows=ib)
+    bad = np.nonzero(got != base[order])[0]
+    assert len(bad) == 0, [(int(k), int(order[k]), int(got[k]), int(base[order[k]]), bool(k >= blocks)) for k in bad[:8]]
+    # the join's refine lists the same kind of units: 3 rows of A tiled to 440 against the 6 rows of B give 2640 candidates, all listed
+    reps = 440
+    ja = np.arange(3 * reps) % 3
+    sja = GeoSeries(ca.take(ja.astype(np.int64)))
+    assert 3 * reps * len(B) > 2 * blocks
+    for name in ("intersects", "within", "contains", "equals"):  # with masks: the full mask; count-only: the early stop
+        hit = np.vectorize(lambda m: P.PREDICATES[name](int(m), 1), otypes=[bool])(table)
+        p0 = np.array([(l, r) for l in range(3 * reps) for r in range(len(B)) if hit[ja[l], r]], dtype=np.uint32).reshape(-1, 2)
+        pairs_got, _, masks = point_relation_pairs(sja, sb, name)
+        assert 0 < len(p0) < 3 * reps * len(B) and np.array_equal(pairs_got, p0) and np.array_equal(masks, table[ja[p0[:, 0]], p0[:, 1]]), name
+        k = C.c_int64(-1)
+        rc = _abi.lib().gpk_point_relation_join(sja.device().handle, sb.device().handle, None, P.PRED_IDS[name], 0, None, None, None, 0, C.byref(k), _abi.MEM_HOST, None)
+        assert rc == _abi.GPK_OK and k.value == len(p0), name
 
 
 # ---- 8. the table join and the router ------------------------------------------------------------------------------------------------------------

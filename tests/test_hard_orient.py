@@ -4,20 +4,27 @@
   2. every column a GPU test uses has exactly the stated composition, survives the exact symmetries, and its far points are certain;
   3. the planted sign alone decides every family's answer, and each exact reference run with `sign(double determinant)` in place of
      its orientation gives another answer on at least half of the hard rows;
-  4. a census of the inexact fixtures the suite had before (printed, not asserted)."""
+  4. a census of the inexact fixtures the suite had before (printed, not asserted);
+  5. the figures for the constructive kernels (tests/hard_clip.py): composition, certainty of everything but the planted triple, the
+     transition gap by the headers' definition, one shape per exact sign, and different shapes for + and -."""
 import os
 import random
 import re
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from tests import exact_predicates as E
 from tests import exact_ref as X
+from tests import hard_clip as K
 from tests import hard_orient as H
+from tests import lineclip_ref as LC
 from tests import linerel_ref as L
 from tests import pointrel_ref as P
+from tests import polyclip_ref as C
 from tests import polyrel_ref as Y
+from tests import polyunion_ref as U
 from tests import relation_ref as R
 from tests import triangulate_ref as T
 from tests import validity_ref as V
@@ -297,6 +304,186 @@ def test_host_triangulation_of_hard_rows(drivers):
 
 
 from tests.test_triangulate_host import drivers  # noqa: E402,F401  (the fixture that builds the two host drivers)
+
+
+# ---- 5. the figures for the constructive kernels (tests/hard_clip.py; the GPU side is tests/test_gpu_hard_clip.py) ---------------------------------
+#
+# A "shape" is (status, (parts, rings, coordinates per ring with the closing one), which input coordinate or crossing stands where).
+
+
+def by_sign(ts, shapes):
+    """{exact sign of the planted triple: the set of shapes its rows have}, easy rows included"""
+    out = {}
+    for t, s in zip(ts, shapes):
+        out.setdefault(t.sign, set()).add(s)
+    return out
+
+
+def assert_column(ts, n_rows):
+    """the column keeps COMPOSITION (classified anew, without the collinear rows where the figure has none) and at least 96 rows are hard"""
+    want = H.stated_composition(H.N_ROWS)
+    if n_rows != H.N_ROWS:
+        assert n_rows == H.N_ROWS - want[H.COLLINEAR] == 168 and want[H.COLLINEAR] == 24
+        want = {k: v for k, v in want.items() if k != H.COLLINEAR}
+    assert len(ts) == n_rows and H.composition(ts) == want
+    assert [t.kind for t in ts] == [k for i in range(H.N_ROWS) for k in [H.COMPOSITION[i % 8]] if n_rows == H.N_ROWS or k != H.COLLINEAR]
+    assert sum(1 for t in ts if t.kind in H.HARD and H.classes(t.a, t.b, t.c) == "WWWWWW") >= 96
+
+
+def assert_only_planted_is_uncertain(t, rings_a, rings_b):
+    planted = {t.a, t.b, t.c}
+    for s, e, p in K.edge_vertex_evaluations(rings_a, rings_b):
+        if {s, e, p} != planted:
+            assert K.certain_and_off(s, e, p), (t, s, e, p)
+
+
+# figure -> form -> operation -> {sign: (parts, rings, coordinates per ring)}, stated by hand from the figures' docstrings
+COUNTS = {
+    ("pass", "short"): {"A&B": {1: (1, 1, (5,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))}, "B&A": {1: (1, 1, (5,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))},
+                        "A-B": {1: (1, 1, (8,)), 0: (1, 1, (7,)), -1: (1, 1, (7,))}, "B-A": {1: (1, 1, (5,)), 0: (1, 1, (5,)), -1: (1, 1, (6,))},
+                        "A|B": {1: (1, 1, (8,)), 0: (1, 1, (8,)), -1: (1, 1, (9,))}, "B|A": {1: (1, 1, (8,)), 0: (1, 1, (8,)), -1: (1, 1, (9,))}},
+    # the long ring has 44 more coordinates; they are all outside B
+    ("pass", "long"): {"A&B": {1: (1, 1, (5,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))}, "B&A": {1: (1, 1, (5,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))},
+                       "A-B": {1: (1, 1, (52,)), 0: (1, 1, (51,)), -1: (1, 1, (51,))}, "B-A": {1: (1, 1, (5,)), 0: (1, 1, (5,)), -1: (1, 1, (6,))},
+                       "A|B": {1: (1, 1, (52,)), 0: (1, 1, (52,)), -1: (1, 1, (53,))}, "B|A": {1: (1, 1, (52,)), 0: (1, 1, (52,)), -1: (1, 1, (53,))}},
+    # a far triangle is the first member of either row: one more part wherever its row is kept
+    ("pass", "multi"): {"A&B": {1: (1, 1, (5,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))}, "B&A": {1: (1, 1, (5,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))},
+                        "A-B": {1: (2, 2, (4, 8)), 0: (2, 2, (4, 7)), -1: (2, 2, (4, 7))}, "B-A": {1: (2, 2, (4, 5)), 0: (2, 2, (4, 5)), -1: (2, 2, (4, 6))},
+                        "A|B": {1: (3, 3, (4, 8, 4)), 0: (3, 3, (4, 8, 4)), -1: (3, 3, (4, 9, 4))}, "B|A": {1: (3, 3, (4, 8, 4)), 0: (3, 3, (4, 8, 4)), -1: (3, 3, (4, 9, 4))}},
+    # the box holds the ring: the same counts for either sign — the sign shows in the ORDER of the coordinates (below)
+    ("spike", "short"): {op: {1: c, -1: c} for op, c in {"A&B": (1, 1, (5,)), "B&A": (1, 1, (5,)), "A-B": (0, 0, ()), "B-A": (1, 2, (5, 5))}.items()},
+    ("nested", "short"): {op: {1: c, -1: c} for op, c in {"A&B": (1, 2, (4, 4)), "B&A": (1, 2, (4, 4)), "A-B": (0, 0, ()), "B-A": (2, 3, (5, 4, 4))}.items()},
+    ("hinge", "short"): {"A&B": {1: (1, 1, (4,)), 0: (0, 0, ()), -1: (0, 0, ())}, "B&A": {1: (1, 1, (4,)), 0: (0, 0, ()), -1: (0, 0, ())},
+                         "A-B": {1: (1, 1, (6,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))}, "B-A": {1: (1, 1, (4,)), 0: (1, 1, (4,)), -1: (1, 1, (4,))},
+                         "A|B": {1: (1, 1, (6,)), 0: (1, 1, (6,)), -1: (2, 2, (4, 4))}, "B|A": {1: (1, 1, (6,)), 0: (1, 1, (6,)), -1: (2, 2, (4, 4))}},
+}
+FIGURE_FORMS = [(f, form) for f in K.FORMS for form in K.FORMS[f]]
+
+
+@pytest.mark.parametrize("gen", GENS)
+@pytest.mark.parametrize("figure,form", FIGURE_FORMS, ids=[f"{f}-{form}" for f, form in FIGURE_FORMS])
+def test_clip_figures(figure, form, gen):
+    """what tests/test_gpu_hard_clip.py relies on, on the references alone: the column keeps COMPOSITION (the spike and the nested hole
+    without their 24 collinear rows, which are invalid polygons; nothing else is left out) and at least 96 rows are hard; only the
+    planted triple is uncertain among all (edge, vertex) evaluations of the two rows; the transitions of every segment are MIN_GAP
+    apart by the headers' own definition; every operation has status 0 or 2 and ONE shape per exact sign, stated above as counts; and
+    for intersection, difference and union the shapes of + and - differ in at least one operand order — a kernel that follows the sign
+    of the double determinant, wrong on the 96 hard rows, returns the other sign's shape there.  The nested hole is the exception:
+    its hole is inside its shell whatever the sign (that is what makes the row valid), so both signs have one shape, and the power
+    comes from the question itself: the crossing number of c against the shell with the double sign says `outside` on every hard row."""
+    ts, ka, A, kb, B = K.poly_rows(figure, gen, form)
+    assert_column(ts, 168 if figure in K.DROPS_COLLINEAR else 192)
+    for t, a, b in list(zip(ts, A, B))[: 16 if form == "long" else len(ts)]:  # (the arc of the long ring is one construction: a sample, as below)
+        assert_only_planted_is_uncertain(t, K.flat_rings(ka, a), K.flat_rings(kb, b))
+    differ = {}
+    for op in K.OPS_OF[figure]:
+        name = K.POLY_OPS[op][3]
+        got = K.poly_expected(figure, gen, form, op)
+        assert all(r.status in (C.ST_OK, C.ST_EMPTY) for r in got), (figure, form, gen, op)
+        gaps = K.poly_gaps(figure, gen, form, op)
+        assert all(g is None or g >= C.MIN_GAP for g in gaps), (figure, form, gen, op, min(g for g in gaps if g is not None))
+        shapes = by_sign(ts, [r.shape() for r in got])
+        assert all(len(v) == 1 for v in shapes.values()), (figure, form, gen, op, {s: len(v) for s, v in shapes.items()})
+        assert {s: next(iter(v))[1] for s, v in shapes.items()} == COUNTS[figure, form][op], (figure, form, gen, op)
+        differ[name] = differ.get(name, False) or shapes[1] != shapes[-1]
+    if figure == "nested":
+        assert not any(differ.values())
+        hard = [(t, a) for t, a in zip(ts, A) if t.kind in H.HARD]
+        assert len(hard) == 96 and all(naive_crossing_number(t.c, a[0]) <= 0 < C.ring_position(*H.on_integer_grid(t.c, a[0])) for t, a in hard)
+    else:
+        assert differ == {K.POLY_OPS[op][3]: True for op in K.OPS_OF[figure]}, (figure, form, gen, differ)
+
+
+def naive_crossing_number(pt, ring):
+    """polyclip_ref.ring_position with the sign of the double determinant in place of the exact cross product"""
+    inside = False
+    for a, b in zip(ring, ring[1:]):
+        s = H.naive(a, b, pt)
+        if s == 0 and min(a[0], b[0]) <= pt[0] <= max(a[0], b[0]) and min(a[1], b[1]) <= pt[1] <= max(a[1], b[1]):
+            return 0
+        if (a[1] > pt[1]) != (b[1] > pt[1]) and (b[1] > a[1]) == (s > 0):
+            inside = not inside
+    return 1 if inside else -1
+
+
+def test_spike_ring_turns_at_its_apex():
+    """the placement the spike ring needs, asserted with seqedit_ref and not assumed: the lexicographically smallest coordinate is the
+    apex a (index 0), its neighbours are b and c, so the turn gpk_orient_polygons takes is orient(b, a, c) — the planted triple —, on
+    the short ring and on the one of more than SHORT_RING coordinates; the exact shoelace sign (Fractions) is that turn's sign; and the
+    sign of the f64 shoelace sum, or of the double determinant, is wrong on every hard row"""
+    from tests import seqedit_ref as S
+
+    with open(os.path.join(H.CSRC, "gpk_seqedit.hip")) as f:
+        assert "constexpr int SHORT_RING = 256;" in f.read() and H.LONG_ARC + 5 > 256
+    for gen in GENS:
+        n_hard = 0
+        for t0 in H.triples(gen):
+            for long in (False, True):
+                t = H.spike_triple(t0, long)
+                ring = np.array(H.spike_row(t0, long)[0])
+                assert len(ring) == (H.LONG_ARC + 5 if long else 5) and t.kind == t0.kind and t.sign == t0.sign
+                s, v, u, w = S.ring_turn(ring)
+                assert (v, u, w) == (0, len(ring) - 2, 1) and tuple(ring[u]) == t.b and tuple(ring[v]) == t.a and tuple(ring[w]) == t.c
+                assert s == H.exact(t.b, t.a, t.c) == -t.sign
+                f = [(Fraction(float(x)), Fraction(float(y))) for x, y in ring]
+                area2 = sum(f[i][0] * f[i + 1][1] - f[i + 1][0] * f[i][1] for i in range(len(f) - 1))
+                assert (area2 > 0) - (area2 < 0) == s if t.kind != H.COLLINEAR else s == 0 != area2  # (a collinear row touches itself: s == 0, whatever its area)
+                if t.kind in H.HARD:
+                    assert H.naive(t.b, t.a, t.c) != s
+                    n_hard += not long
+        assert n_hard == 96
+
+
+LINE_SHAPES = {  # mode -> sign -> parts as ((tag, number of the coordinate) or "x" for a crossing): the line is [w, c, q1]
+    LC.INSIDE: {1: (((LC.TAG_L, 0), (LC.TAG_L, 1), "x"),), 0: (((LC.TAG_L, 0), (LC.TAG_L, 1)),), -1: (((LC.TAG_L, 0), "x"),)},
+    LC.OUTSIDE: {1: (("x", (LC.TAG_L, 2)),), 0: (((LC.TAG_L, 1), (LC.TAG_L, 2)),), -1: (("x", (LC.TAG_L, 1), (LC.TAG_L, 2)),)},
+}
+
+
+@pytest.mark.parametrize("long", [False, True], ids=["short", "long"])
+@pytest.mark.parametrize("gen", GENS)
+def test_line_clip_figure(gen, long):
+    """the line [w, c, q1] of the pass figure against A, for the four families: all 192 rows, the transitions apart, one shape per
+    exact sign — stated above; a MULTILINESTRING numbers its coordinates after the two of its far member, whose one part comes first
+    in the outside —, three different shapes in either mode"""
+    for kl, kp in K.LINE_FAMILIES:
+        ts, lines, polys = K.line_rows(gen, kl, kp, long)
+        assert_column(ts, 192)
+        if (kl, kp) == (LC.MLS, LC.MPG) or not long:
+            for t, l, p in zip(ts[: 16 if long else 192], lines, polys):
+                assert_only_planted_is_uncertain(t, K.flat_rings(kl, l), K.flat_rings(kp, p))
+        for mode in (LC.INSIDE, LC.OUTSIDE):
+            got = K.line_expected(gen, kl, kp, long, mode)
+            gaps = K.line_gaps(gen, kl, kp, long, mode)
+            assert all(g is None or g >= LC.MIN_GAP for g in gaps), (gen, kl, kp, mode)
+            shapes = by_sign(ts, [r.shape() for r in got])
+            assert all(len(v) == 1 for v in shapes.values())
+            k0 = 2 if kl == LC.MLS else 0
+            want = {s: tuple(tuple(e if e == "x" else (e[0], e[1] + k0) for e in pt) for pt in parts) for s, parts in LINE_SHAPES[mode].items()}
+            if kl == LC.MLS and mode == LC.OUTSIDE:
+                want = {s: (((LC.TAG_L, 0), (LC.TAG_L, 1)),) + parts for s, parts in want.items()}
+            assert {s: next(iter(v)) for s, v in shapes.items()} == want, (gen, kl, kp, mode)
+            assert len({next(iter(v)) for v in shapes.values()}) == 3
+
+
+def test_transition_gap_is_the_headers_definition():
+    """transition_gap counts points where kept-ness changes, a segment's own ends included when they are such points, and nothing else:
+    on the hand cases it is never above the references' own figures where both exist for a segment's inner cuts, it is None for a
+    ring kept whole, and on the pass figure it is the 0.04 .. 0.07 between c and the crossing of q2 -> w on A's edge while `clip`'s third value
+    — every cut of a segment, its ends included — is the 1e-17 between c and the crossing next to it"""
+    assert C.transition_gap(C.PG, [C.S10], C.PG, [C.sq(2, 2, 5, 5)], C.INTERSECTION) is None  # b inside a: no transition at all
+    assert C.transition_gap(C.PG, [C.S10], C.PG, [C.sq(5, 5, 15, 15)], C.INTERSECTION) is None  # one crossing an edge; the corner (10, 10) is kept on both hands
+    for mode in (C.INTERSECTION, C.DIFFERENCE):  # a bar across: both upright edges of the square are crossed at 4 and at 6 of 10
+        assert C.transition_gap(C.PG, [C.S10], C.PG, [C.sq(-2, 4, 12, 6)], mode) == Fraction(1, 5)
+    assert U.transition_gap(U.PG, [U.S10], U.PG, [U.sq(-2, 4, 12, 6)]) == Fraction(1, 5)
+    assert LC.transition_gap(LC.LS, [(-2, 5), (12, 5)], LC.PG, [C.S10], LC.INSIDE) == Fraction(10, 14)
+    assert LC.transition_gap(LC.LS, [(-3, 5), (0, 5), (4, 5)], LC.PG, [C.S10], LC.INSIDE) is None  # one transition, at the vertex (0, 5)
+    assert LC.transition_gap(LC.LS, [(-3, 5), (0, 5), (12, 5)], LC.PG, [C.S10], LC.INSIDE) == Fraction(10, 12)  # the vertex and the exit
+    t = next(t for t in H.triples("mixed") if t.kind == H.HARD_LEFT)
+    a, b = H.on_integer_grid(*H.pass_rows(t)[:2])
+    every_cut = C.clip(C.PG, a, C.PG, b, C.INTERSECTION)[2]
+    gap = C.transition_gap(C.PG, a, C.PG, b, C.INTERSECTION)
+    assert every_cut < Fraction(1, 10**12) and Fraction(1, 30) < gap < Fraction(1, 10)
 
 
 # ---- 4. census of the earlier fixtures ----------------------------------------------------------------------------------------------------------

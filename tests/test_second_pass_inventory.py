@@ -31,6 +31,19 @@ def test_inventory_names_tests_that_exist_and_size_from_the_device():
             assert "device_info()" in text and re.search(r"assert n\w* > ", m.group(0)), s.test
 
 
+def test_every_fixed_grid_site_is_registered_with_a_test_that_exists():
+    """a new `X_LIST_BLOCKS` / `X_BIG_BLOCKS` grid fails here until it is entered in second_pass.FIXED_GRID_SITES with the test that
+    lists more units than the grid has work-groups; the named test exists and sizes its list from the constant"""
+    assert SP.counted_fixed_sites() == SP.fixed_inventory() and len(SP.FIXED_GRID_SITES) == 5
+    for s in SP.FIXED_GRID_SITES:
+        assert SP.fixed_grid(s.constant) == 1024, s
+        path, name = s.test.split("::")
+        with open(os.path.join(ROOT, path)) as f:
+            text = f.read()
+        m = re.search(rf"^def {re.escape(name)}\(.*?(?=^def |^@pytest|\Z)", text, re.S | re.M)
+        assert m and re.search(r"BLOCKS", m.group(0)) and re.search(r"rotating_tiling|shuffled_tiling", m.group(0)), s.test
+
+
 def test_second_trip_rows():
     assert SP.second_trip_rows(256, 32, 64) == 256 * 32 * 64 * 5 // 4 + 37 and SP.second_trip_rows(8, 8, 1, extra=5) == 69
     with pytest.raises(AssertionError):
