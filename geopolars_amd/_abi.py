@@ -52,6 +52,7 @@ PCLIP_INTERSECTION, PCLIP_DIFFERENCE = 0, 1  # GPK_PCLIP_*: the two modes of gpk
 PCLIP_OK, PCLIP_TOUCH, PCLIP_EMPTY, PCLIP_NULL, PCLIP_UNRESOLVED = 0, 1, 2, 3, 4  # the row status of gpk_polygon_clip
 GEODESIC_AREA_SIGNED = 1  # GPK_GEODESIC_AREA_SIGNED
 PUNION_UNION = 0  # GPK_PUNION_*: the mode of gpk_polygon_union (its row status is PCLIP_*)
+PSYMDIFF_SYMMETRIC_DIFFERENCE = 0  # GPK_PSYMDIFF_*: the mode of gpk_polygon_symdiff (its row status is PCLIP_*)
 PP_INTERIORS, PP_BOUNDARIES, PP_A_OUTSIDE, PP_B_OUTSIDE = 1, 2, 4, 8  # GPK_PP_*: the bits of the polygon x polygon relation mask
 (PP_PRED_INTERSECTS, PP_PRED_WITHIN, PP_PRED_CONTAINS, PP_PRED_TOUCHES, PP_PRED_OVERLAPS, PP_PRED_EQUALS,
  PP_PRED_CONTAINS_PROPERLY) = range(7)  # GPK_PP_PRED_*
@@ -223,6 +224,7 @@ _PROTOS = {
     "gpk_line_clip": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
     "gpk_polygon_clip": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
     "gpk_polygon_union": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
+    "gpk_polygon_symdiff": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
     "gpk_union_all_pairs": (C.c_int32, [_VP, _VP, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, C.POINTER(C.c_int64), _VP]),
     "gpk_intersection_measure_join": (
         C.c_int32,

@@ -47,6 +47,7 @@ SOURCES = [
     "gpk_lineclip.hip",
     "gpk_polyclip.hip",
     "gpk_polyunion.hip",
+    "gpk_polysymdiff.hip",
     "gpk_lineline.hip",
     "gpk_pointrel.hip",
     "gpk_validity.hip",

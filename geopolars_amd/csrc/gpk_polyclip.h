@@ -93,6 +93,7 @@ GPK_LC_FN bool emitted_backwards(int walk, int mode) { return walk == WALK_B && 
 // The two tables as a type.  The crossing type, the cut test and the device walks take any rule of this shape (gpk_polyunion.h has
 // another one); without one they take this, and compile to what they were.
 struct ClipRule {
+    static constexpr bool DIRECTION_BY_CLASS = false;  // a walk is emitted one way throughout (gpk_polysymdiff.h has the other kind)
     static GPK_LC_FN bool kept(int cls, int walk, int mode) { return pc::kept(cls, walk, mode); }
     static GPK_LC_FN bool emitted_backwards(int walk, int mode) { return pc::emitted_backwards(walk, mode); }
 };
@@ -181,7 +182,10 @@ struct End {
     P2 far;       // an end INSIDE a segment p -> q of its walk (a crossing, a vertex of the other row): the segment's other end — p
                   // behind the start of an arc, q beyond its end, in the emitted direction; set by the run routines below, which know
                   // the segment.  (An end at a coordinate of the walked ring holds its own value here; ring_corners copies it and
-                  // nothing reads the copy, since such a corner is not `computed`.)
+                  // nothing reads the copy, since such a corner is not `computed`.)  At a crossing every arc end has its OWN far:
+                  // under the clip's and the union's rules one arc ends and one starts there; under a rule with directions by class
+                  // two end and two start (turn_to), the two of a walk with the two ends of that walk's segment, and stitch<true>
+                  // reads e.far of the arriving arc for the leftmost turn.
 };
 GPK_LC_FN End end_at_coord(P2 v) { return End{v.x, v.y, -1, -1, v}; }
 GPK_LC_FN End with_far(End id, P2 far) {
@@ -299,6 +303,86 @@ GPK_LC_FN void run_segment_end(Run& r, P2 p, P2 q, Sink& out) {
     r.prev_p = p;
 }
 
+// ---- the same machine under a rule whose DIRECTION goes by class (Rule::DIRECTION_BY_CLASS; gpk_polysymdiff.h) -------------------------
+// Such a rule keeps INTERIOR and EXTERIOR pieces alike and emits the INTERIOR ones backwards, so a kept run does not only begin and
+// end: it TURNS where the class changes, and an arc ends and another begins there with the same identity.  Run::depth is then the
+// LEVEL of the walk inside the other row — 1 for an INTERIOR piece at an exact class (a segment's begin, an input coordinate), 0 for
+// an EXTERIOR one, +1 / -1 at every proper crossing — and a kept piece is emitted backwards while the level is positive: as with
+// the depth above, two crossings closer than rounding that come out in the wrong order cannot invert the rest of the segment.
+// The sink has one more call, rekey(int key), made before end_arc of a backwards arc: the key of an arc is that of its start in the
+// EMITTED direction, which a backwards arc reaches last — the segment the walk is on when the arc ends, | 1 when it ends inside it.
+// A forwards and a backwards arc that start at the same point of the same walk thus share a key; the backwards one has ended
+// there, so it has the lower arc number and comes first (key_less).
+GPK_LC_FN int arc_key(int walk, int seg, bool inside) { return (walk == WALK_B ? KEY_WALK_B : 0) | (2 * seg + (inside ? 1 : 0)); }
+GPK_LC_FN int level_of(int cls) { return cls == CLS_INTERIOR ? 1 : 0; }
+// the class after a proper crossing with no vertex at the crossing point (the first half of crossing_type_by)
+GPK_LC_FN int class_after_crossing(int side_q, int ccw, bool hole) { return ((side_q * ccw > 0) != hole) ? CLS_INTERIOR : CLS_EXTERIOR; }
+
+// the open arc ends at `id` on segment p -> q (inside: strictly inside it, else at p)
+template <class Sink>
+GPK_LC_FN void turn_close(Run& r, End id, bool inside, P2 p, P2 q, int key, Sink& out) {
+    if (r.emit) {
+        const bool back = r.depth > 0;
+        if (inside) out.coord(P2{id.x, id.y});
+        if (back) out.rekey(key);
+        out.end_arc(with_far(id, q), inside ? p : r.prev_p, back ? ARC_BACKWARDS : 0);
+    }
+    r.any_break = true;
+    r.emit = false;
+}
+// The piece after `id` is kept or not (kept1) at level level1; cut: an arc end even where nothing else changes.  An arc that is
+// open ends at id when the run ends, turns round or is cut there, and one begins when the piece after is kept.
+template <class Sink>
+GPK_LC_FN void turn_to(Run& r, bool kept1, int level1, bool cut, End id, bool inside, P2 p, P2 q, int seg, int walk, Sink& out) {
+    const bool was = r.open;
+    const bool change = was != kept1 || (was && ((r.depth > 0) != (level1 > 0) || cut));
+    if (change && was) turn_close(r, id, inside, p, q, arc_key(walk, seg, inside), out);
+    r.depth = level1;
+    if (!change) return;
+    r.open = kept1;
+    if (!kept1) return;
+    if (r.stop) {  // second lap: no arc begins after the first break
+        r.open = false;
+        return;
+    }
+    out.begin_arc(with_far(id, p), q, arc_key(walk, seg, inside));
+    out.coord(P2{id.x, id.y});
+    r.emit = true;
+}
+// segment p -> q begins with a piece of class cls0; cut: p is a cut (is_cut_by of the piece before and cls0)
+template <class Rule, class Sink>
+GPK_LC_FN void turn_segment_begin(Run& r, int cls0, bool cut, P2 p, P2 q, int seg, int walk, int mode, Sink& out) {
+    const bool kept0 = Rule::kept(cls0, walk, mode);
+    if (!r.started) {
+        r.started = true;
+        r.head = r.open = kept0;
+        r.emit = false;
+        r.depth = level_of(cls0);
+        return;
+    }
+    turn_to(r, kept0, level_of(cls0), cut, end_at_coord(p), false, p, q, seg, walk, out);
+}
+// the vertex `id` of the other row on the open segment, with the exact classes of the pieces before and after it
+template <class Rule, class Sink>
+GPK_LC_FN void turn_at_vertex(Run& r, int before, int after, End id, P2 p, P2 q, int seg, int walk, int mode, Sink& out) {
+    turn_to(r, Rule::kept(after, walk, mode), level_of(after), is_cut_by<Rule>(before, after, walk, mode), id, true, p, q, seg, walk, out);
+}
+// a proper crossing into a piece of class `after`: the level moves, the run stays kept or dropped
+template <class Sink>
+GPK_LC_FN void turn_at_crossing(Run& r, int after, End id, P2 p, P2 q, int seg, int walk, Sink& out) {
+    turn_to(r, r.open, r.depth + (after == CLS_INTERIOR ? 1 : -1), false, id, true, p, q, seg, walk, out);
+}
+template <class Sink>
+GPK_LC_FN void turn_segment_end(Run& r, P2 p, P2 q, Sink& out) {
+    if (r.open && r.emit) out.coord(q);
+    r.prev_p = p;
+}
+// a run still open when the walk is back at the ring's first coordinate v0 (the start of segment seg0) ends there
+template <class Sink>
+GPK_LC_FN void turn_close_at_start(Run& r, P2 v0, int seg0, int walk, Sink& out) {
+    if (r.open) turn_close(r, end_at_coord(v0), false, v0, v0, arc_key(walk, seg0, false), out);
+}
+
 // ---- junctions -------------------------------------------------------------------------------------------------------------------
 // Where the ray J -> d lies when turning CLOCKWISE from the ray J -> r: 0: less than half a turn, 1: half a turn, 2: more, 3: a full
 // turn (the same ray).  r, d != J.
@@ -380,9 +464,11 @@ GPK_LC_FN void ring_corners(const Arc* arcs, const int* next, const P2* xy, int 
 // the ends of its two carrying segments (the order is monotone along a segment).  M is the lowest of the local minima — of two
 // coordinates ulps apart on one carrier exactly one is a local minimum, so the noise between them does not choose.  At an input
 // coordinate M every incident edge leaves into the closed right half plane and the ring is counter-clockwise iff the lowest-lying of
-// them is an outgoing one, whatever else touches M; the rays are the exact directions.  At a crossing M (no other ring passes through
-// it) the ring turns from the carrier p1 -> q1 to the carrier p2 -> q2, and the turn is the side of q2 against p1 -> q1: exact, and
-// independent of the rounded crossing.
+// them is an outgoing one, whatever else touches M; the rays are the exact directions.  At a crossing M the ring turns from the
+// carrier p1 -> q1 to the carrier p2 -> q2, and the turn is the side of q2 against p1 -> q1: exact, and independent of the rounded
+// crossing.  Under the clip's and the union's rules no other ring passes through a crossing.  Under a rule with junctions at
+// crossings (stitch<true>) a second ring does, in the OPPOSITE wedge of the two carriers: the corners handed over here are those of
+// this ring alone (ring_corners follows its links), so the turn is that of this ring's own wedge and the other ring does not enter.
 template <class Orient>
 GPK_LC_FN int ring_sign(const Arc* arcs, const int* next, const P2* xy, int first, int n_arcs, Orient orient) {
     auto local_min = [](const Corner& c) {
@@ -475,7 +561,11 @@ constexpr int ORDER_SHELL = 1 << 30;  // flag of an entry of the ring order: the
 // the number of its first arc, | ORDER_SHELL when the ring opens a part (the holes of a part follow its shell).  Returns ST_OK,
 // ST_TOUCH, ST_EMPTY (n == 0) or ST_UNRESOLVED (the counts are then 0).  innermost (gpk_polyunion.h; left off by the two modes
 // above): a hole goes to the enclosing shell that every other enclosing shell encloses, not to the first one in key order.
-template <class Orient>
+// CROSSINGS (gpk_polysymdiff.h; off for every rule under which at most one arc starts at a computed crossing): at a proper crossing
+// two arcs end and two start, all four with one identity and one value, and the leftmost turn runs there as well — from the
+// arriving carrier e_nb -> e.far the arc goes on along the one of the two halves of the other carrier whose end (s_nb) lies to the
+// LEFT of it: one exact sign of four input coordinates, the computed value is not read.
+template <bool CROSSINGS = false, class Orient>
 GPK_LC_FN int stitch(const Arc* arcs, int n, const P2* xy, Orient orient, int* next, int* ring_first, int* order, int* info, int& n_parts,
                      int& n_rings, int& n_coords, bool innermost = false) {
     n_parts = n_rings = n_coords = 0;
@@ -498,6 +588,9 @@ GPK_LC_FN int stitch(const Arc* arcs, int n, const P2* xy, Orient orient, int* n
                 }
                 junction = true;
                 if (A.e.ea < 0 && cw_before(P2{A.e.x, A.e.y}, A.e_nb, arcs[j].s_nb, arcs[best].s_nb, orient)) best = j;
+                if constexpr (CROSSINGS) {
+                    if (A.e.ea >= 0 && orient(A.e_nb, A.e.far, arcs[best].s_nb) <= 0 && orient(A.e_nb, A.e.far, arcs[j].s_nb) > 0) best = j;
+                }
             }
         }
         if (best < 0) return ST_UNRESOLVED;
@@ -645,11 +738,17 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
     double2 first_q = v0;
     int last_cls = 0;             // the class of the last piece of the segment before the current one
     int pp0 = 0, first_cls0 = 0;  // the position of the ring's first coordinate and the class of its first piece
+    int seg0 = rc0 - w.c0;        // the number of the ring's first segment (read under a rule with directions by class only)
+    (void)seg0;
     for (int lap = 0; lap < 2; ++lap) {
         if (lap == 1) {
             if (!run.head) {
                 // the ring's first piece is not kept: a run still open ends at the first coordinate
-                if (run.open && run.emit) out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, 0);
+                if constexpr (Rule::DIRECTION_BY_CLASS) {
+                    turn_close_at_start(run, lc::p2(v0), seg0, walk, out);
+                } else {
+                    if (run.open && run.emit) out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, 0);
+                }
                 return;
             }
             if (!run.any_break) {
@@ -664,7 +763,11 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                     p = q;
                 }
                 // (a ring that merely touches the other row at its first coordinate is cut there: one arc, but not closed in itself)
-                out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, pp0 == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first_cls0, walk, mode) ? 0 : ARC_WHOLE);
+                int whole = pp0 == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first_cls0, walk, mode) ? 0 : ARC_WHOLE;
+                if constexpr (Rule::DIRECTION_BY_CLASS) {
+                    if (Rule::backwards(first_cls0, walk, mode)) whole |= ARC_BACKWARDS;  // (the key stays: the ring starts at v0 either way)
+                }
+                out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, whole);
                 return;
             }
         }
@@ -685,9 +788,15 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
             if (!had) {
                 pp0 = pp;
                 first_cls0 = first;
+                seg0 = seg;
             }
-            run_segment_begin(run, Rule::kept(first, walk, mode), lc::p2(p), lc::p2(q), seg, walk, out);
-            if (had && pp == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first, walk, mode)) run_cut(run, end_at_coord(lc::p2(p)), false, lc::p2(p), lc::p2(q), seg, walk, out);
+            if constexpr (Rule::DIRECTION_BY_CLASS) {
+                turn_segment_begin<Rule>(run, first, had && pp == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first, walk, mode), lc::p2(p), lc::p2(q), seg, walk,
+                                         mode, out);
+            } else {
+                run_segment_begin(run, Rule::kept(first, walk, mode), lc::p2(p), lc::p2(q), seg, walk, out);
+                if (had && pp == GPK_LP_BOUNDARY && is_cut_by<Rule>(last_cls, first, walk, mode)) run_cut(run, end_at_coord(lc::p2(p)), false, lc::p2(p), lc::p2(q), seg, walk, out);
+            }
             if (lap == 1 && !run.open) return;  // the head (or the run into it) has ended
             if (lap == 1) run.stop = true;      // from here on the first break ends the walk
             const double lx = fmin(p.x, q.x), hx = fmax(p.x, q.x), ly = fmin(p.y, q.y), hy = fmax(p.y, q.y);
@@ -700,9 +809,13 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                     const double2 a = make_double2(e.a.x, e.a.y), b = make_double2(e.b.x, e.b.y);
                     if (e.kind == 0) {
                         const int after = piece_class<G>(O, other.p0, other.p1, a, q, lane), before = looking_back(piece_class<G>(O, other.p0, other.p1, a, p, lane));
-                        const int type = (Rule::kept(after, walk, mode) ? 1 : 0) - (Rule::kept(before, walk, mode) ? 1 : 0);
-                        if (type) run_transition(run, type, end_at_coord(e.a), lc::p2(p), lc::p2(q), seg, walk, out);
-                        else if (is_cut_by<Rule>(before, after, walk, mode)) run_cut(run, end_at_coord(e.a), true, lc::p2(p), lc::p2(q), seg, walk, out);
+                        if constexpr (Rule::DIRECTION_BY_CLASS) {
+                            turn_at_vertex<Rule>(run, before, after, end_at_coord(e.a), lc::p2(p), lc::p2(q), seg, walk, mode, out);
+                        } else {
+                            const int type = (Rule::kept(after, walk, mode) ? 1 : 0) - (Rule::kept(before, walk, mode) ? 1 : 0);
+                            if (type) run_transition(run, type, end_at_coord(e.a), lc::p2(p), lc::p2(q), seg, walk, out);
+                            else if (is_cut_by<Rule>(before, after, walk, mode)) run_cut(run, end_at_coord(e.a), true, lc::p2(p), lc::p2(q), seg, walk, out);
+                        }
                     } else if (!lp::vertex_at_crossing<G>(O.xy, other.c0, other.c1, p, q, lx, hx, ly, hy, a, b, lane)) {
                         int ccw;
                         bool hole;
@@ -714,12 +827,20 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
                         // the other walk sees as a vertex on its open segment: the same identity and value here)
                         const int own = vertex_at_crossing_index<G>(W.xy, w.c0, w.c1, p, q, lx, hx, ly, hy, a, b, lane);
                         const End id = own != 0x7fffffff ? end_at_coord(lc::p2(W.xy[own])) : End{x.x, x.y, ea, eb, x};
-                        run_transition(run, crossing_type_by<Rule>(cont::orient(a, b, q), ccw, hole, walk, mode), id, lc::p2(p), lc::p2(q), seg, walk, out);
+                        if constexpr (Rule::DIRECTION_BY_CLASS) {
+                            turn_at_crossing(run, class_after_crossing(cont::orient(a, b, q), ccw, hole), id, lc::p2(p), lc::p2(q), seg, walk, out);
+                        } else {
+                            run_transition(run, crossing_type_by<Rule>(cont::orient(a, b, q), ccw, hole, walk, mode), id, lc::p2(p), lc::p2(q), seg, walk, out);
+                        }
                     }
                     if (lap == 1 && !run.open) return;
                 }
             }
-            run_segment_end(run, lc::p2(p), lc::p2(q), out);
+            if constexpr (Rule::DIRECTION_BY_CLASS) {
+                turn_segment_end(run, lc::p2(p), lc::p2(q), out);
+            } else {
+                run_segment_end(run, lc::p2(p), lc::p2(q), out);
+            }
             last_cls = pq == GPK_LP_BOUNDARY ? piece_class<G>(O, other.p0, other.p1, q, p, lane) : (pq == GPK_LP_INTERIOR ? CLS_INTERIOR : CLS_EXTERIOR);
             p = q;
             pp = pq;
@@ -727,7 +848,11 @@ __device__ inline void walk_ring_group(const DevGeo& W, const RowRef& w, int rc0
         if (!seen) return;  // (cannot happen: a ring that passes ring_init has distinct coordinates)
     }
     // (the second lap found no exit where the first had one: cannot happen, both make the same decisions; close what is open)
-    if (run.open && run.emit) out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, 0);
+    if constexpr (Rule::DIRECTION_BY_CLASS) {
+        turn_close_at_start(run, lc::p2(v0), seg0, walk, out);
+    } else {
+        if (run.open && run.emit) out.end_arc(end_at_coord(lc::p2(v0)), run.prev_p, 0);
+    }
 }
 
 template <int G, class Rule = ClipRule, class Sink>

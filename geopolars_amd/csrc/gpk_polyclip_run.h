@@ -1,5 +1,6 @@
-// gpk_polyclip_run.h — the schedule that gpk_polygon_clip (gpk_polyclip.hip) and gpk_polygon_union (gpk_polyunion.hip) share: the
-// kernels and the host driver, over a rule type (pc::ClipRule, pu::UnionRule) that gives the kept table.  The count and fill kernels
+// gpk_polyclip_run.h — the schedule that gpk_polygon_clip (gpk_polyclip.hip), gpk_polygon_union (gpk_polyunion.hip) and
+// gpk_polygon_symdiff (gpk_polysymdiff.hip) share: the kernels and the host driver, over a rule type (pc::ClipRule, pu::UnionRule,
+// ps::SymdiffRule) that gives the kept table and, where Rule::DIRECTION_BY_CLASS, the direction of a piece.  The count and fill kernels
 // and the stitch kernel are instantiated per rule, so each call launches kernels that hold its own table only; the emit kernel does
 // not depend on the rule, nor do the checks, the staging, the totals and the offsets kernel it shares with gpk_line_clip
 // (gpk_clipcall.h).  Contract: include/geopolars_hip.h; the rules: gpk_polyclip.h, gpk_polyunion.h.
@@ -43,8 +44,11 @@ struct CountSink {
     __device__ __forceinline__ void begin_arc(pc::End, pc::P2, int) { ++arcs; }
     __device__ __forceinline__ void coord(pc::P2) { ++coords; }
     __device__ __forceinline__ void end_arc(pc::End, pc::P2, int) {}
+    __device__ __forceinline__ void rekey(int) {}
 };
 
+// BY_ARC (a rule with directions by class): an arc is backwards when its end says so, and has been given the key of its emitted start
+template <bool BY_ARC>
 struct FillSink {
     pc::Arc* arcs;  // the arc records
     double2* xy;    // the arc coordinates
@@ -66,7 +70,7 @@ struct FillSink {
         cur.e_nb = e_nb;
         cur.len = at - base - cur.c0;
         cur.flags = flags;
-        if (backwards) {  // the ends and the directions of the emitted arc
+        if (BY_ARC ? (flags & pc::ARC_BACKWARDS) != 0 : backwards) {  // the ends and the directions of the emitted arc
             const pc::End t = cur.s;
             cur.s = cur.e;
             cur.e = t;
@@ -79,6 +83,7 @@ struct FillSink {
         if (writer && arc < arc_end) arcs[arc] = cur;
         ++arc;
     }
+    __device__ __forceinline__ void rekey(int key) { cur.key = key; }
 };
 
 template <int G, class Rule>
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(256) void polygon_clip_fill_kernel(DevGeo a, DevGeo
     if (k >= n) return;
     const int aa = arc_start[k], ae = arc_start[k + 1];
     if (ae <= aa) return;  // (group-uniform: a pair without arcs writes nothing)
-    FillSink sink;
+    FillSink<Rule::DIRECTION_BY_CLASS> sink;
     sink.arcs = arcs;
     sink.xy = axy;
     sink.arc = aa;
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(256) void polygon_clip_fill_kernel(DevGeo a, DevGeo
     pc::walk_row_group<G, Rule>(b, rb, a, ra, a, b, pc::WALK_B, mode, o, lane, sink);
 }
 
-template <int G, bool INNERMOST>
+template <int G, bool INNERMOST, bool CROSSINGS>
 __global__ __launch_bounds__(256) void polygon_clip_stitch_kernel(int64_t n, int drop, const int32_t* __restrict__ arc_start,
                                                                   const int32_t* __restrict__ acoord_start, const pc::Arc* __restrict__ arcs,
                                                                   const double2* __restrict__ axy, int32_t* __restrict__ next, int32_t* __restrict__ ring_first,
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(256) void polygon_clip_stitch_kernel(int64_t n, int
     if (!active || lane != 0) return;
     int parts = 0, rings = 0, coords = 0, st = pc::ST_NULL;
     if (valid[k]) {
-        st = pc::stitch(table, na, (const pc::P2*)(axy + acoord_start[k]), lc::DevOrient{}, next + a0, ring_first + a0, order + a0, info + a0, parts, rings,
+        st = pc::stitch<CROSSINGS>(table, na, (const pc::P2*)(axy + acoord_start[k]), lc::DevOrient{}, next + a0, ring_first + a0, order + a0, info + a0, parts, rings,
                         coords, INNERMOST);
         if (st == pc::ST_UNRESOLVED) valid[k] = 0;
         if (st <= pc::ST_TOUCH && parts == 0) st = pc::ST_EMPTY;
@@ -268,7 +273,8 @@ int32_t polygon_clip_run(const RunNames& nm, bool mode_ok, const gpk_geoarray* a
         if (total_arcs > 0)
             GPK_LAUNCH_BY_G(nm.fill, (polygon_clip_fill_kernel<lp::LP_G_SMALL, Rule>), (polygon_clip_fill_kernel<lp::LP_G_LARGE, Rule>), a->d, b->d, in.a_rows,
                             in.b_rows, n, (int)mode, (const int32_t*)arc_start, (const int32_t*)acoord_start, arcs, axy);
-        GPK_LAUNCH_BY_G(nm.stitch, (polygon_clip_stitch_kernel<lp::LP_G_SMALL, INNERMOST>), (polygon_clip_stitch_kernel<lp::LP_G_LARGE, INNERMOST>), n, (int)drop,
+        GPK_LAUNCH_BY_G(nm.stitch, (polygon_clip_stitch_kernel<lp::LP_G_SMALL, INNERMOST, Rule::DIRECTION_BY_CLASS>),
+                        (polygon_clip_stitch_kernel<lp::LP_G_LARGE, INNERMOST, Rule::DIRECTION_BY_CLASS>), n, (int)drop,
                         (const int32_t*)arc_start, (const int32_t*)acoord_start, (const pc::Arc*)arcs, (const double2*)axy, next, ring_first, order, info, valid,
                         n_parts, n_rings, n_coords, keep, status);
         GPK_TRY(exclusive_scan_i32(n_parts, n, part_start, nullptr, tot_parts, s));

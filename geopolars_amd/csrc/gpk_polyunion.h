@@ -59,6 +59,7 @@ GPK_LC_FN bool emitted_backwards(int, int) { return false; }
 
 // the rule type the walks, pc::crossing_type_by and pc::is_cut_by take
 struct UnionRule {
+    static constexpr bool DIRECTION_BY_CLASS = false;
     static GPK_LC_FN bool kept(int cls, int walk, int mode) { return pu::kept(cls, walk, mode); }
     static GPK_LC_FN bool emitted_backwards(int walk, int mode) { return pu::emitted_backwards(walk, mode); }
 };

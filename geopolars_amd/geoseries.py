@@ -762,6 +762,17 @@ class GeoSeries:
         neutral element here (`union_all` drops such rows first).  Coordinates, status and shapes as `polygon_intersection`."""
         return self._polygon_clip("polygon_union", _abi.PUNION_UNION, other, other_rows, return_status, entry="gpk_polygon_union")
 
+    # ---- polygon x polygon symmetric difference (gpk_polysymdiff.hip) ---------------------------------
+    def polygon_symmetric_difference(self, other: "GeoSeries", other_rows=None, return_status: bool = False):
+        """The area exactly one of every row's polygon and other[other_rows[i]] covers (gpk_polygon_symdiff), as a MULTIPOLYGON
+        series: GeoPandas' symmetric_difference on polygon columns, the area part only.  Equal polygons give a valid row without
+        parts, neighbours that share an edge their union, a polygon strictly inside the other a hole (to the innermost shell around
+        it); where the boundaries cross, a \\ b and b \\ a touch at the crossing and stay separate rings.  A null row where
+        `polygon_union` gives one — an empty row is not the neutral element.  Coordinates, status and shapes as
+        `polygon_intersection`."""
+        return self._polygon_clip("polygon_symmetric_difference", _abi.PSYMDIFF_SYMMETRIC_DIFFERENCE, other, other_rows, return_status,
+                                  entry="gpk_polygon_symdiff")
+
     def union_all(self, by=None, return_status: bool = False):
         """The union of the polygons of every group, one MULTIPOLYGON row per group in ascending group id (GeoPandas union_all /
         dissolve); `by`: an integer array, one entry per row (None: one group).  A tree reduction over gpk_polygon_union: rows that
@@ -1568,7 +1579,7 @@ def _as_multipolygon(host: GeoArrowArray) -> GeoArrowArray:
 
 def polygon_clip_call(a, b, a_rows, b_rows, n_rows: int, rows_space: int, mode: int, flags: int, out_src, src_space: int, out_status=None,
                       status_space: int = MEM_HOST, stream=None, entry: str = "gpk_polygon_clip") -> GeoSeries:
-    """gpk_polygon_clip (or, as `entry`, gpk_polygon_union, which takes the same arguments) on two DeviceGeoArrays and raw row-list /
+    """gpk_polygon_clip (or, as `entry`, gpk_polygon_union / gpk_polygon_symdiff, which take the same arguments) on two DeviceGeoArrays and raw row-list /
     output pointers: the owned MULTIPOLYGON result as a device-resident series"""
     h = C.c_void_p()
     _abi.check(getattr(_abi.lib(), entry)(a.handle, b.handle, a_rows, b_rows, n_rows, rows_space, mode, flags, out_src, src_space, out_status,

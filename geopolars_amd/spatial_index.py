@@ -1044,8 +1044,8 @@ def polygon_clip_pairs(a: GeoSeries, b: GeoSeries, l_idx, r_idx, how: str = "int
 
 
 def _polygon_pairs(entry: str, mode: int, a: GeoSeries, b: GeoSeries, l_idx, r_idx, drop_empty: bool, return_status: bool):
-    """polygon_clip_pairs / polygon_union_pairs once the mode and the families are checked"""
-    label = "polygon clip" if entry == "gpk_polygon_clip" else "polygon union"
+    """polygon_clip_pairs / polygon_union_pairs / polygon_symdiff_pairs once the mode and the families are checked"""
+    label = {"gpk_polygon_clip": "polygon clip", "gpk_polygon_union": "polygon union"}.get(entry, "polygon symmetric difference")
     try:
         li, ri = np.ascontiguousarray(l_idx, dtype=np.uint32), np.ascontiguousarray(r_idx, dtype=np.uint32)
     except (TypeError, ValueError, OverflowError):
@@ -1104,6 +1104,40 @@ def polygon_union_pairs_device(a: DeviceGeoArray, b: DeviceGeoArray, a_rows, b_r
     n = a_rows.shape[0] if a_rows is not None else (b_rows.shape[0] if b_rows is not None else a.n_geoms)
     return polygon_clip_call(a, b, _ptr(a_rows), _ptr(b_rows), n, MEM_DEVICE, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0, _ptr(out_src), MEM_DEVICE,
                              _ptr(out_status), MEM_DEVICE, stream, entry="gpk_polygon_union")
+
+
+# ---- polygon x polygon symmetric difference over a pair list (gpk_polygon_symdiff) -------------------------------------------------------
+
+PSYMDIFF_MODES = {"symmetric_difference": _abi.PSYMDIFF_SYMMETRIC_DIFFERENCE}
+
+
+def polygon_symdiff_mode_arg(how: str, a_family: int, b_family: int) -> int:
+    """The GPK_PSYMDIFF_* mode of `how`, checked before any device call together with the families: polygons x polygons."""
+    if how not in PSYMDIFF_MODES:
+        raise _abi.GeopolarsHipError(_abi.GPK_ERR_INVALID_ARGUMENT,
+                                     f"polygon symmetric difference: unknown how {how!r}: one of {sorted(PSYMDIFF_MODES)}")
+    if a_family not in POLYGONAL or b_family not in POLYGONAL:
+        raise _mismatch("polygon symmetric difference: Polygon | MultiPolygon x Polygon | MultiPolygon "
+                        f"(found {_abi_name(a_family)} x {_abi_name(b_family)})")
+    return PSYMDIFF_MODES[how]
+
+
+def polygon_symdiff_pairs(a: GeoSeries, b: GeoSeries, left, right, drop_empty: bool = False, return_status: bool = False,
+                          how: str = "symmetric_difference"):
+    """symmetric_difference(a[left[k]], b[right[k]]) for every pair k, as a MULTIPOLYGON GeoSeries (gpk_polygon_symdiff): what
+    a.polygon_symmetric_difference gives row-wise, over an explicit pair list.  Arguments, `drop_empty`, `return_status` and the
+    returned tuple as polygon_clip_pairs."""
+    mode = polygon_symdiff_mode_arg(how, a._family(), b._family())
+    return _polygon_pairs("gpk_polygon_symdiff", mode, a, b, left, right, drop_empty, return_status)
+
+
+def polygon_symdiff_pairs_device(a: DeviceGeoArray, b: DeviceGeoArray, left, right, drop_empty: bool = False, out_src=None, out_status=None,
+                                 stream: int = 0, how: str = "symmetric_difference") -> GeoSeries:
+    """Device-buffer variant, shaped like polygon_clip_pairs_device."""
+    mode = polygon_symdiff_mode_arg(how, a.geom_type, b.geom_type)
+    n = left.shape[0] if left is not None else (right.shape[0] if right is not None else a.n_geoms)
+    return polygon_clip_call(a, b, _ptr(left), _ptr(right), n, MEM_DEVICE, mode, _abi.CLIP_DROP_EMPTY if drop_empty else 0, _ptr(out_src), MEM_DEVICE,
+                             _ptr(out_status), MEM_DEVICE, stream, entry="gpk_polygon_symdiff")
 
 
 @dataclass

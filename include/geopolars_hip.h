@@ -983,6 +983,30 @@ int32_t gpk_polygon_union(const gpk_geoarray* a, const gpk_geoarray* b, const ui
 int32_t gpk_union_all_pairs(const int32_t* group, const uint32_t* rows, int64_t n, int64_t base, uint32_t* a_rows, uint32_t* b_rows,
                             int32_t* next_group, uint32_t* next_rows, int64_t* out_counts, void* stream);
 
+/* ---- polygon x polygon symmetric difference (gpk_polysymdiff.hip) -----------------------------------------------------------------------
+ * The area exactly one of two polygonal rows covers: GeoPandas GeoSeries.symmetric_difference on polygon columns, area part only.
+ * csrc/gpk_polysymdiff.h has the rule: that of gpk_polygon_clip with another kept table, a direction per piece, the leftmost turn at
+ * proper crossings as well, and the union's choice of a hole's shell. */
+#define GPK_PSYMDIFF_SYMMETRIC_DIFFERENCE 0   /* closure of (int(a) \ b) ∪ (int(b) \ a) */
+/* Output row k = symmetric_difference(a[a_rows[k]], b[b_rows[k]]), k < n_rows.  The 14 arguments are those of gpk_polygon_clip, in the
+ * same order and with the same meaning, and so is everything but what the mode computes: the families (POLYGON | MULTIPOLYGON on both
+ * sides, else GPK_ERR_MISMATCHED_GEOMETRY), the row lists, GPK_CLIP_DROP_EMPTY with out_src, out_status 0 to 4, the refusals — every
+ * one in the clip's order and before any device work —, the two waits, the i32 offset overflow error, the owned MULTIPOLYGON column,
+ * ring orientation, and the contract on coordinates: input coordinates bit for bit, crossings within 1e-9 * d of both carrying edges,
+ * the gap of 1e-6 * |segment|, below which a row is within 1e-9 * d or null with status 4.  No covered-by claim is made.  Any other
+ * mode: GPK_ERR_INVALID_ARGUMENT.
+ *   result equal polygons give an empty row (status 2, zero parts).  Neighbours that share an edge give their union.  b strictly inside
+ *          a gives a with b as a hole; a hole goes to the INNERMOST shell that encloses it (a hole of b is a shell inside that hole).
+ *          Where the two boundaries cross properly, a \ b and b \ a touch at the crossing and stay separate rings, all of which carry
+ *          the one value of that crossing.  A ring starts at its arc with the smallest key, the key of an arc being that of its start
+ *          in the direction in which it is emitted (pieces of one boundary inside the other row are emitted backwards).
+ *   null   for the same input conditions as gpk_polygon_clip.  That includes a row without a coordinate on either side, as in the
+ *          union: an empty row is NOT treated as the neutral element.
+ * The result is identical at every placement, for every lane-group size and on every schedule. */
+int32_t gpk_polygon_symdiff(const gpk_geoarray* a, const gpk_geoarray* b, const uint32_t* a_rows, const uint32_t* b_rows, int64_t n_rows,
+                            int32_t rows_space, int32_t mode, int32_t flags, int32_t* out_src, int32_t src_space, uint8_t* out_status,
+                            int32_t status_space, void* stream, gpk_geoarray** out);
+
 /* ---- line x line relations (gpk_lineline.hip) ---------------------------------------------------------------------------------------
  * How two lineal geometries lie to each other.  A, B = LINESTRING or MULTILINESTRING rows, each the closed point set of all its
  * segments and coordinates.  Boundary (the mod-2 rule): every non-empty member of a row counts its first and its last coordinate once
